@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py — the rollout hot path on N MI355X GPUs of one node (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: re-executes itself under the one below)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                     (N > 1 without a launcher: starts the one below as a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,6 +25,14 @@ cache planes with fp32 arithmetic, greedy. The other BASELINE configs are timed 
     c2_greedy_fp16  configs[1] in the reference's default precision           step incl. the RCCL grad all-reduce
     c2_greedy_fp32  configs[1] in the BIT-IDENTICAL configuration (fp32 MFMA encoder, fp32 planes), with the count of
                     reference tours it reproduces on the trained weights (``parity_tours``)
+
+A PLAIN RUN (no ``--full``) does what the headline figure needs and nothing else: set up the headline leg, warm it up, time
+its K steps in ONE region, write its outputs if ``--dump-outputs`` is given, print the line. ``--full`` adds everything
+described below: the further legs (``--legs``), five regions per leg, the HIP-event pass and the rooflines, the one-graph /
+eager timings, the HBM stream ceiling and the large-batch probe, parity, the CPU baseline, the N = 1 reference region of a
+multi-rank run, and the detail file. ``--dump-outputs DIR``: what the headline leg's last timed step returned (rewards,
+log-likelihoods, actions) as ``DIR/<name>.npy`` in float32 / float64 (integers exact in float64), at most 64 MB; the same
+arguments give the same inputs (seeded weights and instances), so two builds can be compared output for output.
 
 THE STDOUT LINE IS <= 4 KB (the driver parses it; r03's 27 KB line came back ``parsed: null``): the contract keys, the
 decode kernel's ``roofline`` {kernel, bound, achieved, peak, unit, frac, traffic, launch_ms_mean}, ``encoder_roofline``,
@@ -90,6 +99,7 @@ LEGS = {
     "c5_sampling_fp16": ("cvrp", 500, 1024, "sampling", 4),
 }
 DEFAULT_LEGS = "c2_greedy,c2_sampling,c3_greedy,c5_sampling,c4_train,c2_greedy_fp16,c2_greedy_fp32"
+PLAIN_LEGS = "c2_greedy"  # a run without --full: the headline leg alone
 
 
 def leg_dtypes(leg: str, args) -> tuple[str, str]:
@@ -250,6 +260,35 @@ TRAIN_PMC_FILE = "r06_c4_train_pmc.json"  # counters of the training kernels as 
 MAX_LINE_BYTES = 4096  # the driver parses the ONE stdout line; r03's 27 KB line came back as `parsed: null`
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def host_outputs(out) -> dict:
+    """The arrays a caller of the timed path receives from one step (the policy's output dict: rewards, log-likelihoods,
+    actions), as host numpy arrays: floating tensors in float32 (float64 stays float64), integer ones in float64 (exact)."""
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            wide = v.dtype == torch.float64 or not v.is_floating_point()
+            arrays[k] = v.to(torch.float64 if wide else torch.float32).cpu().numpy()
+    return arrays
+
+
+def dump_outputs(arrays: dict, out_dir: str) -> None:
+    """DIR/<name>.npy per array; above DUMP_BUDGET_BYTES in all, every array keeps the same fixed, seeded sample of its
+    rows (the same arguments always give the same files)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES and a.ndim and a.shape[0] > 1:
+            keep = max(1, a.shape[0] * DUMP_BUDGET_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def _r(x, digits=4):
     """Numbers of the compact line carry a few significant digits (the detail file keeps the full values)."""
     if isinstance(x, float):
@@ -322,7 +361,8 @@ def compact_line(detail: dict, head_name: str, results: dict, detail_path: str) 
         # what really runs before the clock starts (the echoed `warmup` is only the first group of it)
         "untimed_steps": detail.get("untimed_steps"), "untimed_extra": "1 s HBM read loop before the first leg",
     }
-    line["roofline"] = compact_roofline(detail.get("roofline"))
+    if detail.get("roofline"):
+        line["roofline"] = compact_roofline(detail["roofline"])
     if detail.get("encoder_roofline"):
         line["encoder_roofline"] = compact_roofline(detail["encoder_roofline"])
     for k in ("node_steps_per_sec", "instances_per_sec", "graph_ms_per_step", "eager_ms_per_step", "train_ms_per_step", "rccl_ranks",
@@ -370,6 +410,7 @@ class Bench:
         self.cache_dtype = torch.bfloat16 if args.cache_dtype == "bf16" else torch.float32
         self.enc_dtype = torch.bfloat16 if args.encoder_dtype == "bf16" else None
         self.elem = 2 if args.cache_dtype == "bf16" else 4
+        self.outputs = {}  # leg -> the host copies of what its last timed step returned (--dump-outputs)
 
     def barrier(self) -> None:
         torch.cuda.synchronize()
@@ -425,21 +466,23 @@ class Bench:
                 out = step()
             torch.cuda.synchronize()
             eager_ms = None
+            decode_ms, encode_ms = [], []  # (without --full no kernel is bracketed by events: no roofline)
             if use_graph:
-                # kernel durations for the roofline: an eager pass with HIP events around the two big launches (events
-                # cannot bracket nodes of a captured graph); the timed region below replays the SAME launches as one graph
                 ev_steps = max(10, steps // 8)
-                policy.decode_events, policy.encode_events = [], []
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(ev_steps):
-                    step()
-                torch.cuda.synchronize()
-                eager_ms = (time.perf_counter() - t0) / ev_steps * 1e3
-                untimed += ev_steps
-                decode_ms = [x.elapsed_time(y) for x, y in policy.decode_events]
-                encode_ms = [x.elapsed_time(y) for x, y in policy.encode_events]
-                policy.decode_events = policy.encode_events = None
+                if a.full:
+                    # kernel durations for the roofline: an eager pass with HIP events around the two big launches (events
+                    # cannot bracket nodes of a captured graph); the timed region below replays the SAME launches as one graph
+                    policy.decode_events, policy.encode_events = [], []
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(ev_steps):
+                        step()
+                    torch.cuda.synchronize()
+                    eager_ms = (time.perf_counter() - t0) / ev_steps * 1e3
+                    untimed += ev_steps
+                    decode_ms = [x.elapsed_time(y) for x, y in policy.decode_events]
+                    encode_ms = [x.elapsed_time(y) for x, y in policy.encode_events]
+                    policy.decode_events = policy.encode_events = None
                 from rl4co_amd.graph import GraphedRollout
 
                 try:
@@ -449,15 +492,16 @@ class Bench:
                         out = step()
                     untimed += max(2, warmup)
                     if a.launch == "pipeline":
-                        # one stream first (reported as graph_ms_per_step), then two captured rollouts in flight on two
-                        # streams: the next batch's launches fill the CUs this batch's finishing decode waves release
-                        torch.cuda.synchronize()
-                        t0 = time.perf_counter()
-                        for _ in range(ev_steps):
-                            step()
-                        torch.cuda.synchronize()
-                        graph_ms = (time.perf_counter() - t0) / ev_steps * 1e3
-                        untimed += ev_steps
+                        # (--full) one stream first (reported as graph_ms_per_step), then two captured rollouts in flight on
+                        # two streams: the next batch's launches fill the CUs this batch's finishing decode waves release
+                        if a.full:
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            for _ in range(ev_steps):
+                                step()
+                            torch.cuda.synchronize()
+                            graph_ms = (time.perf_counter() - t0) / ev_steps * 1e3
+                            untimed += ev_steps
                         from rl4co_amd.graph import PipelinedRollout
 
                         pipe = PipelinedRollout(policy, env, data, decode_type=decode, depth=a.pipeline_depth)
@@ -478,8 +522,9 @@ class Bench:
                     log(f"{leg}: HIP graph capture failed ({type(exc).__name__}: {exc}); timing the eager path")
                     use_graph = False
                     torch.cuda.synchronize()
-                    policy.decode_events, policy.encode_events = [], []
-            else:
+                    if a.full:
+                        policy.decode_events, policy.encode_events = [], []
+            elif a.full:
                 policy.decode_events, policy.encode_events = [], []
             gc.collect()
             gc.freeze()  # (see train_leg: a full collection over torch's module graph is a 60 ms host stall)
@@ -489,7 +534,7 @@ class Bench:
             for _ in range(warmup):
                 out = step()
             untimed += warmup
-            if not use_graph:  #  the eager leg's kernel durations come from the timed regions only, as in train_leg
+            if not use_graph and a.full:  #  the eager leg's kernel durations come from the timed regions only, as in train_leg
                 torch.cuda.synchronize()
                 policy.decode_events, policy.encode_events = [], []
             pipelined = use_graph and a.launch == "pipeline"
@@ -524,7 +569,7 @@ class Bench:
                 return time.perf_counter() - t0, rows_, steps_, o_last
 
             solo_ms = None
-            if self.world > 1 and a.solo:
+            if self.world > 1 and a.solo and a.full:
                 # the N = 1 reference of THIS invocation: rank 0 runs the same K steps alone while the other ranks wait at
                 # the barrier — weak scaling, so efficiency = that time / the joint time
                 self.barrier()
@@ -539,9 +584,12 @@ class Bench:
             region_ms = [own_wall / steps * 1e3]
             for _ in range(a.regions - 1):
                 self.barrier()
-                region_ms.append(region(steps)[0] / steps * 1e3)
+                w_, _, _, out = region(steps)
+                region_ms.append(w_ / steps * 1e3)
             self.barrier()
-        if not use_graph:
+            if a.dump_outputs:  # what the last timed step returned, copied off the clock
+                self.outputs[leg] = host_outputs(out)
+        if not use_graph and a.full:
             decode_ms = [x.elapsed_time(y) for x, y in policy.decode_events]
             encode_ms = [x.elapsed_time(y) for x, y in policy.encode_events]
             policy.decode_events = policy.encode_events = None
@@ -568,15 +616,7 @@ class Bench:
             if solo_ms is not None:
                 res["n1_ms_per_step"] = solo_ms
                 res["scaling_efficiency"] = solo_ms / (wall / steps * 1e3)
-        mean_decode_ms = sum(decode_ms) / len(decode_ms)
         per_launch_rows, per_launch_steps = rows / steps, inst_steps / steps
-        need = must_move_bytes(env_name, n_nodes, elem, per_launch_rows, per_launch_steps, batch,
-                               ctx_elem=int(getattr(policy, "last_ctx_elem_bytes", 4)))
-        contract = algorithmic_bytes_per_instance_step(env_name, n_nodes, elem) * per_launch_steps
-        achieved = need / (mean_decode_ms * 1e-3) / 1e9
-        traffic, traffic_source = self.traffic(leg)
-        variant = {1: "STREAM (1 wave / trajectory)", 2: "LDS-resident", 3: "WIDE (4 waves / trajectory)", 4: "MS"}.get(
-            K.decode_variant(n_nodes, cache_dtype, t_steps, batch), "?")
         value = total_inst_steps / wall
         res.update({
             "workload": (f"BASELINE configs[{cfg_idx}]: {env_name.upper()}Env num_loc={num_loc} batch={batch}/GPU "
@@ -600,6 +640,18 @@ class Bench:
             "instances_per_sec": batch * self.world * steps / wall,
             "decode_steps_longest": t_steps, "instance_steps_per_launch": per_launch_steps,
             "mean_reward": float(out["reward"].mean()),
+        })
+        if not decode_ms:  # a run without --full: no kernel durations, no rooflines, no parity count
+            return res
+        mean_decode_ms = sum(decode_ms) / len(decode_ms)
+        need = must_move_bytes(env_name, n_nodes, elem, per_launch_rows, per_launch_steps, batch,
+                               ctx_elem=int(getattr(policy, "last_ctx_elem_bytes", 4)))
+        contract = algorithmic_bytes_per_instance_step(env_name, n_nodes, elem) * per_launch_steps
+        achieved = need / (mean_decode_ms * 1e-3) / 1e9
+        traffic, traffic_source = self.traffic(leg)
+        variant = {1: "STREAM (1 wave / trajectory)", 2: "LDS-resident", 3: "WIDE (4 waves / trajectory)", 4: "MS"}.get(
+            K.decode_variant(n_nodes, cache_dtype, t_steps, batch), "?")
+        res.update({
             "roofline": {
                 "kernel": f"am_decode kernel, {variant}: fused persistent rollout, all decode steps in one launch",
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
@@ -640,7 +692,7 @@ class Bench:
                         ("" if (exact or n_nodes <= 128) else "; the attention launches (59 % of the time) are exp-issue bound: "
                          f"{layers_ * 8 * n_ * n_ * batch / 1e9:.1f} G exponentials per pass at a quarter of the VALU rate"),
             }
-        if full and self.world == 1 and not a.no_parity:
+        if full and self.world == 1 and a.full and not a.no_parity:
             TP = _trained_parity()
 
             try:
@@ -773,6 +825,8 @@ class Bench:
             region_ms.append((time.perf_counter() - t0) / steps * 1e3)
             if r == 0:
                 own_wall, out = time.perf_counter() - t0, o
+        if self.args.dump_outputs:  # what the last timed step returned, copied off the clock
+            self.outputs["c4_train"] = host_outputs(o)
         self.barrier()
         policy.check_backward_errors()
         wall = D.reduce_scalar(own_wall, "max", self.device)
@@ -969,7 +1023,8 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000, help="timed steps of the headline leg (3.5 s of GPU time at the default)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--legs", default=DEFAULT_LEGS, help=f"comma-separated subset of {sorted(LEGS)}; the first one is the headline")
+    ap.add_argument("--legs", default=None, help=f"comma-separated subset of {sorted(LEGS)}; the first one is the headline "
+                                                 f"(default: {PLAIN_LEGS}; with --full: {DEFAULT_LEGS})")
     ap.add_argument("--leg-steps", type=int, default=0, help="timed steps of every further leg (default: steps // 8, at least 10)")
     ap.add_argument("--batch", type=int, default=None, help="override the instances per GPU of the c2_greedy leg")
     ap.add_argument("--cache-dtype", default="bf16", choices=["bf16", "f32"])
@@ -986,9 +1041,9 @@ def main() -> None:
     ap.add_argument("--train-encoder", default="stack", choices=["stack", "blocks"],
                     help="c4_train: the encoder's training forward as one launch for the whole stack (default) or per sub-block")
     ap.add_argument("--pipeline-depth", type=int, default=2, help="captured rollouts in flight (--launch pipeline)")
-    ap.add_argument("--regions", type=int, default=5,
+    ap.add_argument("--regions", type=int, default=None,
                     help="barrier-bracketed K-step regions per leg: the first is the contract's (value, ms_per_step), min / median / "
-                         "max over all of them are reported as region_ms_per_step")
+                         "max over all of them are reported as region_ms_per_step (default: 1; with --full: 5)")
     ap.add_argument("--timeout", type=float, default=float(os.environ.get("RL4CO_BENCH_TIMEOUT", "1500")),
                     help="seconds after which a rank dumps every thread's stack and exits non-zero instead of hanging (a peer that "
                          "died leaves the others in a barrier; torch.distributed.run then tears the job down)")
@@ -999,7 +1054,17 @@ def main() -> None:
                     help="skip the decode launch at 16 384 instances (roofline.frac_large_batch: the HBM rate with planes 4 x the MALL)")
     ap.add_argument("--cpu-sample-batch", type=int, default=4096,
                     help="instances of the same workload timed on the host cores (shrunk to keep the leg within ~30 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the further legs, the repeated regions, the kernel rooflines "
+                         "(HIP-event pass, HBM read probe, large-batch probe), the one-graph / eager timings, parity against the "
+                         "reference's tours, the CPU baseline, the N = 1 reference region of a multi-rank run, the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline leg's last timed step returned (rewards, log-likelihoods, actions) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.legs is None:
+        args.legs = DEFAULT_LEGS if args.full else PLAIN_LEGS
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the rollout engine has no CPU path")
@@ -1012,10 +1077,15 @@ def main() -> None:
             raise SystemExit(f"--gpus {args.gpus} but only {torch.cuda.device_count()} device(s) visible")
         from rl4co_amd.dist import _free_port
 
+        # the launcher runs as a child process: this one has initialised the GPU (the device count above), and a process
+        # that holds the GPU open must not replace its own program
+        import subprocess
+
         os.dup2(json_fd, 1)
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-                                  os.path.abspath(__file__), *sys.argv[1:]])
+        rc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                             "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
+                             os.path.abspath(__file__), *sys.argv[1:]]).returncode
+        raise SystemExit(rc if rc >= 0 else 128 - rc)
     if args.timeout > 0 and not os.environ.get("RL4CO_BENCH_WATCHDOG"):  # fail loudly, never hang: stacks to stderr, exit code 1
         import faulthandler
 
@@ -1100,21 +1170,25 @@ def main() -> None:
         head_name = legs[0]
         head = results[head_name]
         env_name, num_loc, batch, decode, cfg_idx = LEGS[head_name]
-        # achievable-stream ceiling on this box (float4 grid-stride read of 2 GiB)
-        from rl4co_amd import kernels as K
+        if args.dump_outputs:
+            dump_outputs(bench.outputs[head_name], args.dump_outputs)
+        probe_gbs = None
+        if args.full:
+            # achievable-stream ceiling on this box (float4 grid-stride read of 2 GiB)
+            from rl4co_amd import kernels as K
 
-        probe = torch.empty(2 << 30, dtype=torch.uint8, device=device)
-        sink = torch.zeros(1, device=device)
-        K.hbm_read_probe(probe, sink)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
+            probe = torch.empty(2 << 30, dtype=torch.uint8, device=device)
+            sink = torch.zeros(1, device=device)
             K.hbm_read_probe(probe, sink)
-        e1.record()
-        torch.cuda.synchronize()
-        probe_gbs = 5 * probe.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del probe
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                K.hbm_read_probe(probe, sink)
+            e1.record()
+            torch.cuda.synchronize()
+            probe_gbs = 5 * probe.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            del probe
         head_cache, head_enc = leg_dtypes(head_name, args)
         detail = {
             "metric": "decode_steps_per_sec",
@@ -1144,7 +1218,7 @@ def main() -> None:
                   "trajectories_per_sec", "collective", "rank_ms_per_step", "n1_ms_per_step", "scaling_efficiency"):
             if k in head:
                 detail[k] = head[k]
-        if "roofline" in detail:
+        if "roofline" in detail and args.full:
             detail["roofline"]["hbm_read_probe_GBs"] = probe_gbs
             if head_name == "c2_greedy" and world == 1 and args.batch is None and not args.no_large_batch:
                 big = bench.large_batch_probe(head_name)
@@ -1161,20 +1235,23 @@ def main() -> None:
             # "nccl" IS RCCL on ROCm; any other backend (gloo: the shared-GPU test mode) is reported under its own name
             detail["rccl_ranks" if coll["backend"] == "nccl" else "collective_ranks"] = coll["ranks"]
             detail["allreduce_ms"] = results["c4_train"]["collective"]["allreduce_ms_mean"]
-        if world == 1 and not args.no_parity:
+        if world == 1 and args.full and not args.no_parity:
             log("parity vs the reference's tours (trained weights, every inference leg)")
             detail["parity"] = bench.parity(legs)
-        if world == 1 and not args.no_cpu_baseline and head_name != "c4_train":
+        if world == 1 and args.full and not args.no_cpu_baseline and head_name != "c4_train":
             detail["cpu_baseline"] = cpu_baseline(env_name, num_loc, args.cpu_sample_batch, repeats=5)
             detail["cpu_baseline"]["gpu_over_cpu"] = head["value"] / detail["cpu_baseline"]["value"]
         line = compact_line(detail, head_name, results, args.detail)
-        try:  # everything the compact line leaves out: per-leg dicts, rooflines with their notes, the whole parity block
-            os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
-            with open(args.detail, "w") as f:
-                json.dump(detail, f, indent=1)
-        except OSError as exc:
-            log(f"could not write {args.detail}: {exc}")
+        if not args.full:  # (a run without --full writes no detail file)
             line.pop("detail_file", None)
+        else:
+            try:  # everything the compact line leaves out: per-leg dicts, rooflines with their notes, the whole parity block
+                os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
+                with open(args.detail, "w") as f:
+                    json.dump(detail, f, indent=1)
+            except OSError as exc:
+                log(f"could not write {args.detail}: {exc}")
+                line.pop("detail_file", None)
         encoded = json.dumps(line, separators=(",", ":"))
         for optional in ("parity", "encoder_roofline", "legs"):  # never again a line the driver cannot parse
             if len(encoded.encode()) <= MAX_LINE_BYTES:

@@ -245,3 +245,22 @@ def flip_budget(env_name: str, rows: int, gpu: bool = False) -> int:
     if env_name == "cvrptw" and gpu:
         return max(1, rows // 20)
     return max(1, rows // (50 if gpu else 100))
+
+
+REFERENCE_RECORDS = GOLDEN_DIR / "reference"
+
+
+def reference_record(key: str, compute) -> dict:
+    """The reference's side of a comparison, as recorded: ``tests/golden/reference/<key>.npz`` holds the dict of arrays
+    ``compute()`` returned when it ran the reference's own code (its checkout, through oracle/ref_import.py). The tests
+    compare against the record and need no checkout; ``RL4CO_RECORD_REFERENCE=1`` (checkout present) runs ``compute``
+    and rewrites the record — ``python -m oracle.gen_reference_records`` does that for every recorded test."""
+    import os
+
+    path = REFERENCE_RECORDS / f"{key}.npz"
+    if os.environ.get("RL4CO_RECORD_REFERENCE") == "1":
+        arrays = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in compute().items()}
+        path.parent.mkdir(parents=True, exist_ok=True)
+        np.savez_compressed(path, **arrays)
+    with np.load(path) as z:
+        return {k: torch.from_numpy(z[k].copy()) for k in z.files}

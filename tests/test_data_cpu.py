@@ -1,6 +1,7 @@
 """Rows N2 / N3: npz schema, dihedral-8 augmentation and the POMO evaluation
-epilogue — checked against the REAL reference source (skipped where /root/reference is absent)
-and against the oracle restatement; the rollout itself runs through the fake device (C oracle)."""
+epilogue — checked against what the REAL reference source computes (recorded under tests/golden/reference by
+oracle/gen_reference_records.py; the one test that runs the reference's loader needs its checkout) and against the
+oracle restatement; the rollout itself runs through the fake device (C oracle)."""
 import numpy as np
 import pytest
 import torch
@@ -8,7 +9,7 @@ import torch
 from oracle import ref_import
 from oracle import reference_torch as R
 from tests.fake_device import cpu_device  # noqa: F401
-from tests.helpers import GoldenCase
+from tests.helpers import GoldenCase, reference_record
 
 needs_reference = pytest.mark.skipif(not ref_import.available(), reason="reference checkout not present")
 
@@ -50,24 +51,31 @@ def test_npz_matches_reference_loader(tmp_path):
     assert tuple(td_ref.batch_size) == (g.batch,)
 
 
-@needs_reference
 def test_dihedral8_matches_reference_transform(cpu_device):
-    import importlib
-
     from rl4co_amd.data import StateAugmentation
 
-    ref_import.install()
-    tr = importlib.import_module("rl4co.data.transforms")
-    TD = importlib.import_module("tensordict").TensorDict
     g = GoldenCase("tsp20_b64_greedy_simple")
+
+    def reference():
+        import importlib
+
+        ref_import.install()
+        tr = importlib.import_module("rl4co.data.transforms")
+        TD = importlib.import_module("tensordict").TensorDict
+        out = tr.StateAugmentation(num_augment=8, augment_fn="dihedral8")(TD({"locs": g.data["locs"].clone()}, batch_size=[g.batch]))
+        return {"locs": out["locs"]}
+
     ours = StateAugmentation(8, augment_fn="dihedral8")(_td(g))
-    theirs = tr.StateAugmentation(num_augment=8, augment_fn="dihedral8")(TD({"locs": g.data["locs"].clone()}, batch_size=[g.batch]))
+    theirs = reference_record("dihedral8_tsp20_b64", reference)
     assert torch.equal(ours["locs"], theirs["locs"])
     assert ours["locs"].shape == (8 * g.batch, 20, 2)
     assert torch.equal(ours["locs"][: g.batch], g.data["locs"])  # first block = identity
 
 
-@needs_reference
+def _kw_key(kw: dict) -> str:
+    return "_".join(f"{k}-{'+'.join(v) if isinstance(v, list) else v}" for k, v in sorted(kw.items()))
+
+
 @pytest.mark.parametrize("kw", [dict(num_augment=8), dict(num_augment=4, first_aug_identity=False),
                                 dict(num_augment=5, normalize=True), dict(num_augment=8, feats=["locs", "depot2"]),
                                 dict(num_augment=8, augment_fn="dihedral8", first_aug_identity=False)])
@@ -75,20 +83,25 @@ def test_state_augmentation_matches_reference_transform(kw, cpu_device):
     """rl4co/data/transforms.py:49-151 argument for argument: the symmetric (SymNCO) augmentation consumes the global
     torch generator like the reference (same seed -> the same rows, bit for bit), first-block identity,
     `first_aug_identity=False`'s own row restore, min-max normalisation, several features."""
-    import importlib
-
     from rl4co_amd.data import StateAugmentation
 
-    ref_import.install()
-    tr = importlib.import_module("rl4co.data.transforms")
-    TD = importlib.import_module("tensordict").TensorDict
     g = GoldenCase("tsp20_b64_greedy_simple")
     data = {"locs": g.data["locs"].clone(), "depot2": g.data["locs"][:, :3].clone()}
+
+    def reference():
+        import importlib
+
+        ref_import.install()
+        tr = importlib.import_module("rl4co.data.transforms")
+        TD = importlib.import_module("tensordict").TensorDict
+        torch.manual_seed(77)
+        out = tr.StateAugmentation(**kw)(TD({k: v.clone() for k, v in data.items()}, batch_size=[g.batch]))
+        return {k: out[k] for k in data}
+
     torch.manual_seed(77)
     ours = StateAugmentation(**kw)(__import__("rl4co_amd.tensordict", fromlist=["TensorDict"]).TensorDict(
         {k: v.clone() for k, v in data.items()}, batch_size=[g.batch]))
-    torch.manual_seed(77)
-    theirs = tr.StateAugmentation(**kw)(TD({k: v.clone() for k, v in data.items()}, batch_size=[g.batch]))
+    theirs = reference_record(f"state_augmentation_{_kw_key(kw)}", reference)
     for k in data:
         assert ours[k].shape == theirs[k].shape == (kw["num_augment"] * g.batch, *data[k].shape[1:])
         assert torch.equal(ours[k], theirs[k]), k
@@ -152,35 +165,39 @@ def test_pomo_evaluate_epilogue(cpu_device):
     assert bool((out["max_aug_reward"] >= out["max_reward"][:, 0] - 1e-6).all())
 
 
-@needs_reference
 @pytest.mark.parametrize("a,s,b,t", [(8, 6, 16, 20), (1, 7, 5, 9), (8, 1, 4, 3), (3, 100, 7, 50), (70, 2, 3, 4)])
 def test_pomo_best_restatement_equals_reference_epilogue(a, s, b, t):
     """oracle_pomo_best (the host restatement of rl4co_pomo_best, which the GPU tests pin the kernel to) against the
     reference's own unbatchify / max / gather_by_index (utils/ops.py:33-66 as used by zoo/pomo/model.py:112-140), with
     many exact ties in the rewards: the first maximum wins on both axes."""
-    import importlib
-
     from oracle import c_oracle
 
-    ref_import.install()
-    ops = importlib.import_module("rl4co.utils.ops")
-    torch.manual_seed(a * 1000 + s)
-    reward = torch.randint(0, 4, (s * a * b,)).float() * -0.5  # four distinct values: ties everywhere
-    if s * a * b > 40:  # and a few NaN rewards: torch.max propagates them (the first NaN wins), so must the epilogue
-        reward[torch.randperm(s * a * b)[:5]] = float("nan")
-    actions = torch.randint(0, 50, (s * a * b, t))
+    def reference():
+        import importlib
+
+        ref_import.install()
+        ops = importlib.import_module("rl4co.utils.ops")
+        torch.manual_seed(a * 1000 + s)
+        reward = torch.randint(0, 4, (s * a * b,)).float() * -0.5  # four distinct values: ties everywhere
+        if s * a * b > 40:  # and a few NaN rewards: torch.max propagates them (the first NaN wins), so must the epilogue
+            reward[torch.randperm(s * a * b)[:5]] = float("nan")
+        actions = torch.randint(0, 50, (s * a * b, t))
+        r = ops.unbatchify(reward, (a, s)).view(b, a, s)
+        acts = ops.unbatchify(actions, (a, s)).view(b, a, s, t)
+        max_reward, idx = r.max(dim=-1)
+        best_ms = ops.gather_by_index(acts, idx, dim=idx.dim()).view(b, a, t)
+        max_aug, idx2 = max_reward.max(dim=1)
+        return {"reward": reward, "actions": actions, "max_reward": max_reward, "idx": idx, "best_ms": best_ms,
+                "max_aug": max_aug, "idx2": idx2, "best_aug_actions": ops.gather_by_index(best_ms, idx2, dim=1).view(b, t)}
+
+    want = reference_record(f"pomo_best_a{a}_s{s}_b{b}_t{t}", reference)
+    reward, actions = want["reward"], want["actions"]
+    max_reward, idx, best_ms, max_aug, idx2 = (want[k] for k in ("max_reward", "idx", "best_ms", "max_aug", "idx2"))
     got = c_oracle.pomo_best(reward, actions, a, s)
-    r = ops.unbatchify(reward, (a, s))
-    acts = ops.unbatchify(actions, (a, s))
-    r = r.view(b, a, s)
-    acts = acts.view(b, a, s, t)
-    max_reward, idx = r.max(dim=-1)
     assert torch.equal(got["max_reward"].nan_to_num(7.0), max_reward.nan_to_num(7.0)) and torch.equal(got["best_start"], idx)
-    best_ms = ops.gather_by_index(acts, idx, dim=idx.dim()).view(b, a, t)
     assert torch.equal(got["best_multistart_actions"], best_ms)
-    max_aug, idx2 = max_reward.max(dim=1)
     assert torch.equal(got["max_aug_reward"].nan_to_num(7.0), max_aug.nan_to_num(7.0)) and torch.equal(got["best_aug"], idx2)
-    assert torch.equal(got["best_aug_actions"], ops.gather_by_index(best_ms, idx2, dim=1).view(b, t))
+    assert torch.equal(got["best_aug_actions"], want["best_aug_actions"])
     no_actions = c_oracle.pomo_best(reward, None, a, s)
     assert torch.equal(no_actions["max_aug_reward"].nan_to_num(7.0), max_aug.nan_to_num(7.0)) and "best_aug_actions" not in no_actions
 
@@ -200,19 +217,21 @@ def test_augmentation_refuses_cpu_tensors_without_the_device():
 # instance files and datasets (row N2): generate_data.py / dataset.py / RL4COEnvBase.dataset
 # ---------------------------------------------------------------------------------------------
 
-@needs_reference
 @pytest.mark.parametrize("problem,size,dist", [("tsp", 20, None), ("vrp", 50, None), ("pdp", 20, None), ("op", 20, "const"),
                                                ("op", 50, "unif"), ("op", 100, "dist"), ("pctsp", 50, None)])
 def test_generated_instance_files_equal_reference_generator(problem, size, dist):
     """The same numpy draws under the same seed: every array of the file equals the reference generator's, bit for bit."""
-    import importlib
-
     from rl4co_amd import data as D
 
-    ref_import.install()
-    ref_gen = importlib.import_module("rl4co.data.generate_data")
-    np.random.seed(4321)
-    want = ref_gen.generate_env_data(problem, 64, size, dist)
+    def reference():
+        import importlib
+
+        ref_import.install()
+        ref_gen = importlib.import_module("rl4co.data.generate_data")
+        np.random.seed(4321)
+        return ref_gen.generate_env_data(problem, 64, size, dist)
+
+    want = {k: v.numpy() for k, v in reference_record(f"generate_env_data_{problem}{size}_{dist}", reference).items()}
     np.random.seed(4321)
     got = D.generate_env_data(problem, 64, size, dist)
     assert sorted(got) == sorted(want)
@@ -220,24 +239,38 @@ def test_generated_instance_files_equal_reference_generator(problem, size, dist)
         assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
 
 
-@needs_reference
 def test_generate_dataset_files_equal_reference(tmp_path):
-    import importlib
+    import os
 
     from rl4co_amd import data as D
 
-    ref_import.install()
-    ref_gen = importlib.import_module("rl4co.data.generate_data")
     kw = dict(name="val", problem="op", dataset_size=32, graph_sizes=[20, 50], seed=4321)
+
+    def reference():  # every array of every file the reference writes, under "<path in the data dir, / as %>__<key>"
+        import importlib
+
+        ref_import.install()
+        ref_gen = importlib.import_module("rl4co.data.generate_data")
+        ref_gen.generate_dataset(data_dir=str(tmp_path / "ref"), **kw)
+        rec = {}
+        for dirpath, _, names in os.walk(tmp_path / "ref"):
+            for n in names:
+                rel = os.path.relpath(os.path.join(dirpath, n), tmp_path / "ref")
+                with np.load(os.path.join(dirpath, n)) as z:
+                    rec.update({f"{rel.replace(os.sep, '%')}__{k}": z[k] for k in z.files})
+        return rec
+
+    want = reference_record("generate_dataset_op_val", reference)
     ours = D.generate_dataset(data_dir=str(tmp_path / "ours"), **kw)
-    ref_gen.generate_dataset(data_dir=str(tmp_path / "ref"), **kw)
     assert len(ours) == 6  # three prize distributions x two sizes
+    assert len({k.split("__")[0] for k in want}) == 6
     for f in ours:
-        rel = f[len(str(tmp_path / "ours")) + 1:]
-        a, b = np.load(f), np.load(str(tmp_path / "ref" / rel))
-        assert sorted(a.files) == sorted(b.files)
+        rel = os.path.relpath(f, tmp_path / "ours").replace(os.sep, "%")
+        a = np.load(f)
+        assert sorted(a.files) == sorted(k.split("__")[1] for k in want if k.split("__")[0] == rel), rel
         for k in a.files:
-            assert np.array_equal(a[k], b[k]), (rel, k)
+            b = want[f"{rel}__{k}"].numpy()
+            assert a[k].dtype == b.dtype and np.array_equal(a[k], b), (rel, k)
     assert D.generate_dataset(data_dir=str(tmp_path / "ours"), **kw) == []  # existing files are kept unless overwrite=True
     with pytest.raises(NotImplementedError):
         D.generate_env_data("mdpp", 4, 10)

@@ -38,7 +38,7 @@ def _detail(line):
 
 
 def test_single_gpu_line_has_the_contract_keys():
-    line = _run(["--steps", "10", "--warmup", "2", "--legs", "c2_greedy", "--no-cpu-baseline", "--no-parity"])
+    line = _run(["--steps", "10", "--warmup", "2", "--legs", "c2_greedy", "--no-cpu-baseline", "--no-parity", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline"):
         assert k in line, k
@@ -56,7 +56,7 @@ def test_single_gpu_line_has_the_contract_keys():
 
 def test_default_legs_line_stays_small_and_carries_baseline_and_parity():
     """The driver's own command shape (all legs, parity block, cpu_baseline) must still fit the line."""
-    line = _run(["--steps", "10", "--warmup", "2", "--leg-steps", "4"], timeout=900)
+    line = _run(["--steps", "10", "--warmup", "2", "--leg-steps", "4", "--full"], timeout=900)
     cb = line["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1
     # BASELINE.md §3: C1 (TSP-20 x 256, check_solution on / off) and the headline workload, 1 warm-up + >= 5 passes, median
@@ -76,11 +76,32 @@ def test_default_legs_line_stays_small_and_carries_baseline_and_parity():
     assert "parity" in detail and "c4_train" in detail["legs"] and detail["legs"]["c4_train"]["roofline"]["bound"] == "mfma"
 
 
+def test_plain_run_times_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full: the headline leg alone, K steps in one region, no rooflines / parity / baseline / detail file; the
+    last timed step's outputs under --dump-outputs, as float32 / float64 arrays."""
+    import numpy as np
+
+    line = _run(["--steps", "6", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["metric"] == "decode_steps_per_sec" and line["steps"] == 6 and line["warmup"] == 2 and line["config"]["leg"] == "c2_greedy"
+    assert line["region_ms_per_step"]["n"] == 1 and line["config"]["launch"] == "pipeline"
+    for k in ("legs", "roofline", "parity", "cpu_baseline", "detail_file", "graph_ms_per_step", "eager_ms_per_step"):
+        assert not line.get(k), k
+    assert abs(line["value"] - 4096 * 100 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-6
+    reward, actions = np.load(tmp_path / "reward.npy"), np.load(tmp_path / "actions.npy")
+    ll = np.load(tmp_path / "log_likelihood.npy")
+    assert reward.dtype == np.float32 and reward.shape == (4096,) and np.isfinite(reward).all() and (reward < 0).all()
+    assert ll.dtype == np.float32 and ll.shape == (4096,)
+    assert actions.dtype == np.float64 and actions.shape == (4096, 100) and (actions == np.round(actions)).all()
+    assert (np.sort(actions, 1) == np.arange(100)).all()  # greedy TSP tours: every node once
+
+
 def test_two_ranks_self_spawned():
     two_gpus = torch.cuda.device_count() >= 2
     extra = {} if two_gpus else {"RL4CO_BENCH_SHARED_GPU": "1", "RL4CO_DIST_BACKEND": "gloo"}
-    line = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--legs", "c2_greedy,c4_train", "--no-cpu-baseline", "--no-parity"],
-                env_extra=extra)
+    line = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--legs", "c2_greedy,c4_train", "--no-cpu-baseline", "--no-parity",
+                 "--full"], env_extra=extra)
     assert line["n_gpus"] == 2 and line["collective_backend"] == ("nccl" if two_gpus else "gloo")
     # "rccl_ranks" only when the collective really ran on RCCL; gloo ranks (two processes sharing one GPU) say so
     assert line["rccl_ranks" if two_gpus else "collective_ranks"] == 2 and ("rccl_ranks" in line) == two_gpus
@@ -100,8 +121,8 @@ def test_the_drivers_rank_counts_on_one_shared_gpu(n):
     can check of `bench.py --gpus 8`; the times themselves mean nothing here."""
     if torch.cuda.device_count() >= n:
         pytest.skip("enough GPUs for the real thing: test_all_visible_gpus_on_rccl")
-    line = _run(["--gpus", str(n), "--steps", "4", "--warmup", "1", "--legs", "c2_greedy,c4_train", "--no-cpu-baseline", "--no-parity"],
-                env_extra={"RL4CO_BENCH_SHARED_GPU": "1", "RL4CO_DIST_BACKEND": "gloo"}, timeout=600)
+    line = _run(["--gpus", str(n), "--steps", "4", "--warmup", "1", "--legs", "c2_greedy,c4_train", "--no-cpu-baseline", "--no-parity",
+                 "--full"], env_extra={"RL4CO_BENCH_SHARED_GPU": "1", "RL4CO_DIST_BACKEND": "gloo"}, timeout=600)
     assert line["n_gpus"] == n and line["collective_backend"] == "gloo" and line["collective_ranks"] == n and "rccl_ranks" not in line
     assert line["config"]["parallelism"].startswith(f"replicas x{n}")
     assert line["rank_ms_per_step"]["min"] <= line["rank_ms_per_step"]["max"] == pytest.approx(line["ms_per_step"], rel=1e-3)
@@ -117,8 +138,8 @@ def test_all_visible_gpus_on_rccl():
     n = torch.cuda.device_count()
     if n < 2:
         pytest.skip("one GPU visible: RCCL with more than one rank needs a multi-GPU node")
-    line = _run(["--gpus", str(n), "--steps", "6", "--warmup", "2", "--legs", "c2_greedy,c4_train", "--no-cpu-baseline", "--no-parity"],
-                timeout=900)
+    line = _run(["--gpus", str(n), "--steps", "6", "--warmup", "2", "--legs", "c2_greedy,c4_train", "--no-cpu-baseline", "--no-parity",
+                 "--full"], timeout=900)
     assert line["n_gpus"] == n and line["collective_backend"] == "nccl" and line["rccl_ranks"] == n
     assert 0.5 < line["scaling_efficiency"] <= 1.2 and line["allreduce_ms"] > 0
     assert line["legs"]["c4_train"]["scaling_efficiency"] > 0.5

@@ -13,7 +13,7 @@ cd /tmp
 for B in $BATCHES; do
   O=$R/gpurun_out/${TAG}_mall/$B
   mkdir -p $O
-  ARGS="--legs c2_greedy --batch $B --steps 10 --warmup 2 --no-cpu-baseline --no-parity --launch eager --regions 1"
+  ARGS="--legs c2_greedy --batch $B --steps 10 --warmup 2 --no-cpu-baseline --no-parity --launch eager --regions 1 --full"
   timeout 300 python $R/bench.py $ARGS --detail $O/detail.json > $O/bench.json 2> $O/bench.err
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py $ARGS --detail $O/detail_trace.json > $O/bench_trace.json 2> $O/bench_trace.err
   timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python $R/bench.py $ARGS --steps 3 --detail $O/detail_f.json > /dev/null 2> $O/pmc_fetch.err
