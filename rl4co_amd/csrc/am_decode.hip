@@ -400,12 +400,25 @@ __device__ inline void gemv_t(float (&out)[EPL], const float* __restrict__ wt, c
   }
 }
 
+// Row cache (TSP / CVRP, not UNFOLD): the LDS a workgroup may hold without lowering the CU's workgroup count keeps the
+// three plane rows of S nodes. Resident are the S highest-index nodes that can still be listed (TSP: unvisited; CVRP:
+// the depot and the unvisited customers; mask off: all nodes) — as the list is ascending and holds only such nodes,
+// its resident entries are always its tail. When a resident node leaves (visited), its slot goes to the highest
+// non-resident candidate, marked pending: the next step that lists that node reads its rows from HBM as it would
+// anyway and writes them into the slot in the same passes; from then on they come from LDS. Only the load source
+// differs — every lane walks the same list positions in the same order, so the arithmetic is untouched.
+constexpr int kRowCacheNone = 0xFF;  // slot byte of a node that is not resident
+__host__ __device__ inline int row_cache_bytes(int N, int S, int esz) {
+  return S > 0 ? S * 3 * kD * esz + lds_pad(N) + S : 0;
+}
+
 template <class C, int ENV, bool UNFOLD = false>
-__global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_args a) {
+__global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_args a, const int S) {
   constexpr int EPL = C::EPL;
   constexpr int LPR = kD / EPL;   // lanes per cache row
   constexpr int RPL = 64 / LPR;   // rows per wave-wide load (= row groups G)
   constexpr int LPH = kDH / EPL;  // lanes per head
+  constexpr bool kRowCache = !UNFOLD && (ENV == RL4CO_ENV_TSP || ENV == RL4CO_ENV_CVRP);
   using elem = typename C::elem;
   using raw_t = typename C::raw;
 
@@ -420,6 +433,9 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   uint16_t* fl = reinterpret_cast<uint16_t*>(mh + kH);  // [Np] nodes this step reads, ascending
   uint8_t* mk = reinterpret_cast<uint8_t*>(fl + Np);    // [Np] 1 = feasible
   uint8_t* vis = mk + Np;                               // [Np] CVRP visited flags
+  elem* rc = reinterpret_cast<elem*>(vis + Np);         // [S][3][128] row cache (16-byte aligned: 40 Np + 32 bytes in)
+  uint8_t* rslot = reinterpret_cast<uint8_t*>(rc + S * 3 * kD);  // [Np] slot of each node, kRowCacheNone if not resident
+  uint8_t* rpend = rslot + Np;                                    // [S] 1 = slot not filled yet
 
   const int cb = r % a.B_inst;  // instance whose cache this trajectory reads
   const int rg = lane / LPR;    // row group inside a wave-wide load
@@ -471,17 +487,61 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
                                                 : nullptr;
   wave_lds_sync();
 
+  // ---- row cache: the S highest-index candidates, all pending --------------------------------
+  const bool list_all = !(a.mask_inner && a.mask_logits);
+  auto candidate = [&](int j) -> bool {  // can node j still be listed in a later step?
+    return list_all || (ENV == RL4CO_ENV_TSP ? mk[j] != 0 : (j == 0 || vis[j] == 0));
+  };
+  const bool caching = kRowCache && S > 0;
+  if (caching) {
+    for (int j = lane; j < Np; j += 64) rslot[j] = (uint8_t)kRowCacheNone;
+    wave_lds_sync();
+    int k = 0;
+    for (int j0 = N - 1; j0 >= 0 && k < S; j0 -= 64) {  // lane l takes node j0 - l: descending in lane order
+      const int j = j0 - lane;
+      const bool f = j >= 0 && candidate(j);
+      const unsigned long long bal = __ballot(f);
+      const int s = k + __popcll(bal & ((1ull << lane) - 1ull));
+      if (f && s < S) {
+        rslot[j] = (uint8_t)s;
+        rpend[s] = 1;
+      }
+      k += __popcll(bal);
+    }
+    wave_lds_sync();
+  }
+  auto lds_row = [&](int j, int plane) -> const elem* { return rc + (rslot[j] * 3 + plane) * kD + e0; };
+  auto fill_row = [&](int j, int plane, const raw_t& v) {  // a pending (or already filled) slot gets its row
+    const int s = rslot[j];
+    if (s != kRowCacheNone) *reinterpret_cast<raw_t*>(rc + (s * 3 + plane) * kD + e0) = v;
+  };
+
   float qb[EPL];
 #pragma unroll
   for (int e = 0; e < EPL; ++e) qb[e] = a.q_bias ? a.q_bias[(int64_t)cb * kD + e0 + e] : 0.0f;
 
   const bool single = a.max_steps == 1;
   int t = 0;
-  int rows_read = 0;  // cache rows this trajectory streamed (x 3 planes): the launch's real HBM read volume
+  int rows_read = 0;  // cache rows this trajectory streamed from HBM (x 3 planes): the launch's real HBM read volume
 
   for (; t < a.max_steps && (!st.done || single); ++t) {
     const int F = build_list(a, mk, fl, N, lane);
-    rows_read += F;
+    // list positions [0, hend) are read from HBM, [hend, F) from the row cache; the HBM rows of [pbeg, hend) are also
+    // written into their slots (the pending ones). Resident entries lie in the list's last S positions.
+    int hend = F, pbeg = F;
+    if (caching) {
+      const int c_lo = max(F - S, 0);
+      int last_hbm = c_lo - 1, first_pend = F;
+      for (int c = c_lo + lane; c < F; c += 64) {
+        const int s = rslot[fl[c]];
+        const bool pend = s != kRowCacheNone && rpend[s] != 0;
+        if (s == kRowCacheNone || pend) last_hbm = c;
+        if (pend) first_pend = min(first_pend, c);
+      }
+      hend = rl4co::bfly_i_max(last_hbm) + 1;
+      pbeg = -rl4co::bfly_i_max(-first_pend);
+    }
+    rows_read += hend;
 
     // ---- query: folded context projection + graph context (decoder.py:128-140) ------
     float q[EPL];
@@ -540,6 +600,19 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
 
     // ---- pass 1: per-head scores over the glimpse keys of the listed nodes -------------
     float m = kNegInf;
+    auto score = [&](const raw_t& rw, int c, int j) {  // j < 0: no entry (a no-op)
+      const bool valid = j >= 0;
+      float k[EPL];
+      C::cvt(rw, k);
+      float acc = 0.0f;
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) acc = fmaf(q[e], k[e], acc);
+      acc = rl4co::bfly_sum<1, LPH>(acc);
+      const bool feas = valid && (!a.mask_inner || mk[valid ? j : 0] != 0);
+      const float sv = feas ? acc : kNegInf;
+      if (valid && (li % LPH) == 0) sc[c * kH + hd] = sv;
+      m = fmaxf(m, sv);
+    };
     for (int c0 = 0; c0 < F; c0 += RPL * kUnroll) {
       raw_t rw[kUnroll];
       int jj[kUnroll];
@@ -547,22 +620,13 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
         jj[u] = (c < F) ? (int)fl[c] : -1;
-        rw[u] = (jj[u] >= 0) ? C::ld(Kg + (int64_t)jj[u] * rs) : C::zero();
+        rw[u] = (jj[u] < 0) ? C::zero() : (c < hend ? C::ld(Kg + (int64_t)jj[u] * rs) : C::ld(lds_row(jj[u], 0)));
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
-        const bool valid = jj[u] >= 0;
-        float k[EPL];
-        C::cvt(rw[u], k);
-        float acc = 0.0f;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc = fmaf(q[e], k[e], acc);
-        acc = rl4co::bfly_sum<1, LPH>(acc);
-        const bool feas = valid && (!a.mask_inner || mk[valid ? jj[u] : 0] != 0);
-        const float sv = feas ? acc : kNegInf;
-        if (valid && (li % LPH) == 0) sc[c * kH + hd] = sv;
-        m = fmaxf(m, sv);
+        if (caching && c >= pbeg && c < hend) fill_row(jj[u], 0, rw[u]);
+        score(rw[u], c, jj[u]);
       }
     }
     m = rl4co::bfly_max<LPR, 64>(m);
@@ -581,6 +645,14 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
     float o[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) o[e] = 0.0f;
+    auto accumulate = [&](const raw_t& rw, int c, bool ok) {  // !ok: no entry (adds exact zeros)
+      float v[EPL];
+      C::cvt(rw, v);
+      const float p = ok ? sc[c * kH + hd] : 0.0f;
+      l = l + p;
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) o[e] = fmaf(p, v[e], o[e]);
+    };
     for (int c0 = 0; c0 < F; c0 += RPL * kUnroll) {
       raw_t rw[kUnroll];
       bool ok[kUnroll];
@@ -588,17 +660,13 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
         ok[u] = c < F;
-        rw[u] = ok[u] ? C::ld(Vg + (int64_t)fl[c] * rs) : C::zero();
+        rw[u] = !ok[u] ? C::zero() : (c < hend ? C::ld(Vg + (int64_t)fl[c] * rs) : C::ld(lds_row(fl[c], 1)));
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
-        float v[EPL];
-        C::cvt(rw[u], v);
-        const float p = ok[u] ? sc[c * kH + hd] : 0.0f;
-        l = l + p;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) o[e] = fmaf(p, v[e], o[e]);
+        if (caching && c >= pbeg && c < hend) fill_row(fl[c], 1, rw[u]);
+        accumulate(rw[u], c, ok[u]);
       }
     }
     l = 1.0f / rl4co::bfly_sum<LPR, 64>(l);  // one IEEE division per step; heads = o * (1/l)
@@ -615,28 +683,57 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
     }
 
     // ---- pass 3: pointer logits against the (project_out-folded) logit key -----------
+    auto logit = [&](const raw_t& rw, int c) {
+      float k[EPL];
+      C::cvt(rw, k);
+      float acc = 0.0f;
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) acc = fmaf(o[e], k[e], acc);
+      acc = rl4co::bfly_sum<1, LPR>(acc);
+      if (c < F && li == 0) lg[c] = acc;
+    };
     for (int c0 = 0; c0 < F; c0 += RPL * kUnroll) {
       raw_t rw[kUnroll];
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
-        rw[u] = (c < F) ? C::ld(Kl + (int64_t)fl[c] * rs) : C::zero();
+        rw[u] = (c >= F) ? C::zero() : (c < hend ? C::ld(Kl + (int64_t)fl[c] * rs) : C::ld(lds_row(fl[c], 2)));
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
-        float k[EPL];
-        C::cvt(rw[u], k);
-        float acc = 0.0f;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc = fmaf(o[e], k[e], acc);
-        acc = rl4co::bfly_sum<1, LPR>(acc);
-        if (c < F && li == 0) lg[c] = acc;
+        if (caching && c >= pbeg && c < hend) fill_row(fl[c], 2, rw[u]);
+        logit(rw[u], c);
+      }
+    }
+    if (caching) {
+      // the slots of the listed pending nodes now hold all three rows
+      for (int c = pbeg + lane; c < hend; c += 64) {
+        const int s = rslot[fl[c]];
+        if (s != kRowCacheNone) rpend[s] = 0;
       }
     }
     wave_lds_sync();
 
-    finalize_and_step<ENV>(a, st, lg, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur);
+    const int bi = finalize_and_step<ENV>(a, st, lg, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur);
+    if (caching && rslot[bi] != kRowCacheNone && !candidate(bi)) {
+      // the resident node left: its slot goes to the highest candidate not resident, which the next step that lists
+      // it reads from HBM anyway
+      int nxt = -1;
+      for (int j = lane; j < N; j += 64)
+        if (candidate(j) && rslot[j] == kRowCacheNone) nxt = j;
+      nxt = rl4co::bfly_i_max(nxt);
+      const int s = rslot[bi];
+      wave_lds_sync();
+      if (lane == 0) {
+        rslot[bi] = (uint8_t)kRowCacheNone;
+        if (nxt >= 0) {
+          rslot[nxt] = (uint8_t)s;
+          rpend[s] = 1;
+        }
+      }
+      wave_lds_sync();
+    }
   }
   if (!single && !st.done && t >= a.max_steps) st.errbits |= RL4CO_EBIT_MAX_STEPS;
 
@@ -1141,14 +1238,46 @@ inline int resolve_variant(const rl4co_am_decode_args& a) {
   return RL4CO_VARIANT_STREAM;
 }
 
+// Workgroups of `bytes` LDS one CU holds, at most kStreamWgPerCu: the streaming kernel's register bound (<= 128 VGPRs,
+// four waves per SIMD). The LDS allocation granule is taken as 512 B or 1280 B, whichever binds.
+constexpr int kStreamWgPerCu = 16;
+constexpr int kCuLds = 160 * 1024;
+inline int stream_wg_per_cu(int bytes, int gran) {
+  const int b = (bytes + gran - 1) / gran * gran;
+  return min(kStreamWgPerCu, kCuLds / b);
+}
+
+// Row-cache slots of one streaming launch: the most for which the workgroups per CU stay what the scratch alone allows,
+// capped at N and at 255 (the slot byte). 0 for single-step calls (nothing is reused), the parity mode and the
+// environments whose "can still be listed" set is not kept (OP, PCTSP, PDP, CVRPTW). By default also 0 for fp32 planes:
+// their 1536-byte rows leave room for 3 slots at N = 100, 5.9 % of the bytes, and the leg measured slower with them
+// (DESIGN 4.1). RL4CO_DECODE_ROW_CACHE = n (read at every launch, so one process can compare) sets at most n slots, fp32
+// planes included; 0 turns the cache off.
+int row_cache_slots(const rl4co_am_decode_args& a, int esz, bool unfold) {
+  if (unfold || a.max_steps == 1 || (a.env != RL4CO_ENV_TSP && a.env != RL4CO_ENV_CVRP)) return 0;
+  const int base = rl4co_am_decode_lds_bytes(a.N, a.env);
+  int S = 0;
+  while (S < min(a.N, 255)) {
+    const int bytes = base + row_cache_bytes(a.N, S + 1, esz);
+    if (stream_wg_per_cu(bytes, 512) < stream_wg_per_cu(base, 512) ||
+        stream_wg_per_cu(bytes, 1280) < stream_wg_per_cu(base, 1280) || bytes > kCuLds)
+      break;
+    ++S;
+  }
+  const char* e = getenv("RL4CO_DECODE_ROW_CACHE");
+  if (e && e[0] != '\0') return min(S, max(atoi(e), 0));
+  return esz == 4 ? 0 : S;
+}
+
 template <class C, int ENV, bool UNFOLD = false>
 int launch(const rl4co_am_decode_args& a, hipStream_t stream) {
-  const int lds = rl4co_am_decode_lds_bytes(a.N, ENV);
+  const int S = row_cache_slots(a, (int)sizeof(typename C::elem), UNFOLD);
+  const int lds = rl4co_am_decode_lds_bytes(a.N, ENV) + row_cache_bytes(a.N, S, (int)sizeof(typename C::elem));
   if (lds > 64 * 1024) {
     RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(am_decode_kernel<C, ENV, UNFOLD>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
-  hipLaunchKernelGGL((am_decode_kernel<C, ENV, UNFOLD>), dim3(a.B), dim3(64), lds, stream, a);
+  hipLaunchKernelGGL((am_decode_kernel<C, ENV, UNFOLD>), dim3(a.B), dim3(64), lds, stream, a, S);
   RL4CO_HIP_TRY(hipGetLastError());
   return RL4CO_OK;
 }
