@@ -35,8 +35,10 @@ extern "C" {
  * second position — a caller built for the old list would pass dout as out and lse as dout).
  *   6: rl4co_attn_bwd_{bf16,f16} take the forward's `out`; rl4co_abi_version() itself.
  *   7: rl4co_am_decode_args / rl4co_am_teacher_args end in the context tables' dtype and strides (ctx_dtype ...).
- *   8: the 16 rl4co_<op>_bf16 / rl4co_<op>_f16 pairs are ONE rl4co_<op>(int dtype, ...) each. */
-#define RL4CO_ABI_VERSION 12
+ *   8: the 16 rl4co_<op>_bf16 / rl4co_<op>_f16 pairs are ONE rl4co_<op>(int dtype, ...) each.
+ *  13: rl4co_am_decode_args ends in the top-k / top-p filter (top_k, top_p) and its optional kept-set output
+ *      (kept_bits, kept_words); zero-initialised = no filter. */
+#define RL4CO_ABI_VERSION 13
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -410,6 +412,16 @@ typedef struct rl4co_am_decode_args {
   int32_t reserved0;
   int64_t ctx_row_stride;
   int64_t ctx_batch_stride;
+  /* (v13) top-k / top-p (nucleus) filter of utils/decoding.py:109-188 between temperature and log_softmax, in the order
+   * specified in the am_decode.hip header. top_k <= 0: no top-k (k >= the step's candidates: nothing removed); top_p <= 0
+   * or >= 1: no top-p. Removed nodes get log-prob -inf and are never selected. STREAM / LDS / WIDE variants and the
+   * unfolded mode; an explicit RL4CO_VARIANT_MS with an active filter is refused and the auto choice avoids it. */
+  int32_t top_k;
+  float top_p;
+  uint32_t* kept_bits; /* [B,out_stride,kept_words] or NULL: bit j % 32 of word j / 32 = node j has a finite log-prob
+                        * after mask and filter (the layout of rl4co_env_replay's mask bits); written per step taken */
+  int32_t kept_words;  /* words per (trajectory, step): a multiple of 4 covering N                                    */
+  int32_t reserved1;
 } rl4co_am_decode_args;
 
 int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream);

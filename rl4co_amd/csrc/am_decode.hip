@@ -42,10 +42,22 @@
 //                 lse = log(tree_k(s_k)) ; lp_c = (z_c - zmax) - lse
 //   argmax      = maximum key, lowest index on ties (greedy: key = lp ; sampling:
 //                 key = exp(lp) / noise[node])
+//   top-k/top-p = (utils/decoding.py:109-188, only when the arguments ask for it; topkp.h) on the z above, after the
+//                 temperature: key(z) = order-preserving uint32 image of z ; e_c = exp(z_c - zmax) (the log-sum-exp's
+//                 terms) ; mass(S) = tree_k(sum over c in S, c = k, k+64, ... of e_c) — one order, so monotone in S.
+//                 top-k (0 < k < F): tau = largest key with #{key_c >= tau} >= k (32 counting passes) ; remove
+//                 key_c < tau (ties at tau kept) ; removed: z = -inf, e = 0.
+//                 top-p (0 < p < 1): order the entries by (z, c) ascending, A_c = mass(entries up to c), Z = mass(all),
+//                 remove c iff A_c <= thr, thr = min((1 - p) * Z, Z - 1 ulp) (the maximum always stays): cut = largest key with mass(key < cut) <= thr (32 mass
+//                 passes), then inside the tie group key == cut the largest list position lo with
+//                 mass(key < cut or (key == cut, c <= lo)) <= thr (bisection, <= 13 passes) ; removed as above.
+//                 lse = log(mass(kept)) (== the unfiltered lse when nothing is removed) ; removed entries: lp = -inf,
+//                 sampling key = -inf
 #include <hip/hip_runtime.h>
 
 #include "common.h"
 #include "rl4co_math.h"
+#include "topkp.h"
 
 namespace {
 
@@ -185,11 +197,13 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
 
 // One wave: raw logits lg[0..F) (list order) -> log-probs, selection, outputs, environment
 // transition on the LDS-resident mask. Returns the action; st is updated (incl. done).
-template <int ENV>
-__device__ inline int finalize_and_step(const rl4co_am_decode_args& a, TrajState& st, float* lg, const uint16_t* fl,
-                                        int F, uint8_t* mk, uint8_t* vis, const float* dem, float cap, int r, int t,
-                                        int N, int lane, const float* oplocs = nullptr, const float* opmax = nullptr,
-                                        const float* twdur = nullptr) {
+// FILT: the top-k / top-p filter instantiation (launched only when the arguments ask for it, so that the kernels without it
+// keep their registers); `xs`: 2 N floats of scratch (the score block, dead after pass 2), read only by the filter.
+template <int ENV, bool FILT = false>
+__device__ inline int finalize_and_step(const rl4co_am_decode_args& a, TrajState& st, float* lg, float* xs,
+                                        const uint16_t* fl, int F, uint8_t* mk, uint8_t* vis, const float* dem, float cap,
+                                        int r, int t, int N, int lane, const float* oplocs = nullptr,
+                                        const float* opmax = nullptr, const float* twdur = nullptr) {
   bool nan_seen = false;
   float zmax = kNegInf;
   for (int c = lane; c < F; c += 64) {
@@ -204,14 +218,23 @@ __device__ inline int finalize_and_step(const rl4co_am_decode_args& a, TrajState
   if (__any(nan_seen)) st.errbits |= RL4CO_EBIT_NAN_LOGIT;
   zmax = rl4co::bfly_max<1, 64>(zmax);
   float zsum = 0.0f;
-  for (int c = lane; c < F; c += 64) zsum = zsum + rl4co_expf(lg[c] - zmax);
-  zsum = rl4co::bfly_sum<1, 64>(zsum);
+  const int64_t tcol = (int64_t)a.t0 + t;
+  constexpr bool filt = FILT;
+  if (filt) {  // top-k / top-p: the same terms staged, removed entries -> z = -inf, e = 0; zsum over the kept ones
+    for (int c = lane; c < F; c += 64) xs[c] = rl4co_expf(lg[c] - zmax);
+    zsum = rl4co::topkp_filter(lg, xs, F, a.top_k, a.top_p, lane);
+    if (a.kept_bits)
+      rl4co::topkp_write_bits(a.kept_bits + ((int64_t)r * a.out_stride + tcol) * a.kept_words, a.kept_words, lg, fl, F,
+                              N, reinterpret_cast<uint32_t*>(xs + N), lane);
+  } else {
+    for (int c = lane; c < F; c += 64) zsum = zsum + rl4co_expf(lg[c] - zmax);
+    zsum = rl4co::bfly_sum<1, 64>(zsum);
+  }
   const float lse = rl4co_logf(zsum);
 
   float best = kNegInf;
   int bc = 0x7fffffff;  // best list position
   float ent = 0.0f;
-  const int64_t tcol = (int64_t)a.t0 + t;
   float* alp = a.all_logps ? a.all_logps + ((int64_t)r * a.out_stride + tcol) * N : nullptr;
   if (alp && F < N) {  // nodes outside the list have log-prob -inf
     for (int j = lane; j < N; j += 64)
@@ -229,6 +252,7 @@ __device__ inline int finalize_and_step(const rl4co_am_decode_args& a, TrajState
                                               a.philox_offset + (uint64_t)tcol, (uint32_t)r,
                                               (uint32_t)j);
       key = rl4co_expf(lp) / nz;  // multinomial(p,1) == argmax(p / Exp(1))
+      if (filt && !(lp > kNegInf)) key = kNegInf;  // a removed entry is never drawn, even if every kept key underflows
     }
     if (bc == 0x7fffffff || key > best) {  // strict '>' keeps the lowest index on ties
       best = key;
@@ -412,7 +436,7 @@ __host__ __device__ inline int row_cache_bytes(int N, int S, int esz) {
   return S > 0 ? S * 3 * kD * esz + lds_pad(N) + S : 0;
 }
 
-template <class C, int ENV, bool UNFOLD = false>
+template <class C, int ENV, bool UNFOLD = false, bool FILT = false>
 __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_args a, const int S) {
   constexpr int EPL = C::EPL;
   constexpr int LPR = kD / EPL;   // lanes per cache row
@@ -715,7 +739,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
     }
     wave_lds_sync();
 
-    const int bi = finalize_and_step<ENV>(a, st, lg, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur);
+    const int bi = finalize_and_step<ENV, FILT>(a, st, lg, sc, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur);
     if (caching && rslot[bi] != kRowCacheNone && !candidate(bi)) {
       // the resident node left: its slot goes to the highest candidate not resident, which the next step that lists
       // it reads from HBM anyway
@@ -791,7 +815,7 @@ constexpr int kLdsGroups = 16;
 // (the lane-strided sum of the exponentials and its butterfly, the entropy) is still taken by wave 0 in finalize_and_step's
 // own order from the staged terms; maxima and the (key, lowest position) arg-max are exact in any order. `xs`: 2 nw + 16
 // floats of scratch (the score block, dead between B3 and the next step). Returns the selected list position (wave 0).
-template <int ENV>
+template <int ENV, bool FILT = false>
 __device__ inline int wide_scores(const rl4co_am_decode_args& a, TrajState& st, float* lg, const uint16_t* fl, int F,
                                   const uint8_t* mk, float* xs, int nw, int r, int t, int N, int tid) {
   constexpr int T = 64 * kLdsWaves;
@@ -820,15 +844,23 @@ __device__ inline int wide_scores(const rl4co_am_decode_args& a, TrajState& st, 
   if ((xw[4] + xw[5]) + (xw[6] + xw[7]) != 0.0f) st.errbits |= RL4CO_EBIT_NAN_LOGIT;
   for (int c = tid; c < F; c += T) ex[c] = rl4co_expf(lg[c] - zmax);
   __syncthreads();
+  const int64_t tcol = (int64_t)a.t0 + t;
+  constexpr bool filt = FILT;
   if (w == 0) {
     float zsum = 0.0f;
-    for (int c = lane; c < F; c += 64) zsum = zsum + ex[c];
-    zsum = rl4co::bfly_sum<1, 64>(zsum);
+    if (filt) {  // top-k / top-p over the staged terms (wave 0; the other waves wait at the barrier below)
+      zsum = rl4co::topkp_filter(lg, ex, F, a.top_k, a.top_p, lane);
+      if (a.kept_bits)
+        rl4co::topkp_write_bits(a.kept_bits + ((int64_t)r * a.out_stride + tcol) * a.kept_words, a.kept_words, lg, fl,
+                                F, N, reinterpret_cast<uint32_t*>(xw + 16), lane);
+    } else {
+      for (int c = lane; c < F; c += 64) zsum = zsum + ex[c];
+      zsum = rl4co::bfly_sum<1, 64>(zsum);
+    }
     if (lane == 0) xw[8] = rl4co_logf(zsum);
   }
   __syncthreads();
   const float lse = xw[8];
-  const int64_t tcol = (int64_t)a.t0 + t;
   float* alp = a.all_logps ? a.all_logps + ((int64_t)r * a.out_stride + tcol) * N : nullptr;
   if (alp && F < N) {  // nodes outside the list have log-prob -inf
     for (int j = tid; j < N; j += T)
@@ -846,6 +878,7 @@ __device__ inline int wide_scores(const rl4co_am_decode_args& a, TrajState& st, 
                                               a.philox_offset + (uint64_t)tcol, (uint32_t)r,
                                               (uint32_t)j);
       key = rl4co_expf(lp) / nz;  // multinomial(p,1) == argmax(p / Exp(1))
+      if (filt && !(lp > kNegInf)) key = kNegInf;  // a removed entry is never drawn
     }
     ex[c] = key;
     if (alp) alp[j] = lp;
@@ -882,7 +915,7 @@ __host__ __device__ inline int lds_variant_bytes(int N) { return 3 * N * kD * 2 
 // Four workgroups per CU (<= 128 registers): CVRP-500 x 1024 is 1024 workgroups = exactly four per CU, ONE round. The half
 // (fp16) builds took 130 - 138 registers under a bound of two — three per CU, so a quarter of the trajectories waited for
 // a second round: 25.3 ms per C5 step against 19.9 with bf16 planes (r04).
-template <int ENV, bool RESIDENT, class C = CacheBF16>  // C: CacheBF16 or CacheF16 (same 16-byte lanes, different convert)
+template <int ENV, bool RESIDENT, class C = CacheBF16, bool FILT = false>  // C: CacheBF16 or CacheF16 (same 16-byte lanes)
 __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const rl4co_am_decode_args a) {
   constexpr int EPL = 8, LPR = 16, LPH = 2;
   constexpr int U = 4;  // list entries per wave handled per unrolled block
@@ -1130,7 +1163,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
 
     // ---- all waves: clip, exponentials, log-probs, sampling keys; wave 0: the reductions, then the environment
     // transition and the next step's list -----------------------------------------------------------------
-    const int bc = wide_scores<ENV>(a, st, lg, fl, F, mk, sc, nw, r, t, N, tid);
+    const int bc = wide_scores<ENV, FILT>(a, st, lg, fl, F, mk, sc, nw, r, t, N, tid);
     if (w == 0) {
       commit_and_step<ENV>(a, st, lg, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur, bc);
       const int Fn = build_list(a, mk, fl, N, lane);
@@ -1187,16 +1220,20 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   }
 }
 
-template <int ENV, bool RESIDENT, class C>
-int launch_wide_c(const rl4co_am_decode_args& a, hipStream_t stream) {
+template <int ENV, bool RESIDENT, class C, bool FILT>
+int launch_wide_f(const rl4co_am_decode_args& a, hipStream_t stream) {
   const int lds = RESIDENT ? lds_variant_bytes(a.N) : wide_scratch_bytes(a.N);
   if (lds > 64 * 1024) {
-    RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(am_decode_wide_kernel<ENV, RESIDENT, C>),
+    RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(am_decode_wide_kernel<ENV, RESIDENT, C, FILT>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
-  hipLaunchKernelGGL((am_decode_wide_kernel<ENV, RESIDENT, C>), dim3(a.B), dim3(64 * kLdsWaves), lds, stream, a);
+  hipLaunchKernelGGL((am_decode_wide_kernel<ENV, RESIDENT, C, FILT>), dim3(a.B), dim3(64 * kLdsWaves), lds, stream, a);
   RL4CO_HIP_TRY(hipGetLastError());
   return RL4CO_OK;
+}
+template <int ENV, bool RESIDENT, class C>
+int launch_wide_c(const rl4co_am_decode_args& a, hipStream_t stream) {
+  return rl4co::topkp_on(a) ? launch_wide_f<ENV, RESIDENT, C, true>(a, stream) : launch_wide_f<ENV, RESIDENT, C, false>(a, stream);
 }
 template <int ENV, bool RESIDENT>
 int launch_wide(const rl4co_am_decode_args& a, hipStream_t stream) {
@@ -1211,7 +1248,8 @@ inline int resolve_variant(const rl4co_am_decode_args& a) {
   const bool f16 = a.cache_dtype == RL4CO_DT_F16;  // fp16 planes: every variant the bf16 planes have
   const bool bf16 = a.cache_dtype == RL4CO_DT_BF16 || f16;  // (16-bit planes)
   // multistart on the matrix cores (am_decode_ms.hip): 16-bit planes, N <= 128, plain outputs; every environment
-  const bool ms_ok = bf16 && a.N <= 128 && a.B_inst > 0 && a.all_logps == nullptr && a.entropy == nullptr;
+  const bool ms_ok = bf16 && a.N <= 128 && a.B_inst > 0 && a.all_logps == nullptr && a.entropy == nullptr &&
+                     !rl4co::topkp_on(a);  // the top-k / top-p filter is not in am_decode_ms.hip
   if (a.variant == RL4CO_VARIANT_MS) return ms_ok ? RL4CO_VARIANT_MS : -1;
   const bool fits = bf16 && lds_variant_bytes(a.N) <= 80 * 1024;
   const bool wide_ok = bf16 && wide_scratch_bytes(a.N) <= 64 * 1024;
@@ -1269,17 +1307,21 @@ int row_cache_slots(const rl4co_am_decode_args& a, int esz, bool unfold) {
   return esz == 4 ? 0 : S;
 }
 
-template <class C, int ENV, bool UNFOLD = false>
-int launch(const rl4co_am_decode_args& a, hipStream_t stream) {
+template <class C, int ENV, bool UNFOLD, bool FILT>
+int launch_f(const rl4co_am_decode_args& a, hipStream_t stream) {
   const int S = row_cache_slots(a, (int)sizeof(typename C::elem), UNFOLD);
   const int lds = rl4co_am_decode_lds_bytes(a.N, ENV) + row_cache_bytes(a.N, S, (int)sizeof(typename C::elem));
   if (lds > 64 * 1024) {
-    RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(am_decode_kernel<C, ENV, UNFOLD>),
+    RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(am_decode_kernel<C, ENV, UNFOLD, FILT>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
-  hipLaunchKernelGGL((am_decode_kernel<C, ENV, UNFOLD>), dim3(a.B), dim3(64), lds, stream, a, S);
+  hipLaunchKernelGGL((am_decode_kernel<C, ENV, UNFOLD, FILT>), dim3(a.B), dim3(64), lds, stream, a, S);
   RL4CO_HIP_TRY(hipGetLastError());
   return RL4CO_OK;
+}
+template <class C, int ENV, bool UNFOLD = false>
+int launch(const rl4co_am_decode_args& a, hipStream_t stream) {
+  return rl4co::topkp_on(a) ? launch_f<C, ENV, UNFOLD, true>(a, stream) : launch_f<C, ENV, UNFOLD, false>(a, stream);
 }
 
 }  // namespace
@@ -1334,6 +1376,9 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
   RL4CO_REQUIRE(a.temperature > 0.0f);
   RL4CO_REQUIRE((reinterpret_cast<uintptr_t>(a.steps_summary) & 7) == 0);  // [2..3] is one 64-bit counter
   RL4CO_REQUIRE(a.mode != RL4CO_DECODE_EVALUATE || a.forced_actions != nullptr);
+  RL4CO_REQUIRE(a.top_p == a.top_p && a.top_p <= 1.0f);  // decoding.py:147 "top-p should be in (0, 1]."
+  RL4CO_REQUIRE(a.kept_bits == nullptr || (a.kept_words >= (a.N + 31) / 32 && a.kept_words % 4 == 0 &&
+                                           (reinterpret_cast<uintptr_t>(a.kept_bits) & 3) == 0));
   if (a.env == RL4CO_ENV_TSP) {
     RL4CO_REQUIRE(((a.ctx_first && a.q_step0) || a.unfold) && a.first_node && a.step_i);
   } else if (a.env == RL4CO_ENV_CVRP) {

@@ -227,11 +227,17 @@ def am_decode(
     n_steps: Tensor | None = None,
     steps_summary: Tensor | None = None,
     variant: str = "auto",
+    top_k: int = 0,
+    top_p: float = 0.0,
+    kept_bits: Tensor | None = None,
 ) -> None:
     """Run ``max_steps`` fused decode steps (1 = a single step, >= horizon = whole rollout).
 
     ``state`` holds the environment tensors (updated in place): action_mask [B,N] bool,
     current_node, done; TSP: first_node, i; CVRP: demand, used_capacity, vehicle_capacity, visited.
+    ``top_k`` / ``top_p``: the reference's top-k / nucleus filter (utils/decoding.py:109-188; see ``decoding_filter``).
+    ``kept_bits`` [B, out_stride, W] int32 (W = 4 * ceil(N / 128), the layout of ``env_replay``'s mask bits): per step taken,
+    bit j of the row = node j kept (feasible and not filtered); the columns of steps not taken are left as they are.
     """
     env_name = cache.env_name
     a = _lib.AmDecodeArgs()
@@ -335,8 +341,30 @@ def am_decode(
             raise ValueError("steps_summary must be 4 int32 words on an 8-byte boundary (rl4co_am_decode_args.steps_summary)")
     a.steps_summary = _ptr(steps_summary)
     a.err = _ptr(_dev(err, torch.int32, "err"))
+    a.top_k, a.top_p = decoding_filter(top_k, top_p, n)
+    if kept_bits is not None:
+        _dev(kept_bits, torch.int32, "kept_bits")
+        words = 4 * ((n + 127) // 128)
+        if tuple(kept_bits.shape) != (b, actions.shape[1], words) or not kept_bits.is_contiguous():
+            raise ValueError(f"kept_bits must be a contiguous [{b}, {actions.shape[1]}, {words}] int32 tensor")
+        a.kept_bits, a.kept_words = _ptr(kept_bits), words
     st = _lib.lib().rl4co_am_decode(C.byref(a), _stream())
     _lib.check(st, "rl4co_am_decode")
+
+
+def decoding_filter(top_k, top_p, n: int) -> tuple[int, float]:
+    """The top-k / top-p arguments of utils/decoding.py:109-188 as the kernel takes them: ``top_k <= 0`` is off and is
+    clamped to ``n`` (k >= n removes nothing: 0); ``top_p <= 0`` or ``>= 1`` is off (0.0); ``top_p > 1`` raises the
+    reference's AssertionError (decoding.py:147)."""
+    k = int(top_k or 0)
+    p = float(top_p or 0.0)
+    assert p <= 1.0, "top-p should be in (0, 1]."
+    k = min(k, n) if k > 0 else 0
+    if k >= n:
+        k = 0
+    if not (0.0 < p < 1.0):
+        p = 0.0
+    return k, p
 
 
 def op_max_length(locs: Tensor, max_length: Tensor) -> Tensor:

@@ -778,10 +778,13 @@ class AttentionModelPolicy(nn.Module):
         seed = decoding_kwargs.pop("seed", None)
         multisample = bool(decoding_kwargs.pop("multisample", False))
         select_start_nodes_fn = decoding_kwargs.pop("select_start_nodes_fn", None)
-        # sampling modifiers outside the path (top-k / top-p / a second temperature): their neutral values pass
-        if decoding_kwargs.pop("top_k", 0) or decoding_kwargs.pop("top_p", 0.0):
-            raise NotImplementedError("top-k / top-p sampling is not part of the fused decode kernel")
-        decoding_kwargs.pop("top_p", None)
+        # top-k / top-p (decoding.py:109-188): filtered inside the decode kernels; validated as process_logits does (k is
+        # clamped to the node count in _forward: kernels.decoding_filter)
+        top_k = int(decoding_kwargs.pop("top_k", 0) or 0)
+        top_p = float(decoding_kwargs.pop("top_p", 0.0) or 0.0)
+        if top_p > 0:
+            assert top_p <= 1.0, "top-p should be in (0, 1]."
+        # a second temperature stays outside the path
         if decoding_kwargs.pop("softmax_temp", None) is not None:
             raise NotImplementedError("softmax_temp is not supported; use temperature")
         # decoding.py:238-255, in the reference's order: the flags are checked as PASSED, then overridden by the counts
@@ -803,7 +806,8 @@ class AttentionModelPolicy(nn.Module):
 
         return SimpleNamespace(mode=mode, multistart=multistart, n_rep=n_rep, temperature=temperature, tanh_clipping=tanh_clipping,
                                mask_logits=mask_logits, return_all_logp=return_all_logp, store_all_logp=store_all_logp,
-                               select_best=select_best, exp_noise=exp_noise, seed=seed, select_start_nodes_fn=select_start_nodes_fn)
+                               select_best=select_best, exp_noise=exp_noise, seed=seed, select_start_nodes_fn=select_start_nodes_fn,
+                               top_k=top_k, top_p=top_p)
 
     def _forward(self, td: TensorDict, env: str | RL4COEnvBase | None = None, phase: str = "train",
                  calc_reward: bool = True, return_actions: bool = True, return_entropy: bool = False,
@@ -841,8 +845,12 @@ class AttentionModelPolicy(nn.Module):
         device = td["action_mask"].device
         b_inst, n = td["action_mask"].shape[0], td["action_mask"].shape[-1]
         b = b_inst * max(n_rep, 1)
+        top_k, top_p = K.decoding_filter(opt.top_k, opt.top_p, n)
+        filtered = bool(top_k or top_p)
+        if filtered and not td["action_mask"].is_cuda:  # (the CPU specified-order oracle has no filter)
+            raise NotImplementedError("top-k / top-p sampling runs inside the MI355X decode kernels only")
         cache_g = None
-        if cache is None and grad_path and self.fused_backward and hidden.is_cuda and self.fold:
+        if cache is None and grad_path and self.fused_backward and hidden.is_cuda and self.fold and not filtered:
             from . import teacher
 
             if teacher.supports(self.env_name, cache_dtype, n) and not return_entropy:
@@ -887,6 +895,11 @@ class AttentionModelPolicy(nn.Module):
         out_actions = torch.zeros((b, tmax), dtype=torch.int64, device=device)
         logps = torch.zeros((b, tmax), dtype=torch.float32, device=device)
         all_logps = torch.zeros((b, tmax, n), dtype=torch.float32, device=device) if store_all_logp else None
+        # training with a filter: the rollout's kept sets, ANDed into the re-evaluation's logit mask (the re-evaluated logits
+        # differ from the rollout's in the last bits: a recomputed cut could drop the sampled action). Columns of steps not
+        # taken (an imposed first node, padding after done) stay all ones: neutral
+        kept_bits = (torch.full((b, tmax, 4 * ((n + 127) // 128)), -1, dtype=torch.int32, device=device)
+                     if (grad_path and filtered) else None)
 
         if t0 == 1:
             if select_start_nodes_fn is not None:  # decoding.py:308-311: (td, env, num_starts) -> [num_starts * B] nodes, s-major
@@ -911,6 +924,7 @@ class AttentionModelPolicy(nn.Module):
             mask_logits=mask_logits, exp_noise=exp_noise, philox_seed=philox_seed, philox_seed_dev=seed_dev,
             forced_actions=forced, all_logps=all_logps, steps_summary=status[2:6],
             variant=getattr(self, "decode_variant", "auto"),  # ("auto": the library chooses; bench / probes may pin one)
+            **(dict(top_k=top_k, top_p=top_p, kept_bits=kept_bits) if filtered else {}),  # (only when asked for)
         )
         if self.decode_events is not None:
             ev1.record()
@@ -954,6 +968,7 @@ class AttentionModelPolicy(nn.Module):
             return_entropy=return_entropy, select_best=select_best, calc_reward=calc_reward, checked=checked,
             return_sum_log_likelihood=return_sum_log_likelihood, return_actions=return_actions,
             return_all_logp=return_all_logp, return_hidden=return_hidden, return_init_embeds=return_init_embeds,
+            kept_bits=kept_bits,
         )
         if defer:
             return lambda: self._finish_rollout(r)
@@ -1045,7 +1060,12 @@ class AttentionModelPolicy(nn.Module):
                 meta.update(real_prize=td["real_prize"], prize_required=td["prize_required"])
             step_logps = teacher.teacher_forced_logps(self.env_name, cache_g, cache, out_actions, logps, meta)
         elif grad_path:
-            if hidden.is_cuda and self.fused_backward and not return_entropy:
+            kept = r.kept_bits[:, :t_used].contiguous() if r.kept_bits is not None else None
+            if kept is not None and hidden.is_cuda and self.fused_backward:
+                _l.warn_fallback(f"teacher-topkp/{self.env_name}",
+                                 f"teacher-forced backward for {self.env_name}: the top-k / top-p filter is not in the backward "
+                                 "kernels — dense re-evaluation of all steps with autograd, the rollout's kept sets as the logit mask")
+            elif hidden.is_cuda and self.fused_backward and not return_entropy:
                 from . import _lib as _l
 
                 t_max = __import__("rl4co_amd.teacher", fromlist=["max_nodes"]).max_nodes()
@@ -1056,7 +1076,7 @@ class AttentionModelPolicy(nn.Module):
                                  f"teacher-forced backward for {self.env_name}: {why} — dense re-evaluation of all steps with autograd "
                                  "(16-bit regimes: glimpse attention and log-prob kernels between library GEMMs; fp32: torch)")
             step_logps = self.evaluate_log_probs(td, hidden, out_actions, n_rep, tanh_clipping, temperature,
-                                                 mask_logits, skip_first=(t0 == 1), return_full=return_entropy)
+                                                 mask_logits, skip_first=(t0 == 1), return_full=return_entropy, kept_bits=kept)
             if return_entropy:
                 step_logps, full_logp = step_logps
         else:
@@ -1187,8 +1207,12 @@ class AttentionModelPolicy(nn.Module):
 
     # -- teacher-forced, differentiable re-evaluation (row N1 of SURVEY.md §8f) -------------------
     def evaluate_log_probs(self, td, hidden: Tensor, actions: Tensor, n_rep: int, tanh_clipping: float,
-                           temperature: float, mask_logits: bool, skip_first: bool = False, return_full: bool = False):
+                           temperature: float, mask_logits: bool, skip_first: bool = False, return_full: bool = False,
+                           kept_bits: Tensor | None = None):
         """log p(a_t | s_t) for all t at once, with autograd through encoder and decoder weights.
+
+        ``kept_bits`` [B, T, W] int32 (a filtered rollout's kept sets, kernels.am_decode): ANDed into the mask of the logit
+        tail only — the glimpse attention keeps the feasibility mask, as the reference filters the logits alone.
 
         With the actions known every step's query is known up front, so the T sequential
         single-query attentions of the reference loop become ONE masked [T x N] attention per
@@ -1255,7 +1279,10 @@ class AttentionModelPolicy(nn.Module):
             raw = torch.bmm(gl, kl_inst.transpose(1, 2))
             if s > 1:
                 raw = raw.view(b_inst, s, t_len, n).transpose(0, 1).reshape(b, t_len, n)
-            step_logps = train_ops.logit_logp(raw.float(), mask_bits if mask_logits else None, actions, tanh_clipping, temperature)
+            lmask = mask_bits if mask_logits else None
+            if kept_bits is not None:  # the rollout's kept sets, for the logit tail only
+                lmask = kept_bits if lmask is None else lmask & kept_bits
+            step_logps = train_ops.logit_logp(raw.float(), lmask, actions, tanh_clipping, temperature)
             if skip_first:  # multistart: the first action is imposed, its log-prob is 0 (decoding.py:318-323)
                 step_logps = torch.cat([torch.zeros_like(step_logps[:, :1]), step_logps[:, 1:]], 1)
             return step_logps
@@ -1264,6 +1291,9 @@ class AttentionModelPolicy(nn.Module):
             logits = torch.tanh(logits) * tanh_clipping
         if mask_logits:
             logits = logits.masked_fill(~masks, float("-inf"))
+        if kept_bits is not None:  # removed by the rollout's filter: -inf, renormalised over the kept set
+            j = torch.arange(n, device=kept_bits.device)
+            logits = logits.masked_fill(((kept_bits[..., j // 32] >> (j % 32)) & 1) == 0, float("-inf"))
         logp = F.log_softmax(logits / temperature, dim=-1)
         step_logps = logp.gather(-1, actions[..., None]).squeeze(-1)
         if skip_first:  # multistart: the first action is imposed, its log-prob is 0 (decoding.py:318-323)
