@@ -20,6 +20,7 @@ from torch import Tensor
 
 from . import _lib
 from .cache import EMBED_DIM, FoldedCache, fold_weights
+from .envspec import customer_features, spec
 
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
 
@@ -269,27 +270,21 @@ class PackedEncoder:
         q_bias = torch.empty((b, d), dtype=torch.float32, device=dev) if t["w_fixed"] is not None else None
         hidden = torch.empty((b, n, d), dtype=torch.float32, device=dev) if (want_hidden or not fold) else None
         a = AmEncoderArgs()
-        a.env = {"tsp": _lib.ENV_TSP, "pdp": _lib.ENV_PDP}.get(pol.env_name, _lib.ENV_CVRP)
+        sp = spec(pol.env_name)
+        # the encoder kernels have three init-embedding modes, named by the environment that has it alone: TSP (every node
+        # alike), PDP (depot | pickups | deliveries), CVRP (depot | customers with 1-4 feature columns behind x, y)
+        a.env = _lib.ENV_CVRP if sp.features else sp.env_id
         a.B, a.N, a.num_layers, a.norm = b, n, self.num_layers, self.norm_kind
         a.cache_dtype, a.act_dtype = _lib.dtype_id(cache_dtype), _lib.dtype_id(self.act_dtype)
         a.ctx_dtype = _lib.dtype_id(ctx_dt) if ctx_dt != torch.float32 else 0
         a.locs = locs.data_ptr()
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-        if pol.env_name in ("cvrp", "op", "pctsp", "cvrptw"):
-            # OP embeds the customers' prize where CVRP embeds their demand (init.py:115-136, 254-280);
-            # PCTSP the expected prize and, as a fourth feature, the penalty (init.py:283-312)
-            third = {"cvrp": "demand", "op": "prize", "pctsp": "expected_prize", "cvrptw": "demand"}[pol.env_name]
-            third = td[third][..., 1:] if pol.env_name == "op" else td[third]
-            demand = third.float().contiguous()
-            a.demand, a.w_depot, a.b_depot = demand.data_ptr(), ptr(t["w_depot"]), ptr(t["b_depot"])
-            if pol.env_name == "pctsp":
-                penalty = td["penalty"][..., 1:].float().contiguous()
-                a.feature4 = penalty.data_ptr()
-            if pol.env_name == "cvrptw":  # init.py:139-153: + tw start, tw end, service time
-                tw0 = td["time_windows"][..., 1:, 0].float().contiguous()
-                tw1 = td["time_windows"][..., 1:, 1].float().contiguous()
-                dur = td["durations"][..., 1:].float().contiguous()
-                a.feature4, a.feature5, a.feature6 = tw0.data_ptr(), tw1.data_ptr(), dur.data_ptr()
+        if sp.features:
+            # the customers' feature columns (init.py:115-153, 254-312; envspec.py), each a contiguous fp32 [B, n - 1]
+            cols = [c.contiguous() for f in customer_features(sp, td) for c in f.unbind(-1)]
+            for slot, c in zip(("demand", "feature4", "feature5", "feature6"), cols):
+                setattr(a, slot, c.data_ptr())
+            a.w_depot, a.b_depot = ptr(t["w_depot"]), ptr(t["b_depot"])
         if pol.env_name == "pdp":
             a.w_depot, a.b_depot = ptr(t["w_depot"]), ptr(t["b_depot"])
             a.w_extra, a.b_extra = ptr(t["w_extra"]), ptr(t["b_extra"])

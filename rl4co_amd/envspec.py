@@ -1,0 +1,142 @@
+"""One table of per-environment facts behind the host-side kernel bindings.
+
+The kernels take the environment as a template parameter and a fixed set of argument slots (``rl4co_am_decode_args``:
+``demand``, ``used_capacity``, ``vehicle_capacity``, ``visited``, ``locs``, ...). Which state tensor of which environment
+rides in which slot is stated HERE, once; ``kernels.bind_env_state`` / ``kernels.env_step``, ``policy`` (state, final
+TensorDict, replay, horizon), ``teacher.run_backward`` and the encoder's feature columns read it. Adding an environment
+means adding a record below. Data only: nothing here touches the GPU or loads the library.
+"""
+from __future__ import annotations
+
+from typing import Callable, NamedTuple
+
+from . import _lib
+from .cache import canonical_env
+
+
+class Field(NamedTuple):
+    """One state tensor. ``kind`` "traj": per trajectory — expanded over the starts s-major and cloned, the kernels write
+    it; "inst": instance data — shared [B_inst, ...], contiguous, cast to ``dtype``. ``slot``: the field of
+    ``rl4co_am_decode_args`` it rides in (the running context scalar rides in ``scalar`` of ``rl4co_env_replay_args``).
+    ``shape``: "B" / "BN" as in the state; "B1": [B] in the state, [B, 1] in the final TensorDict; instance data: the
+    dims behind B_inst ("N-1" = one entry per customer)."""
+    key: str
+    kind: str
+    dtype: str  # "i64" | "f32" | "u8" (bool or uint8: the same storage)
+    slot: str | None
+    shape: str
+
+
+class Scalar(NamedTuple):
+    """The context scalar ``base - state[running]`` (context.py:105-213). ``base``: a per-trajectory state key, or an
+    instance table whose column 0 is repeated over the starts (``base_col0``: OP's entry limit of the depot = max_length).
+    ``clamp``: at 0 from below (PCTSP, context.py:195). ``clock``: a second scalar taken as it is (CVRPTW's current time)."""
+    running: str
+    base: str
+    base_col0: bool = False
+    clamp: bool = False
+    clock: str | None = None
+
+
+class EnvSpec(NamedTuple):
+    name: str
+    env_id: int  # RL4CO_ENV_* of include/rl4co_amd.h
+    has_depot: bool
+    horizon: Callable[[int], int]  # longest rollout over n nodes (depot included)
+    fields: tuple[Field, ...]
+    scalar: Scalar | None
+    step: tuple[str, tuple[str, ...]]  # the ``kernels`` step entry and the state keys it takes between action and err
+    passthrough: tuple[str, ...]  # td keys the final TensorDict repeats over the starts as they are
+    features: tuple[tuple[str, bool], ...] = ()  # customer init-embedding columns behind (x, y): (td key, drop the depot column)
+    depot_embed: bool = True  # the depot has an init embedding of its own
+    ctx_first: bool = False  # context = (first node, current node), placeholder at step 0; else current node (+ scalars)
+
+    def keys(self, kind: str | None = None) -> tuple[str, ...]:
+        return tuple(f.key for f in self.fields if kind in (None, f.kind))
+
+    @property
+    def teacher_keys(self) -> tuple[str, ...]:
+        """What the backward kernels read of the INSTANCE (td keys): the instance data and a per-instance scalar base."""
+        base = () if self.scalar is None or self.scalar.base_col0 else (self.scalar.base,)
+        return self.keys("inst") + base
+
+
+def _fields(current_node: str, *own: tuple) -> tuple[Field, ...]:
+    common = (("action_mask", "traj", "u8", "action_mask", "BN"), ("current_node", "traj", "i64", "current_node", current_node),
+              ("done", "traj", "u8", "done", "B"))
+    return tuple(Field(*f) for f in common + own)
+
+
+_I = ("i", "traj", "i64", "step_i", "B")
+_VISITED = ("visited", "traj", "u8", "visited", "BN")
+_CVRP_FIELDS = (("demand", "inst", "f32", "demand", "N-1"), ("used_capacity", "traj", "f32", "used_capacity", "B1"),
+                ("vehicle_capacity", "traj", "f32", "vehicle_capacity", "B1"), _VISITED)
+
+SPECS = {s.name: s for s in (
+    # TSP: exactly n steps
+    EnvSpec("tsp", _lib.ENV_TSP, False, lambda n: n,
+            _fields("B", ("first_node", "traj", "i64", "first_node", "B"), ("i", "traj", "i64", "step_i", "B1")),
+            None, ("tsp_step", ("action_mask", "first_node", "current_node", "i", "done")),
+            ("locs",), depot_embed=False, ctx_first=True),
+    # CVRP: every customer + at most one depot visit per customer + 1
+    EnvSpec("cvrp", _lib.ENV_CVRP, True, lambda n: 2 * n, _fields("B1", *_CVRP_FIELDS),
+            Scalar("used_capacity", "vehicle_capacity"),
+            ("cvrp_step", ("demand", "used_capacity", "vehicle_capacity", "visited", "current_node", "action_mask", "done")),
+            ("locs", "demand"), features=(("demand", False),)),
+    # OP: every customer once, the closing depot visit, and a depot pick at step 0 costs one more. The tour length rides
+    # in the used_capacity slot; the per-node entry limits (max_length table) and the coordinates are instance data
+    EnvSpec("op", _lib.ENV_OP, True, lambda n: n + 2,
+            _fields("B1", ("locs", "inst", "f32", "locs", "N2"), ("max_length", "inst", "f32", "max_length", "N"),
+                    ("tour_length", "traj", "f32", "used_capacity", "B"), _I, _VISITED),
+            Scalar("tour_length", "max_length", base_col0=True),
+            ("op_step", ("locs", "max_length", "tour_length", "visited", "current_node", "i", "action_mask", "done")),
+            ("locs", "prize", "max_length"), features=(("prize", True),)),
+    # PCTSP: every customer once and the closing depot visit (the depot is masked at step 0). The real prize per node
+    # (depot column 0) rides in the demand slot, the prize collected so far in used_capacity, prize_required in
+    # vehicle_capacity
+    EnvSpec("pctsp", _lib.ENV_PCTSP, True, lambda n: n,
+            _fields("B", ("real_prize", "inst", "f32", "demand", "N"), ("cur_total_prize", "traj", "f32", "used_capacity", "B"),
+                    ("prize_required", "traj", "f32", "vehicle_capacity", "B"), _I, _VISITED),
+            Scalar("cur_total_prize", "prize_required", clamp=True),
+            ("pctsp_step", ("real_prize", "cur_total_prize", "visited", "current_node", "i", "action_mask", "done")),
+            ("locs", "real_prize", "expected_prize", "penalty"), features=(("expected_prize", False), ("penalty", True))),
+    # PDP: every node once (the depot too under force_start_at_depot). `available` rides in the visited slot; no scalar
+    EnvSpec("pdp", _lib.ENV_PDP, True, lambda n: n,
+            _fields("B1", ("available", "traj", "u8", "visited", "BN"), ("to_deliver", "traj", "u8", "to_deliver", "BN"),
+                    ("i", "traj", "i64", "step_i", "B1")),
+            None, ("pdp_step", ("available", "to_deliver", "current_node", "i", "action_mask", "done")),
+            ("locs",)),
+    # CVRPTW: CVRP + clock; coordinates, (start, end) windows and service times as fp32 instance data (the reference
+    # keeps integer-valued windows)
+    EnvSpec("cvrptw", _lib.ENV_CVRPTW, True, lambda n: 2 * n,
+            _fields("B1", *_CVRP_FIELDS, ("locs", "inst", "f32", "locs", "N2"),
+                    ("time_windows", "inst", "f32", "time_windows", "N2"), ("durations", "inst", "f32", "durations", "N"),
+                    ("current_time", "traj", "f32", "current_time", "B1")),
+            Scalar("used_capacity", "vehicle_capacity", clock="current_time"),
+            ("cvrptw_step", ("demand", "locs", "time_windows", "durations", "used_capacity", "vehicle_capacity", "current_time",
+                             "visited", "current_node", "action_mask", "done")),
+            ("locs", "demand", "time_windows", "durations"),
+            features=(("demand", False), ("time_windows", True), ("durations", True))),
+)}
+
+
+def spec(env_name: str) -> EnvSpec:
+    return SPECS[canonical_env(env_name)]
+
+
+def rem_base(sp: EnvSpec, state: dict, b: int):
+    """The context scalar's minuend, one per trajectory (None: no scalar)."""
+    if sp.scalar is None:
+        return None
+    base = state[sp.scalar.base]
+    if sp.scalar.base_col0:
+        base = base[:, 0]
+        base = (base if base.shape[0] == b else base.repeat(b // base.shape[0])).contiguous()
+    return base
+
+
+def customer_features(sp: EnvSpec, td) -> list:
+    """The customers' init-embedding features behind the coordinates (env_embeddings/init.py), fp32 [B, n - 1, k] each in
+    the order of the embedding's input columns."""
+    cols = [(td[key][:, 1:] if drop_depot else td[key]).float() for key, drop_depot in sp.features]
+    return [c if c.dim() == 3 else c[..., None] for c in cols]

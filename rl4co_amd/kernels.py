@@ -13,9 +13,10 @@ from torch import Tensor
 
 from . import _lib
 from .cache import FoldedCache
+from .envspec import SPECS, EnvSpec, spec
 
 MODE_IDS = {"greedy": _lib.DECODE_GREEDY, "sampling": _lib.DECODE_SAMPLE, "evaluate": _lib.DECODE_EVALUATE}
-ENV_IDS = {"tsp": _lib.ENV_TSP, "cvrp": _lib.ENV_CVRP, "op": _lib.ENV_OP, "pctsp": _lib.ENV_PCTSP, "pdp": _lib.ENV_PDP, "cvrptw": _lib.ENV_CVRPTW}
+ENV_IDS = {name: sp.env_id for name, sp in SPECS.items()}
 VARIANT_IDS = {"auto": _lib.VARIANT_AUTO, "stream": _lib.VARIANT_STREAM, "lds": _lib.VARIANT_LDS, "wide": _lib.VARIANT_WIDE, "ms": _lib.VARIANT_MS}
 
 
@@ -91,6 +92,42 @@ def _check_rows(b: int, **tensors) -> None:
     for name, t in tensors.items():
         if t is not None and t.shape[0] != b:
             raise ValueError(f"{name} has {t.shape[0]} rows, action_mask has {b}")
+
+
+_SLOT_DTYPES = {"i64": torch.int64, "f32": torch.float32}
+
+
+def bind_env_state(a, sp: EnvSpec, state: dict, b: int, n: int) -> int:
+    """Fill the state slots of an ``AmDecodeArgs`` / ``EnvReplayArgs`` from the environment's table (envspec.py): every
+    tensor on the device, of its dtype and contiguous; per-trajectory tensors with ``b`` rows, instance data with one row
+    count (returned: B_inst; ``b`` for an environment without instance data) and its shape behind it."""
+    replay = isinstance(a, _lib.EnvReplayArgs)
+    b_inst = None
+    for f in sp.fields:
+        t = _u8(state[f.key], f.key) if f.dtype == "u8" else _dev(state[f.key], _SLOT_DTYPES[f.dtype], f.key)
+        if f.kind == "traj":
+            _check_rows(b, **{f.key: t})
+        else:
+            b_inst = t.shape[0] if b_inst is None else b_inst
+            if t.shape[0] != b_inst:
+                raise ValueError(f"{f.key} has {t.shape[0]} rows, expected {b_inst}")
+            dims = {"N-1": (n - 1,), "N": (n,), "N2": (n, 2)}[f.shape]
+            if tuple(t.shape[1:]) != dims:
+                raise ValueError(f"{f.key} must be [B_inst, {', '.join(map(str, dims))}], got {tuple(t.shape)}")
+        # (the replay kernel keeps the running context scalar, whichever it is, in one slot)
+        running = replay and sp.scalar is not None and f.key == sp.scalar.running
+        setattr(a, "scalar" if running else f.slot, t.data_ptr())
+    b_inst = b if b_inst is None else b_inst
+    if b % b_inst:
+        raise ValueError(f"{b} trajectories over {b_inst} instances")
+    return b_inst
+
+
+def env_step(env_name: str, state, action: Tensor | None, err: Tensor | None = None) -> None:
+    """The environment's in-place step entry (``tsp_step``, ``cvrp_step``, ...) on its state tensors, looked up in this
+    module when called."""
+    entry, keys = spec(env_name).step
+    globals()[entry](action, *(state[k] for k in keys), err)
 
 
 def new_error_word(device) -> Tensor:
@@ -233,18 +270,17 @@ def am_decode(
 ) -> None:
     """Run ``max_steps`` fused decode steps (1 = a single step, >= horizon = whole rollout).
 
-    ``state`` holds the environment tensors (updated in place): action_mask [B,N] bool,
-    current_node, done; TSP: first_node, i; CVRP: demand, used_capacity, vehicle_capacity, visited.
+    ``state`` holds the environment tensors (updated in place): the fields of the environment's record in ``envspec.py``
+    (``policy._initial_state`` builds them).
     ``top_k`` / ``top_p``: the reference's top-k / nucleus filter (utils/decoding.py:109-188; see ``decoding_filter``).
     ``kept_bits`` [B, out_stride, W] int32 (W = 4 * ceil(N / 128), the layout of ``env_replay``'s mask bits): per step taken,
     bit j of the row = node j kept (feasible and not filtered); the columns of steps not taken are left as they are.
     """
-    env_name = cache.env_name
+    sp = spec(cache.env_name)
     a = _lib.AmDecodeArgs()
-    mask = _u8(state["action_mask"], "action_mask")
-    b, n = mask.shape
+    b, n = state["action_mask"].shape
     assert n == cache.num_nodes, (n, cache.num_nodes)
-    a.env = ENV_IDS[env_name]
+    a.env = sp.env_id
     a.B, a.B_inst, a.N = b, cache.num_instances, n
     a.mode = MODE_IDS[mode]
     a.max_steps = int(max_steps)
@@ -268,55 +304,16 @@ def am_decode(
     else:
         a.ctx_cur = _ptr(_ctx_table(a, cache.ctx_cur, kvl.dtype, "ctx_cur"))
     a.q_bias = _ptr(None if cache.q_bias is None else _dev(cache.q_bias, torch.float32, "q_bias"))
-    a.action_mask = _ptr(mask)
-    a.current_node = _ptr(_dev(state["current_node"], torch.int64, "current_node"))
-    a.done = _ptr(_u8(state["done"], "done"))
-    if env_name == "tsp":
-        if not cache.unfold:
+    if not cache.unfold:  # what the folded context needs besides its tables, by the context's layout
+        if sp.ctx_first:
             a.ctx_first = _ptr(_ctx_table(a, cache.ctx_first, kvl.dtype, "ctx_first"))
             a.q_step0 = _ptr(_dev(cache.q_step0, torch.float32, "q_step0"))
-        a.first_node = _ptr(_dev(state["first_node"], torch.int64, "first_node"))
-        a.step_i = _ptr(_dev(state["i"], torch.int64, "i"))
-    elif env_name == "op":
-        # orienteering: the tour length rides in the used_capacity slot, the per-node entry limits
-        # (max_length table) and the coordinates are instance data like CVRP's demand
-        a.w_cap = _ptr(_dev(cache.w_cap, torch.float32, "w_cap"))
-        assert state["locs"].shape[0] == cache.num_instances and state["max_length"].shape[0] == cache.num_instances
-        a.locs = _ptr(_dev(state["locs"], torch.float32, "locs"))
-        a.max_length = _ptr(_dev(state["max_length"], torch.float32, "max_length"))
-        a.used_capacity = _ptr(_dev(state["tour_length"], torch.float32, "tour_length"))
-        a.step_i = _ptr(_dev(state["i"], torch.int64, "i"))
-        a.visited = _ptr(_u8(state["visited"], "visited"))
-    elif env_name == "pdp":
-        # pickup and delivery: `available` rides in the visited slot; no context scalar
-        a.visited = _ptr(_u8(state["available"], "available"))
-        a.to_deliver = _ptr(_u8(state["to_deliver"], "to_deliver"))
-        a.step_i = _ptr(_dev(state["i"], torch.int64, "i"))
-    elif env_name == "pctsp":
-        # prize-collecting TSP: the real prize per node (depot column 0) rides in the demand slot, the
-        # prize collected so far in used_capacity, prize_required in vehicle_capacity
-        a.w_cap = _ptr(_dev(cache.w_cap, torch.float32, "w_cap"))
-        assert state["real_prize"].shape == (cache.num_instances, n)
-        a.demand = _ptr(_dev(state["real_prize"], torch.float32, "real_prize"))
-        a.used_capacity = _ptr(_dev(state["cur_total_prize"], torch.float32, "cur_total_prize"))
-        a.vehicle_capacity = _ptr(_dev(state["prize_required"], torch.float32, "prize_required"))
-        a.step_i = _ptr(_dev(state["i"], torch.int64, "i"))
-        a.visited = _ptr(_u8(state["visited"], "visited"))
-    else:
-        if env_name == "cvrptw":  # CVRP + clock: coordinates, (start, end) windows, service times as fp32 instance data
-            a.w_time = _ptr(_dev(cache.w_time, torch.float32, "w_time"))
-            a.locs = _ptr(_dev(state["locs"], torch.float32, "locs"))
-            a.time_windows = _ptr(_dev(state["time_windows"], torch.float32, "time_windows"))
-            a.durations = _ptr(_dev(state["durations"], torch.float32, "durations"))
-            a.current_time = _ptr(_dev(state["current_time"], torch.float32, "current_time"))
-            assert state["time_windows"].shape == (cache.num_instances, n, 2)
-        if not cache.unfold:
+        if sp.scalar is not None:
             a.w_cap = _ptr(_dev(cache.w_cap, torch.float32, "w_cap"))
-        a.demand = _ptr(_dev(state["demand"], torch.float32, "demand"))
-        assert state["demand"].shape[0] in (cache.num_instances,), "demand rows must match cache instances"
-        a.used_capacity = _ptr(_dev(state["used_capacity"], torch.float32, "used_capacity"))
-        a.vehicle_capacity = _ptr(_dev(state["vehicle_capacity"], torch.float32, "vehicle_capacity"))
-        a.visited = _ptr(_u8(state["visited"], "visited"))
+            if sp.scalar.clock:
+                a.w_time = _ptr(_dev(cache.w_time, torch.float32, "w_time"))
+    b_inst = bind_env_state(a, sp, state, b, n)
+    assert b_inst == cache.num_instances or not sp.keys("inst"), "instance data rows must match cache instances"
     if exp_noise is not None:
         _dev(exp_noise, torch.float32, "exp_noise")
         assert exp_noise.numel() >= max_steps * b * n, "exp_noise must hold [max_steps,B,N] draws"
@@ -442,85 +439,70 @@ def env_replay(env_name: str, state: dict, actions: Tensor, rem_base: Tensor | N
     environment, ``first`` / ``use_placeholder`` (TSP), ``rem`` (the context scalar: ``rem_base`` minus the running
     capacity / length / prize), ``now`` (CVRPTW), ``mask_bits`` [B,T,W] int32 on request. The `evaluate` decoding's state
     sequence (decoding.py:448-461)."""
-    mask = _u8(state["action_mask"], "action_mask")
-    b, n = mask.shape
+    sp = spec(env_name)
+    b, n = state["action_mask"].shape
     acts = _dev(actions, torch.int64, "actions")
     if acts.dim() != 2 or acts.shape[0] != b:
         raise ValueError(f"actions must be [B = {b}, T], got {tuple(acts.shape)}")
     t_len = acts.shape[1]
     dev = acts.device
     a = _lib.EnvReplayArgs()
-    a.env, a.B, a.N, a.T = ENV_IDS[env_name], b, n, t_len
-    out = {"masks": torch.empty((b, t_len, n), dtype=torch.bool, device=dev),
-           "prev": torch.empty((b, t_len), dtype=torch.int64, device=dev)}
-    a.actions, a.action_mask = acts.data_ptr(), mask.data_ptr()
-    a.current_node = _dev(state["current_node"], torch.int64, "current_node").data_ptr()
-    a.done = _u8(state["done"], "done").data_ptr()
-    a.masks, a.prev = out["masks"].data_ptr(), out["prev"].data_ptr()
-    a.err = _ptr(err)
+    a.env, a.B, a.N, a.T = sp.env_id, b, n, t_len
+    out = _replay_tables(sp, b, t_len, n, dev)
     if mask_bits:  # the same masks as bits, rows padded to whole 128-key chunks (train_ops.glimpse_attention's mask)
-        words = 4 * ((n + 127) // 128)
-        out["mask_bits"] = torch.empty((b, t_len, words), dtype=torch.int32, device=dev)
-        a.mask_bits, a.mask_words = out["mask_bits"].data_ptr(), words
-    _check_rows(b, current_node=state["current_node"], done=state["done"])
-    b_inst = b
-
-    def f32(key, rows=None):
-        t = _dev(state[key], torch.float32, key)
-        if rows is not None and t.shape[0] != rows:
-            raise ValueError(f"{key} has {t.shape[0]} rows, expected {rows}")
-        return t
-
-    if env_name == "tsp":
-        out["first"] = torch.empty((b, t_len), dtype=torch.int64, device=dev)
-        out["use_placeholder"] = torch.empty((b, t_len), dtype=torch.bool, device=dev)
-        _check_rows(b, first_node=state["first_node"], i=state["i"])
-        a.first_node = _dev(state["first_node"], torch.int64, "first_node").data_ptr()
-        a.step_i = _dev(state["i"], torch.int64, "i").data_ptr()
-        a.first, a.use_placeholder = out["first"].data_ptr(), out["use_placeholder"].data_ptr()
-    elif env_name == "pdp":
-        _check_rows(b, available=state["available"], to_deliver=state["to_deliver"], i=state["i"])
-        a.visited = _u8(state["available"], "available").data_ptr()
-        a.to_deliver = _u8(state["to_deliver"], "to_deliver").data_ptr()
-        a.step_i = _dev(state["i"], torch.int64, "i").data_ptr()
-    else:
-        scalar_key = {"cvrp": "used_capacity", "cvrptw": "used_capacity", "op": "tour_length", "pctsp": "cur_total_prize"}[env_name]
+        a.mask_words = 4 * ((n + 127) // 128)
+        out["mask_bits"] = torch.empty((b, t_len, a.mask_words), dtype=torch.int32, device=dev)
+    if sp.scalar is not None:
         if rem_base is None:
             raise ValueError(f"{env_name}: rem_base (the context scalar's minuend, one per trajectory) is required")
         base = _dev(rem_base, torch.float32, "rem_base")
-        _check_rows(b, visited=state["visited"], rem_base=base, **{scalar_key: state[scalar_key]})
-        out["rem"] = torch.empty((b, t_len), dtype=torch.float32, device=dev)
-        a.visited = _u8(state["visited"], "visited").data_ptr()
-        a.scalar, a.rem_base, a.rem = f32(scalar_key).data_ptr(), base.data_ptr(), out["rem"].data_ptr()
-        if env_name in ("cvrp", "cvrptw"):
-            dem = f32("demand")
-            b_inst = dem.shape[0]
-            if dem.shape[1] != n - 1:
-                raise ValueError(f"demand must be [B_inst, {n - 1}], got {tuple(dem.shape)}")
-            a.demand, a.vehicle_capacity = dem.data_ptr(), f32("vehicle_capacity", b).data_ptr()
-            if env_name == "cvrptw":
-                out["now"] = torch.empty((b, t_len), dtype=torch.float32, device=dev)
-                a.locs = f32("locs", b_inst).data_ptr()
-                a.time_windows, a.durations = f32("time_windows", b_inst).data_ptr(), f32("durations", b_inst).data_ptr()
-                a.current_time, a.now = f32("current_time", b).data_ptr(), out["now"].data_ptr()
-        elif env_name == "pctsp":
-            rp = f32("real_prize")
-            b_inst = rp.shape[0]
-            if rp.shape[1] != n:
-                raise ValueError(f"real_prize must be [B_inst, {n}], got {tuple(rp.shape)}")
-            a.demand, a.step_i = rp.data_ptr(), _dev(state["i"], torch.int64, "i").data_ptr()
-        else:  # op
-            lc = f32("locs")
-            b_inst = lc.shape[0]
-            a.locs, a.max_length = lc.data_ptr(), f32("max_length", b_inst).data_ptr()
-            a.step_i = _dev(state["i"], torch.int64, "i").data_ptr()
-    if b % b_inst:
-        raise ValueError(f"{b} trajectories over {b_inst} instances")
-    a.B_inst = b_inst
-    import ctypes
-
-    st = _lib.lib().rl4co_env_replay(ctypes.byref(a), _stream())
+        _check_rows(b, rem_base=base)
+        a.rem_base = base.data_ptr()
+    a.B_inst = bind_env_state(a, sp, state, b, n)
+    a.actions, a.err = acts.data_ptr(), _ptr(err)
+    for k, t in out.items():  # (the output slots carry the names of the tables)
+        setattr(a, k, t.data_ptr())
+    st = _lib.lib().rl4co_env_replay(C.byref(a), _stream())
     _lib.check(st, "rl4co_env_replay")
+    return out
+
+
+def _replay_tables(sp: EnvSpec, b: int, t_len: int, n: int, dev) -> dict:
+    """The tables a replay fills, by the environment's context layout (envspec.py)."""
+    def new(dtype, *tail):
+        return torch.empty((b, t_len, *tail), dtype=dtype, device=dev)
+
+    out = {"masks": new(torch.bool, n), "prev": new(torch.int64)}
+    if sp.ctx_first:
+        out["first"], out["use_placeholder"] = new(torch.int64), new(torch.bool)
+    if sp.scalar is not None:
+        out["rem"] = new(torch.float32)
+        if sp.scalar.clock:
+            out["now"] = new(torch.float32)
+    return out
+
+
+def env_replay_stepwise(env_name: str, state: dict, actions: Tensor, rem_base: Tensor | None, err: Tensor | None = None,
+                        mask_bits: bool = False) -> dict:
+    """``env_replay``'s tables from ``T`` calls of the step entry, tabulated in between (what the kernel loops on the
+    device): the tests' cross-check of the one-launch form, and its stand-in where a test plays the device."""
+    assert not mask_bits, "the mask bits come from the one-launch form only"
+    sp = spec(env_name)
+    b, t_len = actions.shape
+    out = _replay_tables(sp, b, t_len, state["action_mask"].shape[1], actions.device)
+    err = new_error_word(actions.device) if err is None else err
+    for t in range(t_len):
+        out["masks"][:, t] = state["action_mask"]
+        out["prev"][:, t] = state["current_node"]
+        if sp.ctx_first:
+            out["first"][:, t] = state["first_node"]
+            out["use_placeholder"][:, t] = state["i"] < 1
+        if sp.scalar is not None:
+            rem = rem_base - state[sp.scalar.running]
+            out["rem"][:, t] = torch.clamp(rem, min=0) if sp.scalar.clamp else rem
+            if sp.scalar.clock:
+                out["now"][:, t] = state[sp.scalar.clock]
+        env_step(env_name, state, actions[:, t].contiguous(), err)
     return out
 
 

@@ -32,6 +32,7 @@ from torch import Tensor
 from . import kernels as K
 from .cache import FoldedCache, build_folded_cache, canonical_env
 from .envs import RL4COEnvBase, get_env
+from .envspec import customer_features, rem_base, spec
 from .tensordict import TensorDict
 
 # ------------------------------------------------------------------------------------------------
@@ -555,23 +556,14 @@ class AttentionModelPolicy(nn.Module):
         bf = self._encoder_regime()  # the 16-bit autocast type this rollout computes in (bfloat16 or float16)
         assert bf in (torch.bfloat16, torch.float16)
         embed = lambda f, lin: T.init_embed(f, lin, dtype=bf)  # noqa: E731
-        if self.env_name == "pdp":
+        sp, locs = spec(self.env_name), td["locs"]
+        if hasattr(init, "features"):  # PDP: depot | pickups | deliveries, an embedding each
             x = torch.cat([embed(f.contiguous(), lin) for f, lin in init.features(td)], -2)
-        elif self.env_name == "cvrptw":
-            locs = td["locs"]
-            feats = torch.cat((locs[:, 1:, :], td["demand"][..., None], td["time_windows"][..., 1:, :].float(),
-                               td["durations"][..., 1:, None].float()), -1)
-            x = torch.cat((embed(locs[:, :1, :], init.init_embed_depot), embed(feats, init.init_embed)), -2)
-        elif self.env_name in ("cvrp", "op", "pctsp"):
-            locs = td["locs"]
-            third = {"cvrp": "demand", "op": "prize", "pctsp": "expected_prize"}[self.env_name]
-            third = td[third][..., 1:] if self.env_name == "op" else td[third]
-            feats = torch.cat((locs[:, 1:, :], third[..., None]), -1)
-            if self.env_name == "pctsp":
-                feats = torch.cat((feats, td["penalty"][..., 1:, None]), -1)
+        elif sp.depot_embed:
+            feats = torch.cat((locs[:, 1:, :], *customer_features(sp, td)), -1)
             x = torch.cat((embed(locs[:, :1, :], init.init_embed_depot), embed(feats, init.init_embed)), -2)
         else:
-            x = embed(td["locs"], init.init_embed)
+            x = embed(locs, init.init_embed)
         init_h = x
         b, n, d = x.shape
         for layer in enc.net.layers:
@@ -629,58 +621,21 @@ class AttentionModelPolicy(nn.Module):
 
     @staticmethod
     def _max_horizon(env_name: str, n: int) -> int:
-        # TSP: exactly N steps. CVRP: every customer + at most one depot visit per customer + 1.
-        # OP: every customer once, the closing depot visit, and a depot pick at step 0 costs one more.
-        # PCTSP: every customer once and the closing depot visit (the depot is masked at step 0).
-        # PDP: every node once (the depot too under force_start_at_depot).
-        return n if env_name in ("tsp", "pctsp", "pdp") else (n + 2 if env_name == "op" else 2 * n)
+        return spec(env_name).horizon(n)  # (the longest rollout per environment: envspec.py)
 
     def _initial_state(self, td, num_starts: int):
-        """State tensors the kernel updates in place; with multistart the rows are expanded
-        s-major (batchify, ops.py:10-30) while instance-level data (cache, demand) stays [B,...]."""
+        """State tensors the kernel updates in place (the fields of envspec.py); with multistart the per-trajectory rows are
+        expanded s-major (batchify, ops.py:10-30) and fresh, while instance-level data (cache, demand) stays [B,...] — the
+        caller's tensor where it is contiguous fp32."""
         s = max(num_starts, 1)
-
-        def rep(x: Tensor) -> Tensor:
-            x = x.reshape(x.shape[0], -1) if x.dim() > 1 else x
-            out = x.unsqueeze(0).expand(s, *x.shape).reshape(s * x.shape[0], *x.shape[1:]).contiguous()
-            return out
-
-        st = {
-            "action_mask": rep(td["action_mask"]),
-            "current_node": rep(td["current_node"].reshape(-1)),
-            "done": rep(td["done"].reshape(-1)),
-        }
-        if self.env_name == "tsp":
-            st["first_node"] = rep(td["first_node"].reshape(-1))
-            st["i"] = rep(td["i"].reshape(-1))
-        elif self.env_name == "pdp":
-            st["available"] = rep(td["available"])
-            st["to_deliver"] = rep(td["to_deliver"])
-            st["i"] = rep(td["i"].reshape(-1))
-        elif self.env_name == "pctsp":
-            st["real_prize"] = td["real_prize"].contiguous()  # instance data [B_inst, N], depot column 0
-            st["cur_total_prize"] = rep(td["cur_total_prize"].reshape(-1))
-            st["prize_required"] = rep(td["prize_required"].reshape(-1))
-            st["i"] = rep(td["i"].reshape(-1))
-            st["visited"] = rep(td["visited"])
-        elif self.env_name == "op":
-            st["locs"] = td["locs"].contiguous()              # instance data, like CVRP's demand
-            st["max_length"] = td["max_length"].contiguous()  # [B_inst, N] entry limits
-            st["tour_length"] = rep(td["tour_length"].reshape(-1))
-            st["i"] = rep(td["i"].reshape(-1))
-            st["visited"] = rep(td["visited"])
-        else:
-            st["demand"] = td["demand"].contiguous()
-            st["used_capacity"] = rep(td["used_capacity"].reshape(-1))
-            st["vehicle_capacity"] = rep(td["vehicle_capacity"].reshape(-1))
-            st["visited"] = rep(td["visited"])
-            if self.env_name == "cvrptw":  # instance data as fp32 (the reference keeps integer-valued windows)
-                st["locs"] = td["locs"].contiguous()
-                st["time_windows"] = td["time_windows"].float().contiguous()
-                st["durations"] = td["durations"].float().contiguous()
-                st["current_time"] = rep(td["current_time"].reshape(-1))
-        if s == 1:
-            st = {k: (v.clone() if k not in ("demand", "locs", "max_length", "real_prize", "time_windows", "durations") else v) for k, v in st.items()}
+        st = {}
+        for f in spec(self.env_name).fields:
+            x = td[f.key]
+            if f.kind == "inst":
+                st[f.key] = x.float().contiguous()
+                continue
+            x = x if f.shape == "BN" else x.reshape(-1)
+            st[f.key] = x.clone(memory_format=torch.contiguous_format) if s == 1 else x.unsqueeze(0).expand(s, *x.shape).reshape(s * x.shape[0], *x.shape[1:]).contiguous()
         return st
 
     # -- forward (constructive/base.py:154-263) ---------------------------------------------------
@@ -1050,14 +1005,7 @@ class AttentionModelPolicy(nn.Module):
                 self._bwd_err = torch.zeros(1, dtype=torch.int32, device=device)
             meta = dict(t0=t0, mask_inner=self.decoder.mask_inner, mask_logits=mask_logits, err_sink=self._bwd_err,
                         tanh_clipping=tanh_clipping, temperature=temperature, teacher_variant=self.teacher_variant)
-            if self.env_name in ("cvrp", "cvrptw"):
-                meta.update(demand=td["demand"], vehicle_capacity=td["vehicle_capacity"])
-                if self.env_name == "cvrptw":
-                    meta.update(locs=td["locs"], time_windows=td["time_windows"], durations=td["durations"])
-            elif self.env_name == "op":
-                meta.update(locs=td["locs"], max_length=td["max_length"])
-            elif self.env_name == "pctsp":
-                meta.update(real_prize=td["real_prize"], prize_required=td["prize_required"])
+            meta.update((k, td[k]) for k in spec(self.env_name).teacher_keys)  # the instance data the backward replays on
             step_logps = teacher.teacher_forced_logps(self.env_name, cache_g, cache, out_actions, logps, meta)
         elif grad_path:
             kept = r.kept_bits[:, :t_used].contiguous() if r.kept_bits is not None else None
@@ -1153,56 +1101,20 @@ class AttentionModelPolicy(nn.Module):
 
     # -- pieces -------------------------------------------------------------------------------------
     def _env_step_state(self, state: dict, action: Tensor, err: Tensor) -> None:
-        if self.env_name == "tsp":
-            K.tsp_step(action, state["action_mask"], state["first_node"], state["current_node"],
-                       state["i"], state["done"], err)
-        elif self.env_name == "op":
-            K.op_step(action, state["locs"], state["max_length"], state["tour_length"], state["visited"],
-                      state["current_node"], state["i"], state["action_mask"], state["done"], err)
-        elif self.env_name == "cvrptw":
-            K.cvrptw_step(action, state["demand"], state["locs"], state["time_windows"], state["durations"],
-                          state["used_capacity"], state["vehicle_capacity"], state["current_time"], state["visited"],
-                          state["current_node"], state["action_mask"], state["done"], err)
-        elif self.env_name == "pdp":
-            K.pdp_step(action, state["available"], state["to_deliver"], state["current_node"], state["i"],
-                       state["action_mask"], state["done"], err)
-        elif self.env_name == "pctsp":
-            K.pctsp_step(action, state["real_prize"], state["cur_total_prize"], state["visited"], state["current_node"],
-                         state["i"], state["action_mask"], state["done"], err)
-        else:
-            K.cvrp_step(action, state["demand"], state["used_capacity"], state["vehicle_capacity"],
-                        state["visited"], state["current_node"], state["action_mask"], state["done"], err)
+        K.env_step(self.env_name, state, action, err)
 
     def _final_td(self, td, state: dict, n_rep: int) -> TensorDict:
         s = max(n_rep, 1)
         b_inst = td["action_mask"].shape[0]
+        sp = spec(self.env_name)
 
         def rep(x: Tensor) -> Tensor:
             if s == 1:
                 return x
             return x.unsqueeze(0).expand(s, *x.shape).reshape(s * x.shape[0], *x.shape[1:])
 
-        out = {"locs": rep(td["locs"]), "action_mask": state["action_mask"], "done": state["done"]}
-        if self.env_name == "tsp":
-            out.update(first_node=state["first_node"], current_node=state["current_node"],
-                       i=state["i"].view(-1, 1))
-        elif self.env_name == "op":
-            out.update(prize=rep(td["prize"]), max_length=rep(td["max_length"]), current_node=state["current_node"].view(-1, 1),
-                       tour_length=state["tour_length"], visited=state["visited"], i=state["i"])
-        elif self.env_name == "pdp":
-            out.update(available=state["available"], to_deliver=state["to_deliver"],
-                       current_node=state["current_node"].view(-1, 1), i=state["i"].view(-1, 1))
-        elif self.env_name == "pctsp":
-            out.update(real_prize=rep(td["real_prize"]), expected_prize=rep(td["expected_prize"]), penalty=rep(td["penalty"]),
-                       prize_required=state["prize_required"], cur_total_prize=state["cur_total_prize"],
-                       current_node=state["current_node"], visited=state["visited"], i=state["i"])
-        else:
-            out.update(demand=rep(td["demand"]), current_node=state["current_node"].view(-1, 1),
-                       used_capacity=state["used_capacity"].view(-1, 1),
-                       vehicle_capacity=state["vehicle_capacity"].view(-1, 1), visited=state["visited"])
-            if self.env_name == "cvrptw":
-                out.update(time_windows=rep(td["time_windows"]), durations=rep(td["durations"]),
-                           current_time=state["current_time"].view(-1, 1))
+        out = {k: rep(td[k]) for k in sp.passthrough}
+        out.update((f.key, state[f.key].view(-1, 1) if f.shape == "B1" else state[f.key]) for f in sp.fields if f.kind == "traj")
         return TensorDict(out, batch_size=[s * b_inst])
 
     # -- teacher-forced, differentiable re-evaluation (row N1 of SURVEY.md §8f) -------------------
@@ -1230,7 +1142,8 @@ class AttentionModelPolicy(nn.Module):
         masks, ctx_nodes, extras, mask_bits = self._replay(td, actions, n_rep, mask_bits=glimpse_kernel)
         h = hidden if s == 1 else hidden.unsqueeze(0).expand(s, b_inst, n, d).reshape(b, n, d)
         w_ctx = dec.context_embedding.project_context.weight
-        if self.env_name == "tsp":
+        sp = spec(self.env_name)
+        if sp.ctx_first:
             first, prev = ctx_nodes  # [B,T] each (t = 0 is the placeholder)
             idx = torch.stack([first, prev], -1).view(b, t_len * 2)
             ctx = h.gather(1, idx[..., None].expand(b, t_len * 2, d)).view(b, t_len, 2 * d)
@@ -1239,13 +1152,9 @@ class AttentionModelPolicy(nn.Module):
             ctx = torch.where(use_ph[..., None], placeholder, ctx)
         else:
             (prev,) = ctx_nodes
-            cur = h.gather(1, prev[..., None].expand(b, t_len, d))
-            if self.env_name == "pdp":
-                ctx = cur
-            elif self.env_name == "cvrptw":
-                ctx = torch.cat([cur, extras], -1)  # + remaining capacity, current time
-            else:
-                ctx = torch.cat([cur, extras[..., None]], -1)  # + remaining capacity
+            ctx = h.gather(1, prev[..., None].expand(b, t_len, d))
+            if sp.scalar is not None:  # + remaining capacity / length / prize (, current time)
+                ctx = torch.cat([ctx, extras if sp.scalar.clock else extras[..., None]], -1)
         q = F.linear(ctx, w_ctx)
         if dec.use_graph_context:
             g = dec.project_fixed_context(hidden.mean(1))
@@ -1302,64 +1211,23 @@ class AttentionModelPolicy(nn.Module):
 
     @torch.no_grad()
     def _replay(self, td, actions: Tensor, n_rep: int, mask_bits: bool = False):
-        """Per step of the given trajectories: the mask the decoder saw, the context node(s) and the context scalar(s) —
-        ONE launch (``rl4co_env_replay``: the env-step device code looped over T on the device; r06 — the T x ~2 launches
-        of ``_replay_stepwise`` were 20 of the 46 ms of a CVRP-500 x 64 REINFORCE step)."""
-        state = self._initial_state(td, n_rep)
-        b = actions.shape[0]
-        rem_base = None
-        if self.env_name == "op":
-            ml0 = state["max_length"][:, 0]
-            rem_base = (ml0 if ml0.shape[0] == b else ml0.repeat(b // ml0.shape[0])).contiguous()
-        elif self.env_name == "pctsp":
-            rem_base = state["prize_required"]
-        elif self.env_name in ("cvrp", "cvrptw"):
-            rem_base = state["vehicle_capacity"]
-        err = K.new_error_word(actions.device)
-        r = K.env_replay(self.env_name, state, actions.contiguous(), rem_base, err, mask_bits=mask_bits)
-        bits = r.get("mask_bits")
-        if self.env_name == "tsp":
-            return r["masks"], (r["first"], r["prev"]), r["use_placeholder"], bits
-        if self.env_name == "pdp":
-            return r["masks"], (r["prev"],), None, bits
-        return (r["masks"], (r["prev"],), (r["rem"] if self.env_name != "cvrptw" else torch.stack((r["rem"], r["now"]), -1)),
-                bits)
+        """Per step of the given trajectories: the mask the decoder saw, the context node(s), the context scalar(s) and (on
+        request) the masks as bits — ONE launch (``rl4co_env_replay``: the env-step device code looped over T on the device;
+        r06 — the T x ~2 launches of ``_replay_stepwise`` were 20 of the 46 ms of a CVRP-500 x 64 REINFORCE step)."""
+        return self._replay_by(K.env_replay, td, actions, n_rep, mask_bits)
 
     @torch.no_grad()
     def _replay_stepwise(self, td, actions: Tensor, n_rep: int):
         """``_replay`` as T calls of the env-step kernels (what ``rl4co_env_replay`` loops on the device): the tests'
         cross-check of the one-launch form."""
+        return self._replay_by(K.env_replay_stepwise, td, actions, n_rep, False)
+
+    def _replay_by(self, replay, td, actions: Tensor, n_rep: int, mask_bits: bool):
+        sp = spec(self.env_name)
         state = self._initial_state(td, n_rep)
-        b, t_len = actions.shape
-        n = state["action_mask"].shape[1]
-        device = actions.device
-        masks = torch.empty((b, t_len, n), dtype=torch.bool, device=device)
-        prev = torch.empty((b, t_len), dtype=torch.int64, device=device)
-        err = K.new_error_word(device)
-        if self.env_name == "tsp":
-            first = torch.empty((b, t_len), dtype=torch.int64, device=device)
-            use_ph = torch.empty((b, t_len), dtype=torch.bool, device=device)
-        else:
-            rem = torch.empty((b, t_len), dtype=torch.float32, device=device)
-            now = torch.empty((b, t_len), dtype=torch.float32, device=device) if self.env_name == "cvrptw" else None
-        for t in range(t_len):
-            masks[:, t] = state["action_mask"]
-            prev[:, t] = state["current_node"]
-            if self.env_name == "tsp":
-                first[:, t] = state["first_node"]
-                use_ph[:, t] = state["i"] < 1
-            elif self.env_name == "op":
-                ml0 = state["max_length"][:, 0]
-                rem[:, t] = (ml0 if ml0.shape[0] == b else ml0.repeat(b // ml0.shape[0])) - state["tour_length"]
-            elif self.env_name == "pctsp":
-                rem[:, t] = torch.clamp(state["prize_required"] - state["cur_total_prize"], min=0)
-            elif self.env_name == "pdp":
-                pass  # no context scalar
-            else:
-                rem[:, t] = state["vehicle_capacity"] - state["used_capacity"]
-                if now is not None:
-                    now[:, t] = state["current_time"]
-            self._env_step_state(state, actions[:, t].contiguous(), err)
-        if self.env_name == "tsp":
-            return masks, (first, prev), use_ph
-        return masks, (prev,), (rem if self.env_name != "cvrptw" else torch.stack((rem, now), -1))
+        r = replay(self.env_name, state, actions.contiguous(), rem_base(sp, state, actions.shape[0]),
+                   K.new_error_word(actions.device), mask_bits=mask_bits)
+        if sp.ctx_first:
+            return r["masks"], (r["first"], r["prev"]), r["use_placeholder"], r.get("mask_bits")
+        extras = None if sp.scalar is None else (torch.stack((r["rem"], r["now"]), -1) if sp.scalar.clock else r["rem"])
+        return r["masks"], (r["prev"],), extras, r.get("mask_bits")

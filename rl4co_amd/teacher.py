@@ -16,6 +16,7 @@ from torch import Tensor
 
 from . import _lib
 from .cache import EMBED_DIM, FoldedCache, fold_weights
+from .envspec import spec
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -82,7 +83,8 @@ def run_backward(cache: FoldedCache, actions: Tensor, grad_logp: Tensor, meta: d
     logp = torch.zeros((b, t), **f32) if want_logp else None
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     a = AmTeacherArgs()
-    a.env = {"tsp": _lib.ENV_TSP, "cvrp": _lib.ENV_CVRP, "op": _lib.ENV_OP, "pctsp": _lib.ENV_PCTSP, "pdp": _lib.ENV_PDP, "cvrptw": _lib.ENV_CVRPTW}[cache.env_name]
+    sp = spec(cache.env_name)
+    a.env = sp.env_id
     a.B, a.B_inst, a.N, a.T, a.t0 = b, b_inst, n, t, int(meta["t0"])
     a.mask_inner, a.mask_logits = int(meta["mask_inner"]), int(meta["mask_logits"])
     a.tanh_clipping, a.temperature = float(meta["tanh_clipping"]), float(meta["temperature"])
@@ -102,22 +104,17 @@ def run_backward(cache: FoldedCache, actions: Tensor, grad_logp: Tensor, meta: d
     acts = actions.contiguous()
     g = grad_logp.contiguous().float()
     a.actions, a.grad_logp = acts.data_ptr(), g.data_ptr()
-    if cache.env_name in ("cvrp", "cvrptw"):
-        demand = meta["demand"].contiguous()
-        vcap = meta["vehicle_capacity"].reshape(-1).contiguous()
-        a.demand, a.vehicle_capacity = demand.data_ptr(), vcap.data_ptr()
-        if cache.env_name == "cvrptw":
-            locs, tw = meta["locs"].float().contiguous(), meta["time_windows"].float().contiguous()
-            dur = meta["durations"].float().contiguous()
-            a.locs, a.time_windows, a.durations = locs.data_ptr(), tw.data_ptr(), dur.data_ptr()
-            a.w_time, a.d_w_time = ptr(cache.w_time), d_time.data_ptr()
-    elif cache.env_name == "pctsp":
-        demand = meta["real_prize"].float().contiguous()  # [B_inst, N], depot column 0
-        vcap = meta["prize_required"].float().reshape(-1).contiguous()
-        a.demand, a.vehicle_capacity = demand.data_ptr(), vcap.data_ptr()
-    elif cache.env_name == "op":
-        locs, maxlen = meta["locs"].float().contiguous(), meta["max_length"].float().contiguous()
-        a.locs, a.max_length = locs.data_ptr(), maxlen.data_ptr()
+    # the instance's data in the slots the rollout binds it to (envspec.py); a per-trajectory scalar base (vehicle
+    # capacity, prize required) is the instance's own value here, one per instance
+    inst = {}
+    for f in sp.fields:
+        if f.key in sp.teacher_keys:
+            t = meta[f.key].float()
+            inst[f.slot] = (t.reshape(-1) if f.kind == "traj" else t).contiguous()
+    for slot, t in inst.items():
+        setattr(a, slot, t.data_ptr())
+    if d_time is not None:
+        a.w_time, a.d_w_time = ptr(cache.w_time), d_time.data_ptr()
     a.d_kvl, a.d_ctx_cur, a.d_ctx_first, a.d_q_bias = ptr(d_kvl), ptr(d_ctx_cur), ptr(d_ctx_first), ptr(d_q_bias)
     if d_planes is not None:
         # [3, ...]: the three plane gradients; [5, ...] (TSP) / [4, ...] (depot environments): the context-table gradients as

@@ -136,55 +136,6 @@ def _am_decode(cache, state, **kw):
     c_oracle.am_decode(cache, state, row_groups=groups, **kw)
 
 
-def _env_replay(env_name, state, actions, rem_base, err=None, mask_bits=False):
-    """kernels.env_replay on CPU tensors: the tabulation between T calls of the (patched) step functions."""
-    from rl4co_amd import kernels as K
-
-    b, t_len = actions.shape
-    n = state["action_mask"].shape[1]
-    out = {"masks": torch.empty((b, t_len, n), dtype=torch.bool), "prev": torch.empty((b, t_len), dtype=torch.int64)}
-    if env_name == "tsp":
-        out["first"] = torch.empty((b, t_len), dtype=torch.int64)
-        out["use_placeholder"] = torch.empty((b, t_len), dtype=torch.bool)
-    elif env_name != "pdp":
-        out["rem"] = torch.empty((b, t_len), dtype=torch.float32)
-        if env_name == "cvrptw":
-            out["now"] = torch.empty((b, t_len), dtype=torch.float32)
-    scalar = {"cvrp": "used_capacity", "cvrptw": "used_capacity", "op": "tour_length", "pctsp": "cur_total_prize"}.get(env_name)
-    e = err if err is not None else torch.zeros(1, dtype=torch.int32)
-    for t in range(t_len):
-        out["masks"][:, t] = state["action_mask"]
-        out["prev"][:, t] = state["current_node"]
-        if env_name == "tsp":
-            out["first"][:, t] = state["first_node"]
-            out["use_placeholder"][:, t] = state["i"] < 1
-        elif env_name != "pdp":
-            r = rem_base - state[scalar]
-            out["rem"][:, t] = torch.clamp(r, min=0) if env_name == "pctsp" else r
-            if env_name == "cvrptw":
-                out["now"][:, t] = state["current_time"]
-        a = actions[:, t].contiguous()
-        if env_name == "tsp":
-            K.tsp_step(a, state["action_mask"], state["first_node"], state["current_node"], state["i"], state["done"], e)
-        elif env_name == "op":
-            K.op_step(a, state["locs"], state["max_length"], state["tour_length"], state["visited"], state["current_node"],
-                      state["i"], state["action_mask"], state["done"], e)
-        elif env_name == "cvrptw":
-            K.cvrptw_step(a, state["demand"], state["locs"], state["time_windows"], state["durations"], state["used_capacity"],
-                          state["vehicle_capacity"], state["current_time"], state["visited"], state["current_node"],
-                          state["action_mask"], state["done"], e)
-        elif env_name == "pdp":
-            K.pdp_step(a, state["available"], state["to_deliver"], state["current_node"], state["i"], state["action_mask"],
-                       state["done"], e)
-        elif env_name == "pctsp":
-            K.pctsp_step(a, state["real_prize"], state["cur_total_prize"], state["visited"], state["current_node"], state["i"],
-                         state["action_mask"], state["done"], e)
-        else:
-            K.cvrp_step(a, state["demand"], state["used_capacity"], state["vehicle_capacity"], state["visited"],
-                        state["current_node"], state["action_mask"], state["done"], e)
-    return out
-
-
 @pytest.fixture
 def cpu_device(monkeypatch):
     """Patch rl4co_amd.kernels so that policy/env host code runs on CPU tensors via the C oracle."""
@@ -207,7 +158,8 @@ def cpu_device(monkeypatch):
     monkeypatch.setattr(K, "pctsp_step", _pctsp_step)
     monkeypatch.setattr(K, "pctsp_check_solution", _pctsp_check)
     monkeypatch.setattr(K, "am_decode", _am_decode)
-    monkeypatch.setattr(K, "env_replay", _env_replay)
+    # (the tabulation between T calls of the — patched — step functions)
+    monkeypatch.setattr(K, "env_replay", K.env_replay_stepwise)
     monkeypatch.setattr(K, "augment_dihedral8", c_oracle.augment_dihedral8)
     monkeypatch.setattr(K, "augment_symmetric", c_oracle.augment_symmetric)
     monkeypatch.setattr(K, "pomo_best", c_oracle.pomo_best)

@@ -59,7 +59,7 @@ if rows.numel():
     hs = h64[sub]
     b, n, d = hs.shape
     with torch.no_grad():
-        masks, ctx_nodes, extras = pol._replay(env.reset(data.clone()[sub.tolist()]), ref[sub], 0)  # discrete state replay on the env kernels (fp32 state)
+        masks, ctx_nodes, extras, _ = pol._replay(env.reset(data.clone()[sub.tolist()]), ref[sub], 0)  # discrete state replay on the env kernels (fp32 state)
     t_len = ref.shape[1]
     (prev,) = ctx_nodes
     cur = hs.gather(1, prev[..., None].expand(b, t_len, d))
