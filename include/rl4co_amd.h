@@ -37,8 +37,10 @@ extern "C" {
  *   7: rl4co_am_decode_args / rl4co_am_teacher_args end in the context tables' dtype and strides (ctx_dtype ...).
  *   8: the 16 rl4co_<op>_bf16 / rl4co_<op>_f16 pairs are ONE rl4co_<op>(int dtype, ...) each.
  *  13: rl4co_am_decode_args ends in the top-k / top-p filter (top_k, top_p) and its optional kept-set output
- *      (kept_bits, kept_words); zero-initialised = no filter. */
-#define RL4CO_ABI_VERSION 13
+ *      (kept_bits, kept_words); zero-initialised = no filter.
+ *  14: rl4co_am_decode_args carries the split-delivery VRP's dynamic-embedding vectors and per-trajectory remaining
+ *      demand (dyn_vectors, demand_state, behind w_time); rl4co_sdvrp_step. */
+#define RL4CO_ABI_VERSION 14
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -72,6 +74,10 @@ extern "C" {
 #define RL4CO_ENV_PCTSP 3 /* prize-collecting TSP (same row): STREAM / LDS / WIDE decode variants */
 #define RL4CO_ENV_PDP 4 /* pickup and delivery (same row): STREAM / LDS / WIDE decode variants */
 #define RL4CO_ENV_CVRPTW 5 /* CVRP with time windows (same row): STREAM / LDS / WIDE decode variants */
+/* Split-delivery VRP (envs/routing/sdvrp/env.py): the one environment with a dynamic embedding (the remaining demand moves
+ * the keys and values every step). Decode only — STREAM / LDS / WIDE; not the multistart variant, the unfolded mode, the
+ * replay or the teacher kernels, whose six environments are the ids above. */
+#define RL4CO_ENV_SDVRP (RL4CO_ENV_CVRPTW + 1)
 
 #define RL4CO_DECODE_GREEDY 0   /* utils/decoding.py:387-397 */
 #define RL4CO_DECODE_SAMPLE 1   /* utils/decoding.py:399-413 */
@@ -165,6 +171,10 @@ int rl4co_tsp_step(const int64_t* action, uint8_t* action_mask, int64_t* first_n
  * demand [B_inst,N-1] (trajectory b reads row b % B_inst), used/cap f32 [B].
  * Passing action == NULL only recomputes the mask (a9 / a7's reset mask).
  * -------------------------------------------------------------------------- */
+/* In-place SDVRPEnv._step + get_action_mask (sdvrp/env.py:56-123); action == NULL: mask only. demand_with_depot [B,N]. */
+int rl4co_sdvrp_step(const int64_t* action, float* demand_with_depot, float* used_capacity, const float* vehicle_capacity,
+                     int64_t* current_node, uint8_t* action_mask, uint8_t* done, int B, int N, int32_t* err, void* stream);
+
 int rl4co_cvrp_step(const int64_t* action, const float* demand, float* used_capacity,
                     const float* vehicle_capacity, uint8_t* visited, int64_t* current_node,
                     uint8_t* action_mask, uint8_t* done, int B, int B_inst, int N,
@@ -380,6 +390,11 @@ typedef struct rl4co_am_decode_args {
   const float* durations;    /* [B_inst,N] service times                                    */
   float* current_time;       /* [B]                                                         */
   const float* w_time;       /* [128] = W_ctx[:, 129]                                       */
+  /* SDVRP (envs/routing/sdvrp/env.py): used_capacity, vehicle_capacity as CVRP; no visited. The dynamic embedding
+   * Linear(1 -> 3 * 128)(remaining demand) (env_embeddings/dynamic.py:60-78, zoo/am/decoder.py:142-152) is rank one per
+   * node, so it travels as three batch-shared vectors and the kernel adds d_j * (x . u) to each dot product */
+  const float* dyn_vectors;  /* [3,128] fp32 whatever the planes: (u_k, u_v, W_out^T u_l)      */
+  float* demand_state;       /* [B,N] remaining demand with the depot column, read and written  */
   /* decoding inputs */
   const float* exp_noise;   /* [max_steps,B,N] Exp(1) draws (parity mode) or NULL          */
   uint64_t philox_seed;     /* in-kernel Exp(1) noise when exp_noise == NULL               */

@@ -12,8 +12,8 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 13  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
-ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW = 0, 1, 2, 3, 4, 5
+ABI_VERSION = 14  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP = 0, 1, 2, 3, 4, 5, 6
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 VARIANT_AUTO, VARIANT_STREAM, VARIANT_LDS, VARIANT_WIDE, VARIANT_MS = 0, 1, 2, 3, 4
@@ -74,6 +74,7 @@ class AmDecodeArgs(C.Structure):
         ("demand", _vp), ("used_capacity", _vp), ("vehicle_capacity", _vp), ("visited", _vp),
         ("locs", _vp), ("max_length", _vp), ("to_deliver", _vp),
         ("time_windows", _vp), ("durations", _vp), ("current_time", _vp), ("w_time", _vp),
+        ("dyn_vectors", _vp), ("demand_state", _vp),
         ("exp_noise", _vp), ("philox_seed", C.c_uint64), ("philox_offset", C.c_uint64), ("philox_seed_dev", _vp),
         ("forced_actions", _vp),
         ("t0", _i32), ("out_stride", _i32),
@@ -122,6 +123,7 @@ SYMBOLS = {
     "rl4co_cvrp_check_solution": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_tsp_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_cvrp_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "rl4co_sdvrp_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_op_max_length": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_op_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_gather_sum_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),

@@ -47,6 +47,8 @@ class FoldedCache:
     q_step0: Tensor | None  # [128] fp32 (TSP)
     w_cap: Tensor | None  # [128] fp32 (CVRP)
     w_time: Tensor | None = None  # [128] fp32 (CVRPTW: W_ctx[:, 129], the current-time column)
+    # SDVRP: the dynamic embedding's three vectors (u_k, u_v, W_out^T u_l), fp32 whatever the planes (fold_dynamic)
+    dyn: Tensor | None = None  # [3, 128] fp32
     # "unfolded" parity mode (build_folded_cache(fold=False), TSP / CVRP): plane 2 of `kvl` is the RAW logit key and
     # the three batch-shared matrices are applied per decode step in the reference's association
     unfold: bool = False
@@ -55,7 +57,7 @@ class FoldedCache:
     w_out_t: Tensor | None = None        # [128, 128] fp32 project_out.weight^T
     w_placeholder: Tensor | None = None  # [256] fp32 (TSP)
 
-    TENSOR_FIELDS = ("kvl", "ctx_first", "ctx_cur", "q_bias", "q_step0", "w_cap", "w_time", "node_embed", "w_ctx_t",
+    TENSOR_FIELDS = ("kvl", "ctx_first", "ctx_cur", "q_bias", "q_step0", "w_cap", "w_time", "dyn", "node_embed", "w_ctx_t",
                      "w_out_t", "w_placeholder")
 
     def to(self, device) -> "FoldedCache":
@@ -90,9 +92,18 @@ def fold_weights(env_name: str, w_node: Tensor, w_out: Tensor, w_ctx: Tensor) ->
     wl_folded = w_out.t() @ wl  # logits = heads^T W_out^T (Wl h_j)
     if env_name == "tsp":
         return [wk, wv, wl_folded, w_ctx[:, :d], w_ctx[:, d : 2 * d]]
-    if env_name in ("cvrp", "op", "pctsp", "pdp", "cvrptw"):  # current-node embedding (+ one scalar: capacity / remaining length / prize)
+    if env_name in ("cvrp", "op", "pctsp", "pdp", "cvrptw", "sdvrp"):  # current-node embedding (+ one scalar: capacity / remaining length / prize)
         return [wk, wv, wl_folded, w_ctx[:, :d]]
     raise ValueError(f"fused decode supports tsp/cvrp/op, got {env_name!r}")
+
+
+def fold_dynamic(w_dyn: Tensor, w_out: Tensor) -> Tensor:
+    """SDVRP's dynamic embedding ``Linear(1 -> 3 * 128)`` (env_embeddings/dynamic.py:60-78) adds ``d_j u`` to the glimpse key,
+    the glimpse value and the logit key of node j (zoo/am/decoder.py:142-152). Rank one per node, so it folds into the three
+    passes as ``d_j (x . u)``: [3, 128] fp32 = (u_k, u_v, W_out^T u_l) — the logit vector through ``project_out`` like the
+    logit-key plane (``fold_weights``)."""
+    u = w_dyn.detach().float().reshape(3, EMBED_DIM)
+    return torch.stack((u[0], u[1], torch.mv(w_out.detach().float().t(), u[2]))).contiguous()
 
 
 def _fold_tables_f32(h: Tensor, blocks: list[Tensor], w_fixed: Tensor | None):
@@ -128,6 +139,7 @@ def build_folded_cache(
     cache_dtype: torch.dtype = torch.float32,
     gemm_dtype: torch.dtype = torch.float32,
     fold: bool = True,
+    w_dyn: Tensor | None = None,
 ) -> FoldedCache:
     """One ``[B*N,128] x [128,128]`` GEMM per plane, written straight into its plane of the
     plane-major cache (no permute/cast copies), plus a GEMV for the graph context.
@@ -186,4 +198,9 @@ def build_folded_cache(
         q_step0 = None
         w_cap = w_ctx.float()[:, d].contiguous() if w_ctx.shape[1] > d else None  # PDP: no context scalar
     w_time = w_ctx.float()[:, d + 1].contiguous() if w_ctx.shape[1] > d + 1 else None  # CVRPTW: current time
-    return FoldedCache(env_name, kvl, ctx_first, ctx_cur, q_bias, q_step0, w_cap, w_time)
+    dyn = None
+    if env_name == "sdvrp":
+        if w_dyn is None:
+            raise ValueError("sdvrp needs the dynamic embedding's weight (decoder.dynamic_embedding.projection.weight)")
+        dyn = fold_dynamic(w_dyn, w_out)
+    return FoldedCache(env_name, kvl, ctx_first, ctx_cur, q_bias, q_step0, w_cap, w_time, dyn)

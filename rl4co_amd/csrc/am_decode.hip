@@ -53,6 +53,22 @@
 //                 mass(key < cut or (key == cut, c <= lo)) <= thr (bisection, <= 13 passes) ; removed as above.
 //                 lse = log(mass(kept)) (== the unfiltered lse when nothing is removed) ; removed entries: lp = -inf,
 //                 sampling key = -inf
+//   SDVRP       = (env_embeddings/dynamic.py:60-78, zoo/am/decoder.py:142-152) the reference adds Linear(1 -> 3 * 128)(d) to
+//                 the glimpse key, the glimpse value and the logit key, d_j = remaining demand of node j (the depot's taken
+//                 as 0). Rank one per node, so with (u_k, u_v, u_l' = W_out^T u_l) the batch-shared fp32 vectors:
+//                 kq_h   = tree over the head's LPH chunks of [fma chain of q against u_k], once per step
+//                 score  = fmaf(d_j, kq_h, score(c,h) above)
+//                 pd_g   = fmaf(p_c, d_c, pd_g) per row group over its entries in ascending c
+//                 heads[d] = fmaf(tree_g(pd_g), u_v[d], tree_g(o_g[d])) * (1 / tree_g(l_g))
+//                 ul     = tree over the row's LPR chunks of [fma chain of heads against u_l'], once per step
+//                 logit  = fmaf(d_j, ul, logit(c) above)
+//                 With 16-bit planes the one-wave kernel keeps G = 16 row groups for this environment (one accumulator per
+//                 load in flight: entry c -> load (c % 16) / 4, row c % 4; tree = butterfly over the 4 rows, then
+//                 ((g0 + g1) + (g2 + g3)) over the loads) — the four-wave kernels' tree, so STREAM, LDS and WIDE agree bit
+//                 for bit. State (sdvrp/env.py:56-123, one rounding each): delivered = min(d[a], cap - used) ;
+//                 used = (used + delivered) * (a != 0) ; d[a] = d[a] - delivered ; done = no d_j > 0 ; customer j masked
+//                 iff d_j == 0 or used >= cap ; depot masked iff cur == 0 and some customer is feasible. The list holds
+//                 every feasible node every step (a customer comes back until it is served): no row cache.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -65,6 +81,8 @@ constexpr int kD = RL4CO_EMBED_DIM;
 constexpr int kH = RL4CO_NUM_HEADS;
 constexpr int kDH = kD / kH;
 constexpr int kUnroll = 4;  // wave-wide 1 KiB loads kept in flight per pass
+constexpr int kLdsWaves = 4;    // four-wave kernels (LDS / WIDE, below): waves per trajectory
+constexpr int kLdsGroups = 16;  // ... and their row groups
 constexpr float kNegInf = -__builtin_huge_valf();
 constexpr float kSqrtD = 11.3137084989847604f;  // fl32(sqrt(128)), attention.py:293
 
@@ -193,7 +211,7 @@ __device__ inline int build_list(const rl4co_am_decode_args& a, const uint8_t* m
 template <int ENV>
 __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& st, float* lg, const uint16_t* fl, int F,
                                       uint8_t* mk, uint8_t* vis, const float* dem, float cap, int r, int t, int N, int lane,
-                                      const float* oplocs, const float* opmax, const float* twdur, int bc);
+                                      const float* oplocs, const float* opmax, const float* twdur, int bc, float* dd = nullptr);
 
 // One wave: raw logits lg[0..F) (list order) -> log-probs, selection, outputs, environment
 // transition on the LDS-resident mask. Returns the action; st is updated (incl. done).
@@ -203,7 +221,7 @@ template <int ENV, bool FILT = false>
 __device__ inline int finalize_and_step(const rl4co_am_decode_args& a, TrajState& st, float* lg, float* xs,
                                         const uint16_t* fl, int F, uint8_t* mk, uint8_t* vis, const float* dem, float cap,
                                         int r, int t, int N, int lane, const float* oplocs = nullptr,
-                                        const float* opmax = nullptr, const float* twdur = nullptr) {
+                                        const float* opmax = nullptr, const float* twdur = nullptr, float* dd = nullptr) {
   bool nan_seen = false;
   float zmax = kNegInf;
   for (int c = lane; c < F; c += 64) {
@@ -264,7 +282,7 @@ __device__ inline int finalize_and_step(const rl4co_am_decode_args& a, TrajState
   rl4co::bfly_argmax(best, bc);
   if (a.entropy) st.ent_acc = st.ent_acc - rl4co::bfly_sum<1, 64>(ent);
   wave_lds_sync();
-  return commit_and_step<ENV>(a, st, lg, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur, bc);
+  return commit_and_step<ENV>(a, st, lg, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur, bc, dd);
 }
 
 // One wave: lg[0..F) hold the step's log-probs (list order) and `bc` the selected list position. Evaluate-mode lookup,
@@ -272,7 +290,7 @@ __device__ inline int finalize_and_step(const rl4co_am_decode_args& a, TrajState
 template <int ENV>
 __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& st, float* lg, const uint16_t* fl, int F,
                                       uint8_t* mk, uint8_t* vis, const float* dem, float cap, int r, int t, int N, int lane,
-                                      const float* oplocs, const float* opmax, const float* twdur, int bc) {
+                                      const float* oplocs, const float* opmax, const float* twdur, int bc, float* dd) {
   const int64_t tcol = (int64_t)a.t0 + t;
   int bi;
   float logp;
@@ -327,6 +345,28 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
       left |= (v & 1) != 0;
     }
     st.done = !__any(left);  // pdp/env.py:83
+  } else if (ENV == RL4CO_ENV_SDVRP) {
+    // split delivery (sdvrp/env.py:56-123); dd: the trajectory's remaining demands (depot column 0), in LDS
+    const float da = dd[bi];
+    const float delivered = fminf(da, cap - st.used);
+    st.used = (st.used + delivered) * (bi != 0 ? 1.0f : 0.0f);
+    st.cur = bi;
+    wave_lds_sync();  // every lane has read dd[bi]
+    if (lane == 0) dd[bi] = da - delivered;
+    wave_lds_sync();
+    bool any_feasible = false, any_left = false;
+    for (int j = lane; j < N; j += 64) {
+      const float dj = dd[j];
+      any_left |= dj > 0.0f;
+      if (j >= 1) {
+        const bool masked = (dj == 0.0f) || (st.used >= cap);
+        mk[j] = masked ? 0 : 1;
+        any_feasible |= !masked;
+      }
+    }
+    any_feasible = __any(any_feasible);
+    st.done = !__any(any_left);
+    if (lane == 0) mk[0] = ((st.cur == 0) && any_feasible) ? 0 : 1;
   } else if (ENV == RL4CO_ENV_PCTSP) {
     // prize-collecting TSP (pctsp/env.py:62-91,141-148); st.used is the prize collected so far,
     // dem the real prize per node (depot column 0)
@@ -443,6 +483,10 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   constexpr int RPL = 64 / LPR;   // rows per wave-wide load (= row groups G)
   constexpr int LPH = kDH / EPL;  // lanes per head
   constexpr bool kRowCache = !UNFOLD && (ENV == RL4CO_ENV_TSP || ENV == RL4CO_ENV_CVRP);
+  constexpr bool kDyn = ENV == RL4CO_ENV_SDVRP;            // dynamic embedding: d_j * (x . u) joins every dot product
+  constexpr int NG = (kDyn && RPL == 4) ? kUnroll : 1;     // accumulator sets of pass 2 (SDVRP, 16-bit planes: one per load)
+  // the tree below spells out four loads of four rows: the four-wave kernels' 4 waves x 4 rows, entry c -> group c % 16
+  static_assert(NG == 1 || (kUnroll == 4 && kLdsWaves == 4 && kLdsGroups == 16), "SDVRP: STREAM must keep the LDS / WIDE summation tree");
   using elem = typename C::elem;
   using raw_t = typename C::raw;
 
@@ -460,6 +504,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   elem* rc = reinterpret_cast<elem*>(vis + Np);         // [S][3][128] row cache (16-byte aligned: 40 Np + 32 bytes in)
   uint8_t* rslot = reinterpret_cast<uint8_t*>(rc + S * 3 * kD);  // [Np] slot of each node, kRowCacheNone if not resident
   uint8_t* rpend = rslot + Np;                                    // [S] 1 = slot not filled yet
+  float* dd = reinterpret_cast<float*>(vis + Np);                 // [Np] SDVRP (no row cache): remaining demands
 
   const int cb = r % a.B_inst;  // instance whose cache this trajectory reads
   const int rg = lane / LPR;    // row group inside a wave-wide load
@@ -477,12 +522,15 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   // ---- load the trajectory state ---------------------------------------------------
   uint8_t* gmask = a.action_mask + (int64_t)r * N;
   for (int j = lane; j < Np; j += 64) mk[j] = (j < N) ? gmask[j] : (uint8_t)0;
-  constexpr bool kScalarCtx = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_PCTSP || ENV == RL4CO_ENV_CVRPTW;
+  constexpr bool kScalarCtx = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_PCTSP || ENV == RL4CO_ENV_CVRPTW || kDyn;
   constexpr bool kCvrpLike = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_CVRPTW;
   if (ENV == RL4CO_ENV_PDP) {  // bit 0 = available, bit 1 = to_deliver
     const uint8_t* gv = a.visited + (int64_t)r * N;
     const uint8_t* gt = a.to_deliver + (int64_t)r * N;
     for (int j = lane; j < Np; j += 64) vis[j] = (j < N) ? (uint8_t)((gv[j] != 0 ? 1 : 0) | (gt[j] != 0 ? 2 : 0)) : (uint8_t)0;
+  } else if (kDyn) {
+    const float* gd = a.demand_state + (int64_t)r * N;
+    for (int j = lane; j < Np; j += 64) dd[j] = (j < N) ? gd[j] : 0.0f;
   } else if (ENV != RL4CO_ENV_TSP) {
     const uint8_t* gv = a.visited + (int64_t)r * N;
     for (int j = lane; j < Np; j += 64) vis[j] = (j < N) ? gv[j] : (uint8_t)1;
@@ -490,7 +538,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   TrajState st;
   st.cur = (int)a.current_node[r];
   st.first = (ENV == RL4CO_ENV_TSP) ? (int)a.first_node[r] : 0;
-  st.step_i = !kCvrpLike ? a.step_i[r] : 0;
+  st.step_i = !(kCvrpLike || kDyn) ? a.step_i[r] : 0;
   st.time = (ENV == RL4CO_ENV_CVRPTW) ? a.current_time[r] : 0.0f;
   st.used = kScalarCtx ? a.used_capacity[r] : 0.0f;  // OP: tour length so far
   st.done = a.done[r] != 0;
@@ -504,7 +552,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   // the context scalar is cap - used in both depot environments (context.py:147-149, 211-213):
   // OP: longest tour that may still end at the depot (its row of the table) minus the tour so far
   // PCTSP: prize still to collect, clamped at 0 (context.py:184-198)
-  const float cap = (kCvrpLike || ENV == RL4CO_ENV_PCTSP) ? a.vehicle_capacity[r]
+  const float cap = (kCvrpLike || ENV == RL4CO_ENV_PCTSP || kDyn) ? a.vehicle_capacity[r]
                                                                       : ((ENV == RL4CO_ENV_OP) ? opmax[0] : 0.0f);
   const float* dem = kCvrpLike                  ? a.demand + (int64_t)cb * (N - 1)
                      : (ENV == RL4CO_ENV_PCTSP) ? a.demand + (int64_t)cb * N
@@ -544,6 +592,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
 #pragma unroll
   for (int e = 0; e < EPL; ++e) qb[e] = a.q_bias ? a.q_bias[(int64_t)cb * kD + e0 + e] : 0.0f;
 
+  const float* dynv = kDyn ? a.dyn_vectors + e0 : nullptr;  // (u_k, u_v, u_l') [3,128]: this lane's EPL dims of each
   const bool single = a.max_steps == 1;
   int t = 0;
   int rows_read = 0;  // cache rows this trajectory streamed from HBM (x 3 planes): the launch's real HBM read volume
@@ -624,6 +673,12 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
 
     // ---- pass 1: per-head scores over the glimpse keys of the listed nodes -------------
     float m = kNegInf;
+    float kq = 0.0f;  // SDVRP: q_h . u_k,h
+    if constexpr (kDyn) {
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) kq = fmaf(q[e], dynv[e], kq);
+      kq = rl4co::bfly_sum<1, LPH>(kq);
+    }
     auto score = [&](const raw_t& rw, int c, int j) {  // j < 0: no entry (a no-op)
       const bool valid = j >= 0;
       float k[EPL];
@@ -632,6 +687,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
 #pragma unroll
       for (int e = 0; e < EPL; ++e) acc = fmaf(q[e], k[e], acc);
       acc = rl4co::bfly_sum<1, LPH>(acc);
+      if constexpr (kDyn) acc = fmaf(j > 0 ? dd[j] : 0.0f, kq, acc);
       const bool feas = valid && (!a.mask_inner || mk[valid ? j : 0] != 0);
       const float sv = feas ? acc : kNegInf;
       if (valid && (li % LPH) == 0) sc[c * kH + hd] = sv;
@@ -665,17 +721,26 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
     wave_lds_sync();
 
     // ---- pass 2: softmax-weighted value sum ------------------------------------------------
-    float l = 0.0f;
-    float o[EPL];
+    float lacc[NG], pdacc[NG];
+    float oacc[NG][EPL];
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) o[e] = 0.0f;
-    auto accumulate = [&](const raw_t& rw, int c, bool ok) {  // !ok: no entry (adds exact zeros)
+    for (int g = 0; g < NG; ++g) {
+      lacc[g] = 0.0f;
+      pdacc[g] = 0.0f;
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) oacc[g][e] = 0.0f;
+    }
+    auto accumulate = [&](const raw_t& rw, int c, bool ok, int g) {  // !ok: no entry (adds exact zeros)
       float v[EPL];
       C::cvt(rw, v);
       const float p = ok ? sc[c * kH + hd] : 0.0f;
-      l = l + p;
+      lacc[g] = lacc[g] + p;
+      if constexpr (kDyn) {
+        const int j = ok ? (int)fl[c] : 0;
+        pdacc[g] = fmaf(p, j > 0 ? dd[j] : 0.0f, pdacc[g]);
+      }
 #pragma unroll
-      for (int e = 0; e < EPL; ++e) o[e] = fmaf(p, v[e], o[e]);
+      for (int e = 0; e < EPL; ++e) oacc[g][e] = fmaf(p, v[e], oacc[g][e]);
     };
     for (int c0 = 0; c0 < F; c0 += RPL * kUnroll) {
       raw_t rw[kUnroll];
@@ -690,12 +755,28 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
         if (caching && c >= pbeg && c < hend) fill_row(fl[c], 1, rw[u]);
-        accumulate(rw[u], c, ok[u]);
+        accumulate(rw[u], c, ok[u], NG > 1 ? u : 0);
       }
     }
-    l = 1.0f / rl4co::bfly_sum<LPR, 64>(l);  // one IEEE division per step; heads = o * (1/l)
+    // tree over the row groups: the butterfly over a load's rows, then (NG = 4) ((g0 + g1) + (g2 + g3)) over the loads
+    auto tree = [&](auto&& term) -> float {
+      if constexpr (NG == 1) {
+        return rl4co::bfly_sum<LPR, 64>(term(0));
+      } else {
+        return (rl4co::bfly_sum<LPR, 64>(term(0)) + rl4co::bfly_sum<LPR, 64>(term(1))) +
+               (rl4co::bfly_sum<LPR, 64>(term(2)) + rl4co::bfly_sum<LPR, 64>(term(3)));
+      }
+    };
+    const float l = 1.0f / tree([&](int g) { return lacc[g]; });  // one IEEE division per step; heads = o * (1/l)
+    float o[EPL];
+    if constexpr (kDyn) {
+      const float pd = tree([&](int g) { return pdacc[g]; });
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) o[e] = rl4co::bfly_sum<LPR, 64>(o[e]) * l;
+      for (int e = 0; e < EPL; ++e) o[e] = fmaf(pd, dynv[kD + e], tree([&](int g) { return oacc[g][e]; })) * l;
+    } else {
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) o[e] = tree([&](int g) { return oacc[g][e]; }) * l;
+    }
     if constexpr (UNFOLD) {  // glimpse = project_out(heads) (attention.py:287), heads broadcast through LDS
       wave_lds_sync();       // every lane is done with the softmax numerators in sc
       if (rg == 0) {
@@ -707,6 +788,12 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
     }
 
     // ---- pass 3: pointer logits against the (project_out-folded) logit key -----------
+    float ul = 0.0f;  // SDVRP: heads . u_l'
+    if constexpr (kDyn) {
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) ul = fmaf(o[e], dynv[2 * kD + e], ul);
+      ul = rl4co::bfly_sum<1, LPR>(ul);
+    }
     auto logit = [&](const raw_t& rw, int c) {
       float k[EPL];
       C::cvt(rw, k);
@@ -714,6 +801,10 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
 #pragma unroll
       for (int e = 0; e < EPL; ++e) acc = fmaf(o[e], k[e], acc);
       acc = rl4co::bfly_sum<1, LPR>(acc);
+      if constexpr (kDyn) {
+        const int j = c < F ? (int)fl[c] : 0;
+        acc = fmaf(j > 0 ? dd[j] : 0.0f, ul, acc);
+      }
       if (c < F && li == 0) lg[c] = acc;
     };
     for (int c0 = 0; c0 < F; c0 += RPL * kUnroll) {
@@ -739,7 +830,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
     }
     wave_lds_sync();
 
-    const int bi = finalize_and_step<ENV, FILT>(a, st, lg, sc, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur);
+    const int bi = finalize_and_step<ENV, FILT>(a, st, lg, sc, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur, dd);
     if (caching && rslot[bi] != kRowCacheNone && !candidate(bi)) {
       // the resident node left: its slot goes to the highest candidate not resident, which the next step that lists
       // it reads from HBM anyway
@@ -770,6 +861,9 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
       gv[j] = vis[j] & 1;
       gt[j] = (vis[j] >> 1) & 1;
     }
+  } else if (kDyn) {
+    float* gd = a.demand_state + (int64_t)r * N;
+    for (int j = lane; j < N; j += 64) gd[j] = dd[j];
   } else if (ENV != RL4CO_ENV_TSP) {
     uint8_t* gv = a.visited + (int64_t)r * N;
     for (int j = lane; j < N; j += 64) gv[j] = vis[j];
@@ -778,7 +872,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
     a.current_node[r] = st.cur;
     a.done[r] = st.done ? 1 : 0;
     if (ENV == RL4CO_ENV_TSP) a.first_node[r] = st.first;
-    if (!kCvrpLike) a.step_i[r] = st.step_i;
+    if (!(kCvrpLike || kDyn)) a.step_i[r] = st.step_i;
     if (ENV == RL4CO_ENV_CVRPTW) a.current_time[r] = st.time;
     if (kScalarCtx) a.used_capacity[r] = st.used;
     if (a.n_steps) a.n_steps[r] = t;
@@ -806,8 +900,6 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
 //                     step; for few trajectories whose planes do not fit LDS (CVRP-500 x 1024:
 //                     4096 waves instead of 1024, 120 -> 61 us per step).
 // ================================================================================================
-constexpr int kLdsWaves = 4;
-constexpr int kLdsGroups = 16;
 
 // The first half of finalize_and_step for the four-wave kernels, bit for bit: the ELEMENTWISE work of a step's N logits
 // — clip, the softmax exponentials, log-probs, the sampling keys with their Philox draws: ~200 VALU operations per node —
@@ -911,6 +1003,8 @@ __host__ __device__ inline int wide_scratch_bytes(int N) {
   return lds_variant_sc_rows(N) * kH * 4 + nw * 4 + kLdsWaves * kH * 4 + 32 + 2 * nw + 2 * nw;
 }
 __host__ __device__ inline int lds_variant_bytes(int N) { return 3 * N * kD * 2 + wide_scratch_bytes(N); }
+// SDVRP: the trajectory's remaining demands behind the four-wave kernels' scratch
+__host__ __device__ inline int wide_dyn_bytes(int N, int env) { return env == RL4CO_ENV_SDVRP ? ((N + 3) & ~3) * 4 : 0; }
 
 // Four workgroups per CU (<= 128 registers): CVRP-500 x 1024 is 1024 workgroups = exactly four per CU, ONE round. The half
 // (fp16) builds took 130 - 138 registers under a bound of two — three per CU, so a quarter of the trajectories waited for
@@ -933,6 +1027,8 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   uint16_t* fl = reinterpret_cast<uint16_t*>(shi + 8);              // [nw] nodes this step reads
   uint8_t* mk = reinterpret_cast<uint8_t*>(fl + nw);                // [nw] 1 = feasible
   uint8_t* vis = mk + nw;                                           // [nw] CVRP visited
+  float* dd = reinterpret_cast<float*>(vis + nw);                   // [nw] SDVRP: remaining demands
+  constexpr bool kDyn = ENV == RL4CO_ENV_SDVRP;
 
   const int cb = r % a.B_inst;
   const int rg = lane / LPR, li = lane % LPR, hd = li / LPH, e0 = li * EPL;
@@ -953,6 +1049,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   // o/l partial slots inside this wave's own (dead after pass 2) score chunks
   auto opart = [&](int wv, int d) -> float* { return sc + ((16 * (d >> 5) + 4 * wv) * kH) + (d & 31); };
   auto lpart = [&](int wv, int h) -> float* { return sc + ((16 * 4 + 4 * wv) * kH) + h; };
+  auto pdpart = [&](int wv, int h) -> float* { return lpart(wv, h) + kH; };  // SDVRP: sum p_c d_c, the row behind
 
   // ---- planes HBM -> LDS, once per rollout (16-byte coalesced) --------------------------------
   if constexpr (RESIDENT) {
@@ -970,7 +1067,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   }
   // ---- trajectory state: the same six environments as the streaming kernel (wave 0 owns the transition, the other
   // waves receive the scalars it changes through LDS after every step) ----------------------------------------------
-  constexpr bool kScalarCtx = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_PCTSP || ENV == RL4CO_ENV_CVRPTW;
+  constexpr bool kScalarCtx = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_PCTSP || ENV == RL4CO_ENV_CVRPTW || kDyn;
   constexpr bool kCvrpLike = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_CVRPTW;
   uint8_t* gmask = a.action_mask + (int64_t)r * N;
   for (int j = tid; j < nw; j += 64 * kLdsWaves) mk[j] = (j < N) ? gmask[j] : (uint8_t)0;
@@ -979,6 +1076,9 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
     const uint8_t* gt = a.to_deliver + (int64_t)r * N;
     for (int j = tid; j < nw; j += 64 * kLdsWaves)
       vis[j] = (j < N) ? (uint8_t)((gv[j] != 0 ? 1 : 0) | (gt[j] != 0 ? 2 : 0)) : (uint8_t)0;
+  } else if (kDyn) {
+    const float* gd = a.demand_state + (int64_t)r * N;
+    for (int j = tid; j < nw; j += 64 * kLdsWaves) dd[j] = (j < N) ? gd[j] : 0.0f;
   } else if (ENV != RL4CO_ENV_TSP) {
     const uint8_t* gv = a.visited + (int64_t)r * N;
     for (int j = tid; j < nw; j += 64 * kLdsWaves) vis[j] = (j < N) ? gv[j] : (uint8_t)1;
@@ -986,7 +1086,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   TrajState st;
   st.cur = (int)a.current_node[r];
   st.first = (ENV == RL4CO_ENV_TSP) ? (int)a.first_node[r] : 0;
-  st.step_i = !kCvrpLike ? a.step_i[r] : 0;
+  st.step_i = !(kCvrpLike || kDyn) ? a.step_i[r] : 0;
   st.time = (ENV == RL4CO_ENV_CVRPTW) ? a.current_time[r] : 0.0f;
   st.used = kScalarCtx ? a.used_capacity[r] : 0.0f;  // OP: tour length so far; PCTSP: prize collected
   st.done = a.done[r] != 0;
@@ -997,7 +1097,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
                        : (ENV == RL4CO_ENV_CVRPTW) ? a.time_windows + (int64_t)cb * N * 2
                                                    : nullptr;
   const float* twdur = (ENV == RL4CO_ENV_CVRPTW) ? a.durations + (int64_t)cb * N : nullptr;
-  const float cap = (kCvrpLike || ENV == RL4CO_ENV_PCTSP) ? a.vehicle_capacity[r] : ((ENV == RL4CO_ENV_OP) ? opmax[0] : 0.0f);
+  const float cap = (kCvrpLike || ENV == RL4CO_ENV_PCTSP || kDyn) ? a.vehicle_capacity[r] : ((ENV == RL4CO_ENV_OP) ? opmax[0] : 0.0f);
   const float* dem = kCvrpLike                  ? a.demand + (int64_t)cb * (N - 1)
                      : (ENV == RL4CO_ENV_PCTSP) ? a.demand + (int64_t)cb * N
                                                 : nullptr;
@@ -1012,6 +1112,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
 #pragma unroll
   for (int e = 0; e < EPL; ++e) qb[e] = a.q_bias ? a.q_bias[(int64_t)cb * kD + e0 + e] : 0.0f;
 
+  const float* dynv = kDyn ? a.dyn_vectors + e0 : nullptr;  // (u_k, u_v, u_l') [3,128]: this lane's EPL dims of each
   const bool single = a.max_steps == 1;
   int t = 0;
   int rows_read = 0;
@@ -1055,6 +1156,12 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
 
     // ---- pass 1: scores of this wave's list entries ----------------------------------------------
     float m = kNegInf;
+    float kq = 0.0f;  // SDVRP: q_h . u_k,h
+    if constexpr (kDyn) {
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) kq = fmaf(q[e], dynv[e], kq);
+      kq = rl4co::bfly_sum<1, LPH>(kq);
+    }
     for (int i0 = 0; i0 < iters; i0 += U) {
       uint4 rw[U];
       int jj[U];
@@ -1074,6 +1181,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
 #pragma unroll
         for (int e = 0; e < EPL; ++e) acc = fmaf(q[e], k[e], acc);
         acc = rl4co::bfly_sum<1, LPH>(acc);
+        if constexpr (kDyn) acc = fmaf(jj[u] > 0 ? dd[jj[u]] : 0.0f, kq, acc);
         const bool feas = valid && (!a.mask_inner || mk[valid ? jj[u] : 0] != 0);
         const float sv = feas ? acc : kNegInf;
         if (valid && (li & 1) == 0) sc[c * kH + hd] = sv;
@@ -1099,7 +1207,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
     wave_lds_sync();  // the numerators are consumed by this same wave only
 
     // ---- pass 2: softmax weights and weighted values ---------------------------------------------
-    float l = 0.0f;
+    float l = 0.0f, pd = 0.0f;
     float o[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) o[e] = 0.0f;
@@ -1119,24 +1227,38 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
         C::cvt(rw[u], v);
         const float p = ok[u] ? sc[c * kH + hd] : 0.0f;
         l = l + p;
+        if constexpr (kDyn) {
+          const int j = ok[u] ? (int)fl[c] : 0;
+          pd = fmaf(p, j > 0 ? dd[j] : 0.0f, pd);
+        }
 #pragma unroll
         for (int e = 0; e < EPL; ++e) o[e] = fmaf(p, v[e], o[e]);
       }
     }
     l = rl4co::bfly_sum<LPR, 64>(l);
+    if constexpr (kDyn) pd = rl4co::bfly_sum<LPR, 64>(pd);
 #pragma unroll
     for (int e = 0; e < EPL; ++e) o[e] = rl4co::bfly_sum<LPR, 64>(o[e]);
     if (rg == 0) {
 #pragma unroll
       for (int e = 0; e < EPL; ++e) *opart(w, e0 + e) = o[e];
       if ((li & 1) == 0) *lpart(w, hd) = l;
+      if (kDyn && (li & 1) == 0) *pdpart(w, hd) = pd;
     }
     __syncthreads();  // B2: partials of the four waves visible
     l = 1.0f / ((*lpart(0, hd) + *lpart(1, hd)) + (*lpart(2, hd) + *lpart(3, hd)));
+    if constexpr (kDyn) pd = (*pdpart(0, hd) + *pdpart(1, hd)) + (*pdpart(2, hd) + *pdpart(3, hd));
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
       const int d = e0 + e;
-      o[e] = ((*opart(0, d) + *opart(1, d)) + (*opart(2, d) + *opart(3, d))) * l;
+      const float os = (*opart(0, d) + *opart(1, d)) + (*opart(2, d) + *opart(3, d));
+      o[e] = (kDyn ? fmaf(pd, dynv[kD + e], os) : os) * l;
+    }
+    float ul = 0.0f;  // SDVRP: heads . u_l'
+    if constexpr (kDyn) {
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) ul = fmaf(o[e], dynv[2 * kD + e], ul);
+      ul = rl4co::bfly_sum<1, LPR>(ul);
     }
 
     // ---- pass 3: logits of this wave's list entries ---------------------------------------------------
@@ -1156,6 +1278,10 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
 #pragma unroll
         for (int e = 0; e < EPL; ++e) acc = fmaf(o[e], k[e], acc);
         acc = rl4co::bfly_sum<1, LPR>(acc);
+        if constexpr (kDyn) {
+          const int j = c < F ? (int)fl[c] : 0;
+          acc = fmaf(j > 0 ? dd[j] : 0.0f, ul, acc);
+        }
         if (c < F && li == 0) lg[c] = acc;
       }
     }
@@ -1165,7 +1291,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
     // transition and the next step's list -----------------------------------------------------------------
     const int bc = wide_scores<ENV, FILT>(a, st, lg, fl, F, mk, sc, nw, r, t, N, tid);
     if (w == 0) {
-      commit_and_step<ENV>(a, st, lg, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur, bc);
+      commit_and_step<ENV>(a, st, lg, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur, bc, dd);
       const int Fn = build_list(a, mk, fl, N, lane);
       if (lane == 0) {  // the scalars the next query is built from, for the other three waves
         shi[0] = st.cur;
@@ -1197,6 +1323,9 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
         gv[j] = vis[j] & 1;
         gt[j] = (vis[j] >> 1) & 1;
       }
+    } else if (kDyn) {
+      float* gd = a.demand_state + (int64_t)r * N;
+      for (int j = lane; j < N; j += 64) gd[j] = dd[j];
     } else if (ENV != RL4CO_ENV_TSP) {
       uint8_t* gv = a.visited + (int64_t)r * N;
       for (int j = lane; j < N; j += 64) gv[j] = vis[j];
@@ -1205,7 +1334,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
       a.current_node[r] = st.cur;
       a.done[r] = st.done ? 1 : 0;
       if (ENV == RL4CO_ENV_TSP) a.first_node[r] = st.first;
-      if (!kCvrpLike) a.step_i[r] = st.step_i;
+      if (!(kCvrpLike || kDyn)) a.step_i[r] = st.step_i;
       if (ENV == RL4CO_ENV_CVRPTW) a.current_time[r] = st.time;
       if (kScalarCtx) a.used_capacity[r] = st.used;
       if (a.n_steps) a.n_steps[r] = t;
@@ -1222,7 +1351,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
 
 template <int ENV, bool RESIDENT, class C, bool FILT>
 int launch_wide_f(const rl4co_am_decode_args& a, hipStream_t stream) {
-  const int lds = RESIDENT ? lds_variant_bytes(a.N) : wide_scratch_bytes(a.N);
+  const int lds = (RESIDENT ? lds_variant_bytes(a.N) : wide_scratch_bytes(a.N)) + wide_dyn_bytes(a.N, ENV);
   if (lds > 64 * 1024) {
     RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(am_decode_wide_kernel<ENV, RESIDENT, C, FILT>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -1249,10 +1378,11 @@ inline int resolve_variant(const rl4co_am_decode_args& a) {
   const bool bf16 = a.cache_dtype == RL4CO_DT_BF16 || f16;  // (16-bit planes)
   // multistart on the matrix cores (am_decode_ms.hip): 16-bit planes, N <= 128, plain outputs; every environment
   const bool ms_ok = bf16 && a.N <= 128 && a.B_inst > 0 && a.all_logps == nullptr && a.entropy == nullptr &&
-                     !rl4co::topkp_on(a);  // the top-k / top-p filter is not in am_decode_ms.hip
+                     !rl4co::topkp_on(a) &&           // the top-k / top-p filter is not in am_decode_ms.hip
+                     a.env != RL4CO_ENV_SDVRP;        // nor is the dynamic embedding
   if (a.variant == RL4CO_VARIANT_MS) return ms_ok ? RL4CO_VARIANT_MS : -1;
-  const bool fits = bf16 && lds_variant_bytes(a.N) <= 80 * 1024;
-  const bool wide_ok = bf16 && wide_scratch_bytes(a.N) <= 64 * 1024;
+  const bool fits = bf16 && lds_variant_bytes(a.N) + wide_dyn_bytes(a.N, a.env) <= 80 * 1024;
+  const bool wide_ok = bf16 && wide_scratch_bytes(a.N) + wide_dyn_bytes(a.N, a.env) <= 64 * 1024;
   if (a.variant == RL4CO_VARIANT_STREAM) return RL4CO_VARIANT_STREAM;
   if (a.variant == RL4CO_VARIANT_LDS) return fits ? RL4CO_VARIANT_LDS : -1;
   if (a.variant == RL4CO_VARIANT_WIDE) return wide_ok ? RL4CO_VARIANT_WIDE : -1;
@@ -1292,7 +1422,7 @@ inline int stream_wg_per_cu(int bytes, int gran) {
 // (DESIGN 4.1). RL4CO_DECODE_ROW_CACHE = n (read at every launch, so one process can compare) sets at most n slots, fp32
 // planes included; 0 turns the cache off.
 int row_cache_slots(const rl4co_am_decode_args& a, int esz, bool unfold) {
-  if (unfold || a.max_steps == 1 || (a.env != RL4CO_ENV_TSP && a.env != RL4CO_ENV_CVRP)) return 0;
+  if (unfold || a.max_steps == 1 || (a.env != RL4CO_ENV_TSP && a.env != RL4CO_ENV_CVRP)) return 0;  // (SDVRP: a visited node comes back)
   const int base = rl4co_am_decode_lds_bytes(a.N, a.env);
   int S = 0;
   while (S < min(a.N, 255)) {
@@ -1327,9 +1457,8 @@ int launch(const rl4co_am_decode_args& a, hipStream_t stream) {
 }  // namespace
 
 extern "C" int rl4co_am_decode_lds_bytes(int N, int env) {
-  (void)env;
   const int Np = lds_pad(N);
-  return Np * kH * 4 + Np * 4 + kH * 4 + Np * 2 + Np + Np;
+  return Np * kH * 4 + Np * 4 + kH * 4 + Np * 2 + Np + Np + (env == RL4CO_ENV_SDVRP ? Np * 4 : 0);  // SDVRP: + the demands
 }
 
 extern "C" int rl4co_am_decode_row_groups(const rl4co_am_decode_args* args) {
@@ -1338,6 +1467,7 @@ extern "C" int rl4co_am_decode_row_groups(const rl4co_am_decode_args* args) {
   if (v < 0) return -1;
   if (v == RL4CO_VARIANT_MS) return 0;  // bf16 MFMA variant: tolerance-tested, no specified-order oracle
   if (v == RL4CO_VARIANT_LDS || v == RL4CO_VARIANT_WIDE) return kLdsGroups;
+  if (args->env == RL4CO_ENV_SDVRP && args->cache_dtype != RL4CO_DT_F32) return kLdsGroups;  // one accumulator per load
   return args->cache_dtype != RL4CO_DT_F32 ? 64 / (kD / CacheBF16::EPL) : 64 / (kD / CacheF32::EPL);
 }
 
@@ -1349,7 +1479,7 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
   RL4CO_REQUIRE(args != nullptr);
   const rl4co_am_decode_args& a = *args;
   RL4CO_REQUIRE(a.env == RL4CO_ENV_TSP || a.env == RL4CO_ENV_CVRP || a.env == RL4CO_ENV_OP ||
-                a.env == RL4CO_ENV_PCTSP || a.env == RL4CO_ENV_PDP || a.env == RL4CO_ENV_CVRPTW);
+                a.env == RL4CO_ENV_PCTSP || a.env == RL4CO_ENV_PDP || a.env == RL4CO_ENV_CVRPTW || a.env == RL4CO_ENV_SDVRP);
   RL4CO_REQUIRE(a.B > 0 && a.B_inst > 0 && a.B % a.B_inst == 0);
   RL4CO_REQUIRE(a.N >= 2 && a.N <= 4096);
   RL4CO_REQUIRE(a.max_steps >= 1);
@@ -1386,6 +1516,9 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
   } else if (a.env == RL4CO_ENV_CVRPTW) {
     RL4CO_REQUIRE(a.w_cap && a.w_time && a.demand && a.used_capacity && a.vehicle_capacity && a.visited);
     RL4CO_REQUIRE(a.locs && a.time_windows && a.durations && a.current_time);
+  } else if (a.env == RL4CO_ENV_SDVRP) {
+    RL4CO_REQUIRE(a.w_cap && a.dyn_vectors && a.demand_state && a.used_capacity && a.vehicle_capacity);
+    RL4CO_REQUIRE((reinterpret_cast<uintptr_t>(a.dyn_vectors) & 15) == 0);
   } else if (a.env == RL4CO_ENV_PDP) {
     RL4CO_REQUIRE(a.visited && a.to_deliver && a.step_i && (a.N - 1) % 2 == 0);
   } else if (a.env == RL4CO_ENV_PCTSP) {
@@ -1413,6 +1546,7 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
       case RL4CO_ENV_OP: return res ? launch_wide<RL4CO_ENV_OP, true>(a, s) : launch_wide<RL4CO_ENV_OP, false>(a, s);
       case RL4CO_ENV_PCTSP: return res ? launch_wide<RL4CO_ENV_PCTSP, true>(a, s) : launch_wide<RL4CO_ENV_PCTSP, false>(a, s);
       case RL4CO_ENV_PDP: return res ? launch_wide<RL4CO_ENV_PDP, true>(a, s) : launch_wide<RL4CO_ENV_PDP, false>(a, s);
+      case RL4CO_ENV_SDVRP: return res ? launch_wide<RL4CO_ENV_SDVRP, true>(a, s) : launch_wide<RL4CO_ENV_SDVRP, false>(a, s);
       default: return res ? launch_wide<RL4CO_ENV_CVRPTW, true>(a, s) : launch_wide<RL4CO_ENV_CVRPTW, false>(a, s);
     }
   }
@@ -1423,9 +1557,12 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
       case RL4CO_ENV_OP: return launch<CacheF16, RL4CO_ENV_OP>(a, s);
       case RL4CO_ENV_PCTSP: return launch<CacheF16, RL4CO_ENV_PCTSP>(a, s);
       case RL4CO_ENV_PDP: return launch<CacheF16, RL4CO_ENV_PDP>(a, s);
+      case RL4CO_ENV_SDVRP: return launch<CacheF16, RL4CO_ENV_SDVRP>(a, s);
       default: return launch<CacheF16, RL4CO_ENV_CVRPTW>(a, s);
     }
   }
+  if (a.env == RL4CO_ENV_SDVRP)
+    return a.cache_dtype == RL4CO_DT_F32 ? launch<CacheF32, RL4CO_ENV_SDVRP>(a, s) : launch<CacheBF16, RL4CO_ENV_SDVRP>(a, s);
   if (a.env == RL4CO_ENV_CVRPTW)
     return a.cache_dtype == RL4CO_DT_F32 ? launch<CacheF32, RL4CO_ENV_CVRPTW>(a, s)
                                          : launch<CacheBF16, RL4CO_ENV_CVRPTW>(a, s);

@@ -127,6 +127,55 @@ __global__ void __launch_bounds__(64) cvrp_step_kernel(
   cvrp_step_body(action ? action + blockIdx.x : nullptr, demand, used_capacity, vehicle_capacity, visited, cur, mask, done, B, B_inst, N, err, (int)blockIdx.x, (int)threadIdx.x);
 }
 
+// ---- split-delivery VRP (envs/routing/sdvrp/env.py:56-123): every line one IEEE fp32 operation, in the reference's order
+__global__ void __launch_bounds__(64) sdvrp_step_kernel(const int64_t* action, float* demand, float* used_capacity,
+                                                        const float* vehicle_capacity, int64_t* cur, uint8_t* mask,
+                                                        uint8_t* done, int N, int32_t* err) {
+  const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
+  float* dd = demand + (int64_t)b * N;
+  uint8_t* row = mask + (int64_t)b * N;
+  const float cap = vehicle_capacity[b];
+  float used = used_capacity[b];
+  int64_t c = cur[b];
+  bool bad = false;
+  float left = 0.0f;  // remaining demand of the visited node after this step
+  if (action != nullptr) {
+    int64_t a = action[b];
+    if (a < 0 || a >= N) {
+      bad = true;
+      a = 0;
+    }
+    const float da = dd[a];
+    const float delivered = fminf(da, cap - used);          // sdvrp/env.py:64
+    used = (used + delivered) * (a != 0 ? 1.0f : 0.0f);     // sdvrp/env.py:67
+    left = da - delivered;                                  // sdvrp/env.py:70
+    c = a;
+  }
+  __syncthreads();  // every lane has read dd[c] before lane 0 replaces it
+  bool any_feasible = false, any_left = false;
+  for (int j = lane; j < N; j += 64) {
+    const float dj = (action != nullptr && j == c) ? left : dd[j];
+    any_left |= dj > 0.0f;
+    if (j >= 1) {
+      const bool masked = (dj == 0.0f) || (used >= cap);    // sdvrp/env.py:119-121
+      row[j] = masked ? 0 : 1;
+      any_feasible |= !masked;
+    }
+  }
+  any_feasible = __any(any_feasible);
+  any_left = __any(any_left);
+  if (lane == 0) {
+    row[0] = ((c == 0) && any_feasible) ? 0 : 1;            // sdvrp/env.py:122
+    if (action != nullptr) {
+      dd[c] = left;
+      used_capacity[b] = used;
+      cur[b] = c;
+      done[b] = any_left ? 0 : 1;                           // sdvrp/env.py:73
+    }
+    if (bad && err) atomicOr(err, RL4CO_EBIT_INFEASIBLE);
+  }
+}
+
 }  // namespace
 
 extern "C" int rl4co_tsp_step(const int64_t* action, uint8_t* action_mask, int64_t* first_node,
@@ -151,6 +200,18 @@ extern "C" int rl4co_cvrp_step(const int64_t* action, const float* demand, float
   hipLaunchKernelGGL(cvrp_step_kernel, dim3(B), dim3(64), 0, rl4co::as_stream(stream), action,
                      demand, used_capacity, vehicle_capacity, visited, current_node, action_mask,
                      done, B, B_inst, N, err);
+  RL4CO_HIP_TRY(hipGetLastError());
+  return RL4CO_OK;
+}
+
+extern "C" int rl4co_sdvrp_step(const int64_t* action, float* demand_with_depot, float* used_capacity,
+                                const float* vehicle_capacity, int64_t* current_node, uint8_t* action_mask, uint8_t* done,
+                                int B, int N, int32_t* err, void* stream) {
+  RL4CO_REQUIRE(demand_with_depot && used_capacity && vehicle_capacity && current_node && action_mask);
+  RL4CO_REQUIRE(action == nullptr || done != nullptr);
+  RL4CO_REQUIRE(B > 0 && N > 1);
+  hipLaunchKernelGGL(sdvrp_step_kernel, dim3(B), dim3(64), 0, rl4co::as_stream(stream), action, demand_with_depot,
+                     used_capacity, vehicle_capacity, current_node, action_mask, done, N, err);
   RL4CO_HIP_TRY(hipGetLastError());
   return RL4CO_OK;
 }

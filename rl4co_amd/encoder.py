@@ -19,7 +19,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .cache import EMBED_DIM, FoldedCache, fold_weights
+from .cache import EMBED_DIM, FoldedCache, fold_dynamic, fold_weights
 from .envspec import customer_features, spec
 
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
@@ -188,6 +188,8 @@ class PackedEncoder:
             t["q_step0"] = None
             t["w_cap"] = w_ctx[:, EMBED_DIM].contiguous() if w_ctx.shape[1] > EMBED_DIM else None  # PDP: no scalar
         t["w_time"] = w_ctx[:, EMBED_DIM + 1].contiguous() if w_ctx.shape[1] > EMBED_DIM + 1 else None  # CVRPTW
+        w_dyn = getattr(getattr(dec.dynamic_embedding, "projection", None), "weight", None)  # SDVRP
+        t["dyn"] = None if w_dyn is None else fold_dynamic(w_dyn, dec.pointer.project_out.weight)
         self.num_layers = len(layers)
         self.t, self.version = t, ver
         return t
@@ -318,5 +320,5 @@ class PackedEncoder:
                                 w_out_t=dec.pointer.project_out.weight.detach().float().t().contiguous(),
                                 w_placeholder=None if ph is None else ph.detach().float().contiguous())
             return cache, hidden
-        cache = FoldedCache(pol.env_name, kvl, ctx_first, ctx_cur, q_bias, t["q_step0"], t["w_cap"], t["w_time"])
+        cache = FoldedCache(pol.env_name, kvl, ctx_first, ctx_cur, q_bias, t["q_step0"], t["w_cap"], t["w_time"], t["dyn"])
         return cache, hidden

@@ -457,6 +457,77 @@ class CVRPEnv(RL4COEnvBase):
             K.raise_if_error(err)
 
 
+class SDVRPEnv(CVRPEnv):
+    """Split-delivery VRP (envs/routing/sdvrp/env.py:15-147): CVRP's instances, generator and reward; a visit delivers
+    ``min(remaining demand, remaining capacity)`` and a customer can be entered until its demand is 0. The state carries
+    ``demand_with_depot`` [B, N] (remaining demand, depot column 0) instead of ``visited``."""
+
+    name = "sdvrp"
+
+    def _reset(self, td: TensorDict, batch_size) -> TensorDict:
+        """sdvrp/env.py:91-115"""
+        device = td["locs"].device
+        b = td["locs"].shape[0]
+        n = td["locs"].shape[-2] + 1
+        demand = td["demand"].contiguous()
+        td_reset = TensorDict(
+            {
+                "locs": torch.cat((td["depot"][:, None, :], td["locs"]), -2).contiguous(),
+                "demand": demand,
+                "demand_with_depot": torch.cat((torch.zeros_like(demand[:, :1]), demand), -1).contiguous(),
+                "current_node": torch.zeros(b, 1, dtype=torch.long, device=device),
+                "used_capacity": torch.zeros((b, 1), device=device),
+                "vehicle_capacity": torch.full((b, 1), self.generator.vehicle_capacity, device=device),
+                "action_mask": torch.zeros((b, n), dtype=torch.bool, device=device),
+                "done": torch.zeros((b,), dtype=torch.bool, device=device),
+            },
+            batch_size=[b],
+        )
+        self.get_action_mask(td_reset)
+        return td_reset
+
+    def _step(self, td: TensorDict) -> TensorDict:
+        """sdvrp/env.py:56-89 via rl4co_sdvrp_step (in place, mask included)."""
+        K.sdvrp_step(td["action"].contiguous(), td["demand_with_depot"], td["used_capacity"], td["vehicle_capacity"],
+                     td["current_node"], td["action_mask"], td["done"])
+        return td
+
+    def get_action_mask(self, td: TensorDict) -> Tensor:
+        """sdvrp/env.py:117-123 (recomputed in place into td['action_mask'])."""
+        K.sdvrp_step(None, td["demand_with_depot"], td["used_capacity"], td["vehicle_capacity"], td["current_node"],
+                     td["action_mask"], None)
+        return td["action_mask"]
+
+    def check_solution_validity(self, td: TensorDict, actions: Tensor, err: Tensor | None = None) -> None:
+        """sdvrp/env.py:125-147: replay the deliveries; the depot is not visited twice in a row while demand is left, and
+        at the end no demand is left (trailing depot padding is neutral). ``err``: see TSPEnv. Both findings raise the
+        reference's "Invalid tour"-class assertion through RL4CO_EBIT_INVALID_TOUR."""
+        b = actions.shape[0]
+        demand, cap = td["demand"], td["vehicle_capacity"].reshape(-1)
+        s = b // demand.shape[0]
+        if s > 1:  # multistart rows, s-major
+            demand = demand.unsqueeze(0).expand(s, *demand.shape).reshape(b, -1)
+            cap = cap if cap.shape[0] == b else cap.repeat(s)
+        demands = torch.cat((-cap[:, None], demand), 1).clone()
+        rng = torch.arange(b, device=actions.device)
+        used = torch.zeros_like(cap)
+        bad = torch.zeros(b, dtype=torch.bool, device=actions.device)
+        a_prev = None
+        for a in actions.transpose(0, 1):
+            if a_prev is not None:
+                bad |= (a_prev == 0) & (a == 0) & (demands != 0).any(-1)
+            d = torch.min(demands[rng, a], cap - used)
+            demands[rng, a] -= d
+            used = (used + d).masked_fill(a == 0, 0.0)
+            a_prev = a
+        bad |= (demands != 0).any(-1)
+        bits = bad.any().to(torch.int32) * 4  # RL4CO_EBIT_INVALID_TOUR
+        if err is not None:
+            err |= bits
+        elif int(bits.item()):
+            raise AssertionError("All demand must be satisfied")
+
+
 class CVRPTWEnv(CVRPEnv):
     """CVRP with time windows (envs/routing/cvrptw/env.py:16-199): a customer can only be entered while its window
     is open on arrival; the vehicle waits for the window to open, serves, and the clock restarts at the depot.
@@ -755,4 +826,4 @@ class PDPEnv(RL4COEnvBase):
 
 def get_env(name: str, **kw) -> RL4COEnvBase:
     return {"tsp": TSPEnv, "cvrp": CVRPEnv, "op": OPEnv, "pctsp": PCTSPEnv, "pdp": PDPEnv, "cvrptw": CVRPTWEnv,
-            "spctsp": SPCTSPEnv}[name](**kw)
+            "spctsp": SPCTSPEnv, "sdvrp": SDVRPEnv}[name](**kw)

@@ -120,8 +120,31 @@ SPECS = {s.name: s for s in (
 )}
 
 
+# Environments with a DYNAMIC embedding (zoo/am/decoder.py:142-152): the state moves the keys and values every step, so the
+# per-trajectory state tensor is also an operand of the attention. Served by the decode kernels (STREAM / LDS / WIDE) alone —
+# not by the multistart variant, the unfolded mode, the one-launch replay or the teacher kernels, whose environments are the
+# six of SPECS — hence a table of their own; `spec` resolves both.
+DYNAMIC_SPECS = {s.name: s for s in (
+    # SDVRP (sdvrp/env.py:56-123): CVRP's instance, but a visit delivers min(remaining demand, remaining capacity) and a
+    # customer stays until its demand is 0. `demand_with_depot` [B, N] is per trajectory and written by the kernels; the
+    # init embedding reads the INITIAL `demand`. Horizon: a customer visit either zeroes that customer's demand (at most
+    # n - 1 such visits, a zeroed customer is masked for good) or fills the vehicle (used = cap). After a fill, cap - used
+    # of later loads stays an exact difference of the fp32 demands delivered since the depot (Sterbenz), so each customer
+    # is the filling visit at most twice: <= 2 (n - 1) fills. At most one depot visit follows each customer visit (the
+    # depot is masked while the vehicle stands on it and a customer is feasible): <= 2 * 3 (n - 1) < 6 n steps.
+    EnvSpec("sdvrp", _lib.ENV_SDVRP, True, lambda n: 6 * n,
+            _fields("B1", ("demand_with_depot", "traj", "f32", "demand_state", "BN"),
+                    ("used_capacity", "traj", "f32", "used_capacity", "B1"),
+                    ("vehicle_capacity", "traj", "f32", "vehicle_capacity", "B1")),
+            Scalar("used_capacity", "vehicle_capacity"),
+            ("sdvrp_step", ("demand_with_depot", "used_capacity", "vehicle_capacity", "current_node", "action_mask", "done")),
+            ("locs", "demand"), features=(("demand", False),)),
+)}
+
+
 def spec(env_name: str) -> EnvSpec:
-    return SPECS[canonical_env(env_name)]
+    name = canonical_env(env_name)
+    return DYNAMIC_SPECS[name] if name in DYNAMIC_SPECS else SPECS[name]
 
 
 def rem_base(sp: EnvSpec, state: dict, b: int):

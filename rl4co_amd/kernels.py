@@ -32,7 +32,7 @@ def decode_variant(num_nodes: int, cache_dtype: torch.dtype, max_steps: int, num
                    num_instances: int | None = None, env_name: str = "tsp") -> int:
     """The RL4CO_VARIANT_* rl4co_am_decode would run for this shape (host query)."""
     a = _lib.AmDecodeArgs()
-    a.env = ENV_IDS[env_name]
+    a.env = spec(env_name).env_id
     a.N, a.max_steps, a.B = int(num_nodes), int(max_steps), int(num_trajectories)
     a.B_inst = int(num_trajectories if num_instances is None else num_instances)
     a.cache_dtype = _lib.dtype_id(cache_dtype)
@@ -114,6 +114,8 @@ def bind_env_state(a, sp: EnvSpec, state: dict, b: int, n: int) -> int:
             dims = {"N-1": (n - 1,), "N": (n,), "N2": (n, 2)}[f.shape]
             if tuple(t.shape[1:]) != dims:
                 raise ValueError(f"{f.key} must be [B_inst, {', '.join(map(str, dims))}], got {tuple(t.shape)}")
+        if f.kind == "traj" and f.shape == "BN" and tuple(t.shape) != (b, n):  # (a short row would be read and written past its end)
+            raise ValueError(f"{f.key} must be [{b}, {n}], got {tuple(t.shape)}")
         # (the replay kernel keeps the running context scalar, whichever it is, in one slot)
         running = replay and sp.scalar is not None and f.key == sp.scalar.running
         setattr(a, "scalar" if running else f.slot, t.data_ptr())
@@ -230,6 +232,24 @@ def cvrp_step(action: Tensor | None, demand: Tensor, used_capacity: Tensor, vehi
     _lib.check(st, "rl4co_cvrp_step")
 
 
+def sdvrp_step(action: Tensor | None, demand_with_depot: Tensor, used_capacity: Tensor, vehicle_capacity: Tensor,
+               current_node: Tensor, action_mask: Tensor, done: Tensor | None, err: Tensor | None = None) -> None:
+    """In-place SDVRPEnv._step + get_action_mask (sdvrp/env.py:56-123); action=None -> mask only.
+    ``demand_with_depot`` [B, N] is per trajectory and updated."""
+    mask = _u8(action_mask, "action_mask")
+    b, n = mask.shape
+    _check_rows(b, action=action, demand_with_depot=demand_with_depot, used_capacity=used_capacity,
+                vehicle_capacity=vehicle_capacity, current_node=current_node, done=done)
+    if tuple(demand_with_depot.shape) != (b, n):
+        raise ValueError(f"demand_with_depot must be [{b}, {n}], got {tuple(demand_with_depot.shape)}")
+    st = _lib.lib().rl4co_sdvrp_step(
+        _ptr(None if action is None else _dev(action, torch.int64, "action")),
+        _ptr(_dev(demand_with_depot, torch.float32, "demand_with_depot")), _ptr(_dev(used_capacity, torch.float32, "used_capacity")),
+        _ptr(_dev(vehicle_capacity, torch.float32, "vehicle_capacity")), _ptr(_dev(current_node, torch.int64, "current_node")),
+        _ptr(mask), _ptr(None if done is None else _u8(done, "done")), b, n, _ptr(err), _stream())
+    _lib.check(st, "rl4co_sdvrp_step")
+
+
 def select_start_nodes(batch: int, num_starts: int, num_loc: int, has_depot: bool, device) -> Tensor:
     """ops.py:128-161: s-major ``arange(S).repeat_interleave(B) % num_loc (+1)``."""
     out = torch.empty((batch * num_starts,), dtype=torch.int64, device=device)
@@ -312,6 +332,13 @@ def am_decode(
             a.w_cap = _ptr(_dev(cache.w_cap, torch.float32, "w_cap"))
             if sp.scalar.clock:
                 a.w_time = _ptr(_dev(cache.w_time, torch.float32, "w_time"))
+    if sp.name == "sdvrp":  # the dynamic embedding, folded to three vectors (cache.fold_dynamic)
+        if cache.unfold:
+            raise ValueError("the unfolded parity mode serves tsp / cvrp")
+        dyn = _dev(cache.dyn, torch.float32, "dyn")
+        if tuple(dyn.shape) != (3, 128):
+            raise ValueError(f"cache.dyn must be [3, 128], got {tuple(dyn.shape)}")
+        a.dyn_vectors = dyn.data_ptr()
     b_inst = bind_env_state(a, sp, state, b, n)
     assert b_inst == cache.num_instances or not sp.keys("inst"), "instance data rows must match cache instances"
     if exp_noise is not None:
@@ -483,7 +510,7 @@ def _replay_tables(sp: EnvSpec, b: int, t_len: int, n: int, dev) -> dict:
 
 
 def env_replay_stepwise(env_name: str, state: dict, actions: Tensor, rem_base: Tensor | None, err: Tensor | None = None,
-                        mask_bits: bool = False) -> dict:
+                        mask_bits: bool = False, record: str | None = None) -> dict:
     """``env_replay``'s tables from ``T`` calls of the step entry, tabulated in between (what the kernel loops on the
     device): the tests' cross-check of the one-launch form, and its stand-in where a test plays the device."""
     assert not mask_bits, "the mask bits come from the one-launch form only"
@@ -491,7 +518,11 @@ def env_replay_stepwise(env_name: str, state: dict, actions: Tensor, rem_base: T
     b, t_len = actions.shape
     out = _replay_tables(sp, b, t_len, state["action_mask"].shape[1], actions.device)
     err = new_error_word(actions.device) if err is None else err
+    if record is not None:  # a state tensor the decoder read besides the context (SDVRP: the remaining demands)
+        out[record] = torch.empty((b, t_len, *state[record].shape[1:]), dtype=state[record].dtype, device=actions.device)
     for t in range(t_len):
+        if record is not None:
+            out[record][:, t] = state[record]
         out["masks"][:, t] = state["action_mask"]
         out["prev"][:, t] = state["current_node"]
         if sp.ctx_first:

@@ -358,7 +358,7 @@ class AttentionModelEncoder(nn.Module):
         super().__init__()
         self.env_name = env_name = canonical_env(env_name)
         self.init_embedding = {"tsp": _TSPInit, "cvrp": _VRPInit, "op": _OPInit, "pctsp": _PCTSPInit,
-                               "pdp": _PDPInit, "cvrptw": _VRPTWInit}[env_name](embed_dim)
+                               "pdp": _PDPInit, "cvrptw": _VRPTWInit, "sdvrp": _VRPInit}[env_name](embed_dim)
         self.net = _GraphAttentionNetwork(num_heads, embed_dim, num_layers, normalization, feedforward_hidden)
 
     def forward(self, td):
@@ -383,6 +383,14 @@ class _VRPContext(nn.Module):
         self.project_context = nn.Linear(embed_dim + 1, embed_dim, bias=False)
 
 
+class _SDVRPDynamic(nn.Module):
+    """env_embeddings/dynamic.py:60-78 — parameters only; the kernel adds d_j (x . u) (cache.fold_dynamic)."""
+
+    def __init__(self, embed_dim):
+        super().__init__()
+        self.projection = nn.Linear(1, 3 * embed_dim, bias=False)
+
+
 class _Pointer(nn.Module):
     """nn/attention.py:218-320 PointerAttention: holds ``project_out``."""
 
@@ -403,8 +411,9 @@ class AttentionModelDecoder(nn.Module):
         self.mask_inner = mask_inner
         self.check_nan = check_nan
         self.context_embedding = {"tsp": _TSPContext, "cvrp": _VRPContext, "op": _VRPContext, "pctsp": _VRPContext,
-                                  "pdp": _NodeContext, "cvrptw": _VRPTWContext}[env_name](embed_dim)
-        self.dynamic_embedding = nn.Module()  # StaticEmbedding (dynamic.py:47-57): no parameters
+                                  "pdp": _NodeContext, "cvrptw": _VRPTWContext, "sdvrp": _VRPContext}[env_name](embed_dim)
+        # StaticEmbedding (dynamic.py:47-57): no parameters; SDVRP: Linear(1 -> 3 * 128) on the remaining demand
+        self.dynamic_embedding = _SDVRPDynamic(embed_dim) if env_name == "sdvrp" else nn.Module()
         self.pointer = _Pointer(embed_dim)
         self.project_node_embeddings = nn.Linear(embed_dim, 3 * embed_dim, bias=False)
         self.project_fixed_context = nn.Linear(embed_dim, embed_dim, bias=False)
@@ -423,6 +432,7 @@ class AttentionModelDecoder(nn.Module):
             cache_dtype=cache_dtype,
             gemm_dtype=gemm_dtype,
             fold=fold,
+            w_dyn=getattr(getattr(self.dynamic_embedding, "projection", None), "weight", None),
         )
 
 
@@ -896,7 +906,7 @@ class AttentionModelPolicy(nn.Module):
         # possible rollout and trailing zeros would change the association of the reference-ordered sums, so the kernel
         # takes the real horizon from the device (the decode launch's own step count, kernels.tour_length(horizon=))
         td_early = reward_early = None
-        if (native_env and self.env_name in ("tsp", "pdp", "cvrp", "cvrptw") and calc_reward and mode != "evaluate"
+        if (native_env and self.env_name in ("tsp", "pdp", "cvrp", "cvrptw", "sdvrp") and calc_reward and mode != "evaluate"
                 and (checked or not env.check_solution) and not (n_rep > 0 and select_best)
                 and env.accepts_reward_horizon()):
             td_early = self._final_td(td, state, n_rep)
@@ -1017,7 +1027,8 @@ class AttentionModelPolicy(nn.Module):
                 from . import _lib as _l
 
                 t_max = __import__("rl4co_amd.teacher", fromlist=["max_nodes"]).max_nodes()
-                why = ("fold=False keeps the reference's per-step association, which the backward kernels do not implement" if not self.fold else
+                why = ("the dynamic embedding (remaining demand in keys and values) is not in the backward kernels" if self.env_name == "sdvrp" else
+                       "fold=False keeps the reference's per-step association, which the backward kernels do not implement" if not self.fold else
                        f"{n} nodes are beyond the kernels' limit ({t_max})" if n > t_max else
                        f"{cache_dtype} planes are not served by the backward kernels (float32, bfloat16 or float16 planes) for this call")
                 _l.warn_fallback(f"teacher/{self.env_name}/{n}/{cache_dtype}",
@@ -1137,9 +1148,14 @@ class AttentionModelPolicy(nn.Module):
         # 16-bit regime on the GPU: the masked glimpse attention of all steps on csrc/am_cross_attn.hip (keys shared by the
         # starts of an instance, the mask as bits from the same replay launch); otherwise torch's SDPA in fp32
         regime = self._encoder_regime()
+        dynamic = self.env_name == "sdvrp"  # keys and values move with the state: torch, in the reference's association
         glimpse_kernel = (hidden.is_cuda and regime in (torch.bfloat16, torch.float16) and dec.mask_inner and dec.num_heads == 8
-                          and d == 128 and self.fused_backward)
-        masks, ctx_nodes, extras, mask_bits = self._replay(td, actions, n_rep, mask_bits=glimpse_kernel)
+                          and d == 128 and self.fused_backward and not dynamic)
+        if dynamic:
+            masks, ctx_nodes, extras, demands = self._replay_by(K.env_replay_stepwise, td, actions, n_rep, False, record="demand_with_depot")
+            mask_bits = None
+        else:
+            masks, ctx_nodes, extras, mask_bits = self._replay(td, actions, n_rep, mask_bits=glimpse_kernel)
         h = hidden if s == 1 else hidden.unsqueeze(0).expand(s, b_inst, n, d).reshape(b, n, d)
         w_ctx = dec.context_embedding.project_context.weight
         sp = spec(self.env_name)
@@ -1164,6 +1180,19 @@ class AttentionModelPolicy(nn.Module):
         kvl = kvl_inst if s == 1 else kvl_inst.unsqueeze(0).expand(s, b_inst, n, 3 * d).reshape(b, n, 3 * d)
         k_g, v_g, k_l = kvl.chunk(3, dim=-1)
         nh = dec.num_heads
+        if dynamic:
+            # zoo/am/decoder.py:142-152: (K, V, L) + projection(remaining demand, the depot's taken as 0), per step
+            dem = demands.clone()
+            dem[..., 0] = 0
+            dk, dv, dl = dec.dynamic_embedding.projection(dem[..., None]).chunk(3, dim=-1)  # [B, T, N, 128] each
+            split = lambda x: x.view(b, t_len, n, nh, d // nh).transpose(2, 3)  # noqa: E731
+            kh, vh, k_lt = split(k_g[:, None] + dk), split(v_g[:, None] + dv), k_l[:, None] + dl
+            attn_mask = masks[:, :, None, None, :] if dec.mask_inner else None
+            heads = F.scaled_dot_product_attention(q.view(b, t_len, nh, 1, d // nh), kh, vh, attn_mask=attn_mask).reshape(b, t_len, d)
+            glimpse = dec.pointer.project_out(heads)
+            logits = torch.matmul(k_lt, glimpse[..., None]).squeeze(-1) / math.sqrt(d)
+            return self._logits_to_step_logps(logits, masks, actions, tanh_clipping, temperature, mask_logits, kept_bits,
+                                              skip_first, return_full)
         heads = None
         if glimpse_kernel:
             from . import train_ops
@@ -1196,6 +1225,13 @@ class AttentionModelPolicy(nn.Module):
                 step_logps = torch.cat([torch.zeros_like(step_logps[:, :1]), step_logps[:, 1:]], 1)
             return step_logps
         logits = torch.bmm(glimpse, k_l.transpose(1, 2)) / math.sqrt(d)
+        return self._logits_to_step_logps(logits, masks, actions, tanh_clipping, temperature, mask_logits, kept_bits, skip_first,
+                                          return_full)
+
+    @staticmethod
+    def _logits_to_step_logps(logits, masks, actions, tanh_clipping, temperature, mask_logits, kept_bits, skip_first, return_full):
+        """utils/decoding.py:138-188 on the [B, T, N] logits of a re-evaluation, and the given actions' log-probs."""
+        n = logits.shape[-1]
         if tanh_clipping > 0:
             logits = torch.tanh(logits) * tanh_clipping
         if mask_logits:
@@ -1222,9 +1258,16 @@ class AttentionModelPolicy(nn.Module):
         cross-check of the one-launch form."""
         return self._replay_by(K.env_replay_stepwise, td, actions, n_rep, False)
 
-    def _replay_by(self, replay, td, actions: Tensor, n_rep: int, mask_bits: bool):
+    def _replay_by(self, replay, td, actions: Tensor, n_rep: int, mask_bits: bool, record: str | None = None):
+        """``record``: a per-trajectory state key tabulated per step too ([B, T, ...] before each step; the stepwise form) —
+        returned in the mask bits' place."""
         sp = spec(self.env_name)
         state = self._initial_state(td, n_rep)
+        if record is not None:
+            r = replay(self.env_name, state, actions.contiguous(), rem_base(sp, state, actions.shape[0]),
+                       K.new_error_word(actions.device), record=record)
+            extras = None if sp.scalar is None else r["rem"]
+            return r["masks"], (r["prev"],), extras, r[record]
         r = replay(self.env_name, state, actions.contiguous(), rem_base(sp, state, actions.shape[0]),
                    K.new_error_word(actions.device), mask_bits=mask_bits)
         if sp.ctx_first:
