@@ -39,8 +39,10 @@ extern "C" {
  *  13: rl4co_am_decode_args ends in the top-k / top-p filter (top_k, top_p) and its optional kept-set output
  *      (kept_bits, kept_words); zero-initialised = no filter.
  *  14: rl4co_am_decode_args carries the split-delivery VRP's dynamic-embedding vectors and per-trajectory remaining
- *      demand (dyn_vectors, demand_state, behind w_time); rl4co_sdvrp_step. */
-#define RL4CO_ABI_VERSION 14
+ *      demand (dyn_vectors, demand_state, behind w_time); rl4co_sdvrp_step.
+ *  15: rl4co_am_decode_args carries the multi-agent TSP's folded context table and agent counts (mtsp_ctx, num_agents,
+ *      behind err); rl4co_mtsp_step. */
+#define RL4CO_ABI_VERSION 15
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -78,6 +80,10 @@ extern "C" {
  * the keys and values every step). Decode only — STREAM / LDS / WIDE; not the multistart variant, the unfolded mode, the
  * replay or the teacher kernels, whose six environments are the ids above. */
 #define RL4CO_ENV_SDVRP (RL4CO_ENV_CVRPTW + 1)
+/* Multi-agent TSP, min-max (envs/routing/mtsp/env.py): up to num_agents subtours from the depot (node 0), the reward is the
+ * longest subtour and is carried in the state. Decode only — STREAM / LDS / WIDE; not the multistart variant, the unfolded
+ * mode, the replay or the teacher kernels. */
+#define RL4CO_ENV_MTSP (RL4CO_ENV_CVRPTW + 2)
 
 #define RL4CO_DECODE_GREEDY 0   /* utils/decoding.py:387-397 */
 #define RL4CO_DECODE_SAMPLE 1   /* utils/decoding.py:399-413 */
@@ -174,6 +180,12 @@ int rl4co_tsp_step(const int64_t* action, uint8_t* action_mask, int64_t* first_n
 /* In-place SDVRPEnv._step + get_action_mask (sdvrp/env.py:56-123); action == NULL: mask only. demand_with_depot [B,N]. */
 int rl4co_sdvrp_step(const int64_t* action, float* demand_with_depot, float* used_capacity, const float* vehicle_capacity,
                      int64_t* current_node, uint8_t* action_mask, uint8_t* done, int B, int N, int32_t* err, void* stream);
+
+/* In-place MTSPEnv._step (mtsp/env.py:63-131; the mask is the state); locs [B_inst,N,2], num_agents [B_inst] (trajectory b
+ * reads row b % B_inst); agent_idx i64 [B], current_length / max_subtour_length f32 [B]. */
+int rl4co_mtsp_step(const int64_t* action, const float* locs, const int64_t* num_agents, int64_t* agent_idx,
+                    float* current_length, float* max_subtour_length, int64_t* current_node, uint8_t* action_mask,
+                    uint8_t* done, int B, int B_inst, int N, int32_t* err, void* stream);
 
 int rl4co_cvrp_step(const int64_t* action, const float* demand, float* used_capacity,
                     const float* vehicle_capacity, uint8_t* visited, int64_t* current_node,
@@ -418,6 +430,12 @@ typedef struct rl4co_am_decode_args {
                              * roofline in bench.py. 64 bits: 409 600 trajectories x 5050 rows already reach 2.07e9.
                              * A misaligned pointer is refused (RL4CO_STATUS_INVALID_ARGUMENT)                       */
   int32_t* err;             /* sticky error bits                                           */
+  /* MTSP (envs/routing/mtsp/env.py): locs as OP; agent_idx in step_i, current_length in used_capacity, max_subtour_length
+   * in current_time, all [B], read and written. The context W_ctx [h_cur ; W_dyn f] of the four running scalars
+   * f = (num_agents - agent_idx, current_length, max_subtour_length, |loc_cur - loc_0|) (env_embeddings/context.py:246-280)
+   * travels folded: q = ctx_cur[cur] + sum_k f_k g_k */
+  const float* mtsp_ctx;     /* [4,128] fp32 whatever the planes: g = W_ctx[:, 128:] W_dyn, row k for f_k */
+  const int64_t* num_agents; /* [B_inst]                                                     */
   /* (r06) the folded context tables in the element type of the planes: ctx_dtype = RL4CO_DT_BF16 / _F16 (0 = RL4CO_DT_F32,
    * the default) with their own strides in ELEMENTS (0 = dense: row 128, instance N * 128) — e.g. columns 3 and 4 of the
    * ONE [B_inst * N, 5 * 128] 16-bit matrix a fused cache-fold GEMM writes (row stride 640): no fp32 copies of the tables.

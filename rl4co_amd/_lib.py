@@ -12,8 +12,8 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 14  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
-ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP = 0, 1, 2, 3, 4, 5, 6
+ABI_VERSION = 15  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 VARIANT_AUTO, VARIANT_STREAM, VARIANT_LDS, VARIANT_WIDE, VARIANT_MS = 0, 1, 2, 3, 4
@@ -80,6 +80,7 @@ class AmDecodeArgs(C.Structure):
         ("t0", _i32), ("out_stride", _i32),
         ("actions", _vp), ("logps", _vp), ("all_logps", _vp), ("entropy", _vp),
         ("n_steps", _vp), ("steps_summary", _vp), ("err", _vp),
+        ("mtsp_ctx", _vp), ("num_agents", _vp),
         ("ctx_dtype", _i32), ("reserved0", _i32), ("ctx_row_stride", _i64), ("ctx_batch_stride", _i64),
         ("top_k", _i32), ("top_p", _f32), ("kept_bits", _vp), ("kept_words", _i32), ("reserved1", _i32),
     ]
@@ -124,6 +125,7 @@ SYMBOLS = {
     "rl4co_tsp_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_cvrp_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_sdvrp_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "rl4co_mtsp_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_op_max_length": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_op_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_gather_sum_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),

@@ -49,6 +49,8 @@ class FoldedCache:
     w_time: Tensor | None = None  # [128] fp32 (CVRPTW: W_ctx[:, 129], the current-time column)
     # SDVRP: the dynamic embedding's three vectors (u_k, u_v, W_out^T u_l), fp32 whatever the planes (fold_dynamic)
     dyn: Tensor | None = None  # [3, 128] fp32
+    # mTSP: the four running scalars' folded context vectors g = W_ctx[:, 128:] W_dyn, one row per scalar (fold_features)
+    feat: Tensor | None = None  # [4, 128] fp32
     # "unfolded" parity mode (build_folded_cache(fold=False), TSP / CVRP): plane 2 of `kvl` is the RAW logit key and
     # the three batch-shared matrices are applied per decode step in the reference's association
     unfold: bool = False
@@ -57,7 +59,7 @@ class FoldedCache:
     w_out_t: Tensor | None = None        # [128, 128] fp32 project_out.weight^T
     w_placeholder: Tensor | None = None  # [256] fp32 (TSP)
 
-    TENSOR_FIELDS = ("kvl", "ctx_first", "ctx_cur", "q_bias", "q_step0", "w_cap", "w_time", "dyn", "node_embed", "w_ctx_t",
+    TENSOR_FIELDS = ("kvl", "ctx_first", "ctx_cur", "q_bias", "q_step0", "w_cap", "w_time", "dyn", "feat", "node_embed", "w_ctx_t",
                      "w_out_t", "w_placeholder")
 
     def to(self, device) -> "FoldedCache":
@@ -92,7 +94,7 @@ def fold_weights(env_name: str, w_node: Tensor, w_out: Tensor, w_ctx: Tensor) ->
     wl_folded = w_out.t() @ wl  # logits = heads^T W_out^T (Wl h_j)
     if env_name == "tsp":
         return [wk, wv, wl_folded, w_ctx[:, :d], w_ctx[:, d : 2 * d]]
-    if env_name in ("cvrp", "op", "pctsp", "pdp", "cvrptw", "sdvrp"):  # current-node embedding (+ one scalar: capacity / remaining length / prize)
+    if env_name in ("cvrp", "op", "pctsp", "pdp", "cvrptw", "sdvrp", "mtsp"):  # current-node embedding (+ scalars: capacity / remaining length / prize; mtsp: fold_features)
         return [wk, wv, wl_folded, w_ctx[:, :d]]
     raise ValueError(f"fused decode supports tsp/cvrp/op, got {env_name!r}")
 
@@ -104,6 +106,15 @@ def fold_dynamic(w_dyn: Tensor, w_out: Tensor) -> Tensor:
     logit-key plane (``fold_weights``)."""
     u = w_dyn.detach().float().reshape(3, EMBED_DIM)
     return torch.stack((u[0], u[1], torch.mv(w_out.detach().float().t(), u[2]))).contiguous()
+
+
+def fold_features(w_ctx: Tensor, w_feat: Tensor) -> Tensor:
+    """mTSP's context ``project_context([h_cur ; proj_dynamic_feats(f)])`` (env_embeddings/context.py:246-280) is linear in
+    the four running scalars f: ``W_ctx[:, :128] h_cur + sum_k f_k g_k`` with ``g = W_ctx[:, 128:] W_dyn`` — [4, 128] fp32,
+    row k the vector of scalar k (computed in fp64, rounded once)."""
+    d = EMBED_DIM
+    g = w_ctx.detach().double()[:, d : 2 * d] @ w_feat.detach().double()  # [128, 4]
+    return g.t().float().contiguous()
 
 
 def _fold_tables_f32(h: Tensor, blocks: list[Tensor], w_fixed: Tensor | None):
@@ -140,6 +151,7 @@ def build_folded_cache(
     gemm_dtype: torch.dtype = torch.float32,
     fold: bool = True,
     w_dyn: Tensor | None = None,
+    w_feat: Tensor | None = None,
 ) -> FoldedCache:
     """One ``[B*N,128] x [128,128]`` GEMM per plane, written straight into its plane of the
     plane-major cache (no permute/cast copies), plus a GEMV for the graph context.
@@ -203,4 +215,9 @@ def build_folded_cache(
         if w_dyn is None:
             raise ValueError("sdvrp needs the dynamic embedding's weight (decoder.dynamic_embedding.projection.weight)")
         dyn = fold_dynamic(w_dyn, w_out)
-    return FoldedCache(env_name, kvl, ctx_first, ctx_cur, q_bias, q_step0, w_cap, w_time, dyn)
+    feat = None
+    if env_name == "mtsp":
+        if w_feat is None:
+            raise ValueError("mtsp needs the running scalars' weight (decoder.context_embedding.proj_dynamic_feats.weight)")
+        feat, w_cap, w_time = fold_features(w_ctx, w_feat), None, None  # (columns 128.. of W_ctx are not scalar columns here)
+    return FoldedCache(env_name, kvl, ctx_first, ctx_cur, q_bias, q_step0, w_cap, w_time, dyn, feat)

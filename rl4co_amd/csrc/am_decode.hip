@@ -69,6 +69,15 @@
 //                 used = (used + delivered) * (a != 0) ; d[a] = d[a] - delivered ; done = no d_j > 0 ; customer j masked
 //                 iff d_j == 0 or used >= cap ; depot masked iff cur == 0 and some customer is feasible. The list holds
 //                 every feasible node every step (a customer comes back until it is served): no row cache.
+//   MTSP        = (env_embeddings/context.py:246-280, envs/routing/mtsp/env.py:63-131) min-max multi-agent TSP. The context is
+//                 W_ctx [h_cur ; W_dyn f] with f = (num_agents - agent_idx, current_length, max_subtour_length,
+//                 |loc_cur - loc_0|); with g = W_ctx[:, 128:] W_dyn the batch-shared fp32 [4,128] table, per dim:
+//                 q = (fmaf(g3, f3, fmaf(g2, f2, fmaf(g1, f1, fmaf(g0, f0, ctx_cur[cur])))) + q_bias) * 0.25 — elementwise,
+//                 the same chain in every variant. Pass 2 keeps the SDVRP build's 16 row groups (16-bit planes), so STREAM,
+//                 LDS and WIDE agree bit for bit. State, one rounding each, dist = sqrt(fma(dy, dy, dx * dx)) as OP:
+//                 avail[a] = 0 ; avail[0] = a != 0 and agent_idx < num_agents - 1 ; done = no customer available ;
+//                 avail[0] |= done ; len = len + dist(a, prev) ; if done: len = len + dist(a, depot) ;
+//                 max = len > max ? len : max ; agent_idx += (a == 0) ; len = len * (a != 0). The trajectory ends AT done.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -319,7 +328,33 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
   wave_lds_sync();
 
   // ---- environment transition -------------------------------------------------------
-  if (ENV == RL4CO_ENV_TSP) {
+  if constexpr (ENV == RL4CO_ENV_MTSP) {  // (discarded in every other instantiation: their code is what it was)
+    // min-max multi-agent TSP (mtsp/env.py:63-131); st.used = current_length, st.time = max_subtour_length, st.step_i =
+    // agent_idx, oplocs = coordinates (depot row 0), mk = the reference's `available`
+    const long long nag = a.num_agents[r % a.B_inst];
+    const float px = oplocs[2 * st.cur], py = oplocs[2 * st.cur + 1];
+    const float bx = oplocs[2 * bi], by = oplocs[2 * bi + 1];
+    const bool depot_open = (bi != 0) && (st.step_i < nag - 1);  // mtsp/env.py:86-88 (agent_idx before the step)
+    if (lane == 0) mk[bi] = 0;
+    wave_lds_sync();
+    bool left = false;
+    for (int j = lane; j < N; j += 64) left |= (j >= 1) && mk[j] != 0;
+    st.done = !__any(left);                                      // mtsp/env.py:91
+    if (lane == 0) mk[0] = (depot_open || st.done) ? 1 : 0;      // mtsp/env.py:94
+    float len;
+    {
+      const float dx = bx - px, dy = by - py;
+      len = st.used + sqrtf(fmaf(dy, dy, dx * dx));              // mtsp/env.py:97
+    }
+    if (st.done) {
+      const float dx = bx - oplocs[0], dy = by - oplocs[1];
+      len = len + sqrtf(fmaf(dy, dy, dx * dx));                  // mtsp/env.py:100-102
+    }
+    st.time = len > st.time ? len : st.time;                     // mtsp/env.py:105-109
+    st.step_i += (bi == 0) ? 1 : 0;                              // mtsp/env.py:77
+    st.used = len * (bi != 0 ? 1.0f : 0.0f);                     // mtsp/env.py:112
+    st.cur = bi;
+  } else if (ENV == RL4CO_ENV_TSP) {
     if (st.step_i == 0) st.first = bi;  // tsp/env.py:63
     st.cur = bi;
     if (lane == 0) mk[bi] = 0;
@@ -484,7 +519,8 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   constexpr int LPH = kDH / EPL;  // lanes per head
   constexpr bool kRowCache = !UNFOLD && (ENV == RL4CO_ENV_TSP || ENV == RL4CO_ENV_CVRP);
   constexpr bool kDyn = ENV == RL4CO_ENV_SDVRP;            // dynamic embedding: d_j * (x . u) joins every dot product
-  constexpr int NG = (kDyn && RPL == 4) ? kUnroll : 1;     // accumulator sets of pass 2 (SDVRP, 16-bit planes: one per load)
+  constexpr bool kMtsp = ENV == RL4CO_ENV_MTSP;            // four running scalars in the context, min-max state
+  constexpr int NG = ((kDyn || kMtsp) && RPL == 4) ? kUnroll : 1;  // accumulator sets of pass 2 (SDVRP / MTSP, 16-bit planes: one per load)
   // the tree below spells out four loads of four rows: the four-wave kernels' 4 waves x 4 rows, entry c -> group c % 16
   static_assert(NG == 1 || (kUnroll == 4 && kLdsWaves == 4 && kLdsGroups == 16), "SDVRP: STREAM must keep the LDS / WIDE summation tree");
   using elem = typename C::elem;
@@ -522,7 +558,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   // ---- load the trajectory state ---------------------------------------------------
   uint8_t* gmask = a.action_mask + (int64_t)r * N;
   for (int j = lane; j < Np; j += 64) mk[j] = (j < N) ? gmask[j] : (uint8_t)0;
-  constexpr bool kScalarCtx = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_PCTSP || ENV == RL4CO_ENV_CVRPTW || kDyn;
+  constexpr bool kScalarCtx = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_PCTSP || ENV == RL4CO_ENV_CVRPTW || kDyn || kMtsp;
   constexpr bool kCvrpLike = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_CVRPTW;
   if (ENV == RL4CO_ENV_PDP) {  // bit 0 = available, bit 1 = to_deliver
     const uint8_t* gv = a.visited + (int64_t)r * N;
@@ -531,7 +567,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   } else if (kDyn) {
     const float* gd = a.demand_state + (int64_t)r * N;
     for (int j = lane; j < Np; j += 64) dd[j] = (j < N) ? gd[j] : 0.0f;
-  } else if (ENV != RL4CO_ENV_TSP) {
+  } else if (ENV != RL4CO_ENV_TSP && !kMtsp) {  // (MTSP: the mask is the state, as in TSP)
     const uint8_t* gv = a.visited + (int64_t)r * N;
     for (int j = lane; j < Np; j += 64) vis[j] = (j < N) ? gv[j] : (uint8_t)1;
   }
@@ -539,12 +575,12 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   st.cur = (int)a.current_node[r];
   st.first = (ENV == RL4CO_ENV_TSP) ? (int)a.first_node[r] : 0;
   st.step_i = !(kCvrpLike || kDyn) ? a.step_i[r] : 0;
-  st.time = (ENV == RL4CO_ENV_CVRPTW) ? a.current_time[r] : 0.0f;
-  st.used = kScalarCtx ? a.used_capacity[r] : 0.0f;  // OP: tour length so far
+  st.time = (ENV == RL4CO_ENV_CVRPTW || kMtsp) ? a.current_time[r] : 0.0f;  // MTSP: max_subtour_length
+  st.used = kScalarCtx ? a.used_capacity[r] : 0.0f;  // OP: tour length so far; MTSP: current_length
   st.done = a.done[r] != 0;
   st.errbits = 0;
   st.ent_acc = 0.0f;
-  const float* oplocs = (ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_CVRPTW) ? a.locs + (int64_t)cb * N * 2 : nullptr;
+  const float* oplocs = (ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_CVRPTW || kMtsp) ? a.locs + (int64_t)cb * N * 2 : nullptr;
   const float* opmax = (ENV == RL4CO_ENV_OP)       ? a.max_length + (int64_t)cb * N
                        : (ENV == RL4CO_ENV_CVRPTW) ? a.time_windows + (int64_t)cb * N * 2  // (start, end) per node
                                                    : nullptr;
@@ -593,6 +629,8 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   for (int e = 0; e < EPL; ++e) qb[e] = a.q_bias ? a.q_bias[(int64_t)cb * kD + e0 + e] : 0.0f;
 
   const float* dynv = kDyn ? a.dyn_vectors + e0 : nullptr;  // (u_k, u_v, u_l') [3,128]: this lane's EPL dims of each
+  const float* mg = kMtsp ? a.mtsp_ctx + e0 : nullptr;      // MTSP: g [4,128], this lane's EPL dims of each row
+  const long long nag = kMtsp ? a.num_agents[cb] : 0;
   const bool single = a.max_steps == 1;
   int t = 0;
   int rows_read = 0;  // cache rows this trajectory streamed from HBM (x 3 planes): the launch's real HBM read volume
@@ -640,6 +678,20 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
 #pragma unroll
       for (int e = 0; e < EPL; ++e) q[e] = q[e] + qb[e];
       wave_lds_sync();  // cv is overwritten by this step's scores
+    } else if constexpr (kMtsp) {  // context.py:246-280, folded: ctx_cur[cur] + sum_k f_k g_k
+      const float f0 = (float)(nag - st.step_i);
+      const float ddx = oplocs[2 * st.cur] - oplocs[0], ddy = oplocs[2 * st.cur + 1] - oplocs[1];
+      const float f3 = sqrtf(fmaf(ddy, ddy, ddx * ddx));
+      float cc[EPL];
+      ctx.load(ctx.cur, st.cur, cc);
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) {
+        float v = fmaf(mg[e], f0, cc[e]);
+        v = fmaf(mg[kD + e], st.used, v);
+        v = fmaf(mg[2 * kD + e], st.time, v);
+        v = fmaf(mg[3 * kD + e], f3, v);
+        q[e] = v + qb[e];
+      }
     } else if (ENV == RL4CO_ENV_TSP) {
       if (st.step_i < 1) {  // context.py:120 placeholder context
 #pragma unroll
@@ -864,7 +916,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   } else if (kDyn) {
     float* gd = a.demand_state + (int64_t)r * N;
     for (int j = lane; j < N; j += 64) gd[j] = dd[j];
-  } else if (ENV != RL4CO_ENV_TSP) {
+  } else if (ENV != RL4CO_ENV_TSP && !kMtsp) {
     uint8_t* gv = a.visited + (int64_t)r * N;
     for (int j = lane; j < N; j += 64) gv[j] = vis[j];
   }
@@ -873,7 +925,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
     a.done[r] = st.done ? 1 : 0;
     if (ENV == RL4CO_ENV_TSP) a.first_node[r] = st.first;
     if (!(kCvrpLike || kDyn)) a.step_i[r] = st.step_i;
-    if (ENV == RL4CO_ENV_CVRPTW) a.current_time[r] = st.time;
+    if (ENV == RL4CO_ENV_CVRPTW || kMtsp) a.current_time[r] = st.time;
     if (kScalarCtx) a.used_capacity[r] = st.used;
     if (a.n_steps) a.n_steps[r] = t;
     if (a.steps_summary) {
@@ -1029,6 +1081,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   uint8_t* vis = mk + nw;                                           // [nw] CVRP visited
   float* dd = reinterpret_cast<float*>(vis + nw);                   // [nw] SDVRP: remaining demands
   constexpr bool kDyn = ENV == RL4CO_ENV_SDVRP;
+  constexpr bool kMtsp = ENV == RL4CO_ENV_MTSP;
 
   const int cb = r % a.B_inst;
   const int rg = lane / LPR, li = lane % LPR, hd = li / LPH, e0 = li * EPL;
@@ -1067,7 +1120,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   }
   // ---- trajectory state: the same six environments as the streaming kernel (wave 0 owns the transition, the other
   // waves receive the scalars it changes through LDS after every step) ----------------------------------------------
-  constexpr bool kScalarCtx = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_PCTSP || ENV == RL4CO_ENV_CVRPTW || kDyn;
+  constexpr bool kScalarCtx = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_PCTSP || ENV == RL4CO_ENV_CVRPTW || kDyn || kMtsp;
   constexpr bool kCvrpLike = ENV == RL4CO_ENV_CVRP || ENV == RL4CO_ENV_CVRPTW;
   uint8_t* gmask = a.action_mask + (int64_t)r * N;
   for (int j = tid; j < nw; j += 64 * kLdsWaves) mk[j] = (j < N) ? gmask[j] : (uint8_t)0;
@@ -1079,7 +1132,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   } else if (kDyn) {
     const float* gd = a.demand_state + (int64_t)r * N;
     for (int j = tid; j < nw; j += 64 * kLdsWaves) dd[j] = (j < N) ? gd[j] : 0.0f;
-  } else if (ENV != RL4CO_ENV_TSP) {
+  } else if (ENV != RL4CO_ENV_TSP && !kMtsp) {
     const uint8_t* gv = a.visited + (int64_t)r * N;
     for (int j = tid; j < nw; j += 64 * kLdsWaves) vis[j] = (j < N) ? gv[j] : (uint8_t)1;
   }
@@ -1087,12 +1140,12 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   st.cur = (int)a.current_node[r];
   st.first = (ENV == RL4CO_ENV_TSP) ? (int)a.first_node[r] : 0;
   st.step_i = !(kCvrpLike || kDyn) ? a.step_i[r] : 0;
-  st.time = (ENV == RL4CO_ENV_CVRPTW) ? a.current_time[r] : 0.0f;
+  st.time = (ENV == RL4CO_ENV_CVRPTW || kMtsp) ? a.current_time[r] : 0.0f;  // MTSP: max_subtour_length
   st.used = kScalarCtx ? a.used_capacity[r] : 0.0f;  // OP: tour length so far; PCTSP: prize collected
   st.done = a.done[r] != 0;
   st.errbits = 0;
   st.ent_acc = 0.0f;
-  const float* oplocs = (ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_CVRPTW) ? a.locs + (int64_t)cb * N * 2 : nullptr;
+  const float* oplocs = (ENV == RL4CO_ENV_OP || ENV == RL4CO_ENV_CVRPTW || kMtsp) ? a.locs + (int64_t)cb * N * 2 : nullptr;
   const float* opmax = (ENV == RL4CO_ENV_OP)       ? a.max_length + (int64_t)cb * N
                        : (ENV == RL4CO_ENV_CVRPTW) ? a.time_windows + (int64_t)cb * N * 2
                                                    : nullptr;
@@ -1113,6 +1166,8 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   for (int e = 0; e < EPL; ++e) qb[e] = a.q_bias ? a.q_bias[(int64_t)cb * kD + e0 + e] : 0.0f;
 
   const float* dynv = kDyn ? a.dyn_vectors + e0 : nullptr;  // (u_k, u_v, u_l') [3,128]: this lane's EPL dims of each
+  const float* mg = kMtsp ? a.mtsp_ctx + e0 : nullptr;      // MTSP: g [4,128], this lane's EPL dims of each row
+  const long long nag = kMtsp ? a.num_agents[cb] : 0;
   const bool single = a.max_steps == 1;
   int t = 0;
   int rows_read = 0;
@@ -1123,7 +1178,21 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
     const int iters = (F + kLdsGroups - 1) / kLdsGroups;
     // ---- query ---------------------------------------------------------------------------------
     float q[EPL];
-    if (ENV == RL4CO_ENV_TSP) {
+    if constexpr (kMtsp) {  // context.py:246-280, folded: ctx_cur[cur] + sum_k f_k g_k
+      const float f0 = (float)(nag - st.step_i);
+      const float ddx = oplocs[2 * st.cur] - oplocs[0], ddy = oplocs[2 * st.cur + 1] - oplocs[1];
+      const float f3 = sqrtf(fmaf(ddy, ddy, ddx * ddx));
+      float cc[EPL];
+      ctx.load(ctx.cur, st.cur, cc);
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) {
+        float v = fmaf(mg[e], f0, cc[e]);
+        v = fmaf(mg[kD + e], st.used, v);
+        v = fmaf(mg[2 * kD + e], st.time, v);
+        v = fmaf(mg[3 * kD + e], f3, v);
+        q[e] = v + qb[e];
+      }
+    } else if (ENV == RL4CO_ENV_TSP) {
       if (st.step_i < 1) {
 #pragma unroll
         for (int e = 0; e < EPL; ++e) q[e] = a.q_step0[e0 + e] + qb[e];
@@ -1326,7 +1395,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
     } else if (kDyn) {
       float* gd = a.demand_state + (int64_t)r * N;
       for (int j = lane; j < N; j += 64) gd[j] = dd[j];
-    } else if (ENV != RL4CO_ENV_TSP) {
+    } else if (ENV != RL4CO_ENV_TSP && !kMtsp) {
       uint8_t* gv = a.visited + (int64_t)r * N;
       for (int j = lane; j < N; j += 64) gv[j] = vis[j];
     }
@@ -1335,7 +1404,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
       a.done[r] = st.done ? 1 : 0;
       if (ENV == RL4CO_ENV_TSP) a.first_node[r] = st.first;
       if (!(kCvrpLike || kDyn)) a.step_i[r] = st.step_i;
-      if (ENV == RL4CO_ENV_CVRPTW) a.current_time[r] = st.time;
+      if (ENV == RL4CO_ENV_CVRPTW || kMtsp) a.current_time[r] = st.time;
       if (kScalarCtx) a.used_capacity[r] = st.used;
       if (a.n_steps) a.n_steps[r] = t;
       if (a.steps_summary) {
@@ -1379,7 +1448,8 @@ inline int resolve_variant(const rl4co_am_decode_args& a) {
   // multistart on the matrix cores (am_decode_ms.hip): 16-bit planes, N <= 128, plain outputs; every environment
   const bool ms_ok = bf16 && a.N <= 128 && a.B_inst > 0 && a.all_logps == nullptr && a.entropy == nullptr &&
                      !rl4co::topkp_on(a) &&           // the top-k / top-p filter is not in am_decode_ms.hip
-                     a.env != RL4CO_ENV_SDVRP;        // nor is the dynamic embedding
+                     a.env != RL4CO_ENV_SDVRP &&      // nor is the dynamic embedding
+                     a.env != RL4CO_ENV_MTSP;         // nor the four-scalar context and the min-max state
   if (a.variant == RL4CO_VARIANT_MS) return ms_ok ? RL4CO_VARIANT_MS : -1;
   const bool fits = bf16 && lds_variant_bytes(a.N) + wide_dyn_bytes(a.N, a.env) <= 80 * 1024;
   const bool wide_ok = bf16 && wide_scratch_bytes(a.N) + wide_dyn_bytes(a.N, a.env) <= 64 * 1024;
@@ -1467,7 +1537,7 @@ extern "C" int rl4co_am_decode_row_groups(const rl4co_am_decode_args* args) {
   if (v < 0) return -1;
   if (v == RL4CO_VARIANT_MS) return 0;  // bf16 MFMA variant: tolerance-tested, no specified-order oracle
   if (v == RL4CO_VARIANT_LDS || v == RL4CO_VARIANT_WIDE) return kLdsGroups;
-  if (args->env == RL4CO_ENV_SDVRP && args->cache_dtype != RL4CO_DT_F32) return kLdsGroups;  // one accumulator per load
+  if ((args->env == RL4CO_ENV_SDVRP || args->env == RL4CO_ENV_MTSP) && args->cache_dtype != RL4CO_DT_F32) return kLdsGroups;  // one accumulator per load
   return args->cache_dtype != RL4CO_DT_F32 ? 64 / (kD / CacheBF16::EPL) : 64 / (kD / CacheF32::EPL);
 }
 
@@ -1479,7 +1549,8 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
   RL4CO_REQUIRE(args != nullptr);
   const rl4co_am_decode_args& a = *args;
   RL4CO_REQUIRE(a.env == RL4CO_ENV_TSP || a.env == RL4CO_ENV_CVRP || a.env == RL4CO_ENV_OP ||
-                a.env == RL4CO_ENV_PCTSP || a.env == RL4CO_ENV_PDP || a.env == RL4CO_ENV_CVRPTW || a.env == RL4CO_ENV_SDVRP);
+                a.env == RL4CO_ENV_PCTSP || a.env == RL4CO_ENV_PDP || a.env == RL4CO_ENV_CVRPTW || a.env == RL4CO_ENV_SDVRP ||
+                a.env == RL4CO_ENV_MTSP);
   RL4CO_REQUIRE(a.B > 0 && a.B_inst > 0 && a.B % a.B_inst == 0);
   RL4CO_REQUIRE(a.N >= 2 && a.N <= 4096);
   RL4CO_REQUIRE(a.max_steps >= 1);
@@ -1519,6 +1590,8 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
   } else if (a.env == RL4CO_ENV_SDVRP) {
     RL4CO_REQUIRE(a.w_cap && a.dyn_vectors && a.demand_state && a.used_capacity && a.vehicle_capacity);
     RL4CO_REQUIRE((reinterpret_cast<uintptr_t>(a.dyn_vectors) & 15) == 0);
+  } else if (a.env == RL4CO_ENV_MTSP) {
+    RL4CO_REQUIRE(a.mtsp_ctx && a.num_agents && a.locs && a.used_capacity && a.current_time && a.step_i);
   } else if (a.env == RL4CO_ENV_PDP) {
     RL4CO_REQUIRE(a.visited && a.to_deliver && a.step_i && (a.N - 1) % 2 == 0);
   } else if (a.env == RL4CO_ENV_PCTSP) {
@@ -1547,6 +1620,7 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
       case RL4CO_ENV_PCTSP: return res ? launch_wide<RL4CO_ENV_PCTSP, true>(a, s) : launch_wide<RL4CO_ENV_PCTSP, false>(a, s);
       case RL4CO_ENV_PDP: return res ? launch_wide<RL4CO_ENV_PDP, true>(a, s) : launch_wide<RL4CO_ENV_PDP, false>(a, s);
       case RL4CO_ENV_SDVRP: return res ? launch_wide<RL4CO_ENV_SDVRP, true>(a, s) : launch_wide<RL4CO_ENV_SDVRP, false>(a, s);
+      case RL4CO_ENV_MTSP: return res ? launch_wide<RL4CO_ENV_MTSP, true>(a, s) : launch_wide<RL4CO_ENV_MTSP, false>(a, s);
       default: return res ? launch_wide<RL4CO_ENV_CVRPTW, true>(a, s) : launch_wide<RL4CO_ENV_CVRPTW, false>(a, s);
     }
   }
@@ -1558,9 +1632,12 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
       case RL4CO_ENV_PCTSP: return launch<CacheF16, RL4CO_ENV_PCTSP>(a, s);
       case RL4CO_ENV_PDP: return launch<CacheF16, RL4CO_ENV_PDP>(a, s);
       case RL4CO_ENV_SDVRP: return launch<CacheF16, RL4CO_ENV_SDVRP>(a, s);
+      case RL4CO_ENV_MTSP: return launch<CacheF16, RL4CO_ENV_MTSP>(a, s);
       default: return launch<CacheF16, RL4CO_ENV_CVRPTW>(a, s);
     }
   }
+  if (a.env == RL4CO_ENV_MTSP)
+    return a.cache_dtype == RL4CO_DT_F32 ? launch<CacheF32, RL4CO_ENV_MTSP>(a, s) : launch<CacheBF16, RL4CO_ENV_MTSP>(a, s);
   if (a.env == RL4CO_ENV_SDVRP)
     return a.cache_dtype == RL4CO_DT_F32 ? launch<CacheF32, RL4CO_ENV_SDVRP>(a, s) : launch<CacheBF16, RL4CO_ENV_SDVRP>(a, s);
   if (a.env == RL4CO_ENV_CVRPTW)

@@ -217,6 +217,65 @@ extern "C" int rl4co_sdvrp_step(const int64_t* action, float* demand_with_depot,
 }
 
 // ------------------------------------------------------------------------------------------------
+// Multi-agent TSP, min-max (envs/routing/mtsp/env.py:63-131): every line one IEEE fp32 operation, in the reference's order.
+// The mask is the state (the reference's `available`); distances as OP's below: sqrt(fma(dy, dy, dx * dx)).
+namespace {
+
+__global__ void __launch_bounds__(64) mtsp_step_kernel(const int64_t* action, const float* locs, const int64_t* num_agents,
+                                                       int64_t* agent_idx, float* current_length, float* max_subtour_length,
+                                                       int64_t* cur, uint8_t* mask, uint8_t* done, int B_inst, int N,
+                                                       int32_t* err) {
+  const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
+  const float* lc = locs + (int64_t)(b % B_inst) * N * 2;
+  uint8_t* row = mask + (int64_t)b * N;
+  int64_t a = action[b];
+  bool bad = false;
+  if (a < 0 || a >= N) {
+    bad = true;
+    a = 0;
+  }
+  int64_t c = cur[b];
+  if (c < 0 || c >= N) c = 0;
+  const int64_t agent = agent_idx[b];
+  const bool depot_open = (a != 0) && (agent < num_agents[b % B_inst] - 1);  // mtsp/env.py:86-88
+  bool left = false;
+  for (int j = lane; j < N; j += 64) left |= (j >= 1) && (j != a) && row[j] != 0;
+  const bool fin = !__any(left);                                              // mtsp/env.py:91
+  if (lane == 0) {
+    const float bx = lc[2 * a], by = lc[2 * a + 1];
+    float dx = bx - lc[2 * c], dy = by - lc[2 * c + 1];
+    float len = current_length[b] + sqrtf(fmaf(dy, dy, dx * dx));             // mtsp/env.py:97
+    if (fin) {
+      dx = bx - lc[0], dy = by - lc[1];
+      len = len + sqrtf(fmaf(dy, dy, dx * dx));                               // mtsp/env.py:100-102
+    }
+    const float mx = max_subtour_length[b];
+    max_subtour_length[b] = len > mx ? len : mx;                              // mtsp/env.py:105-109
+    agent_idx[b] = agent + (a == 0 ? 1 : 0);                                  // mtsp/env.py:77
+    current_length[b] = len * (a != 0 ? 1.0f : 0.0f);                         // mtsp/env.py:112
+    cur[b] = a;
+    done[b] = fin ? 1 : 0;
+    row[a] = 0;                                                               // mtsp/env.py:80-82
+    row[0] = (depot_open || fin) ? 1 : 0;                                     // mtsp/env.py:86-94
+    if (bad && err) atomicOr(err, RL4CO_EBIT_INFEASIBLE);
+  }
+}
+
+}  // namespace
+
+extern "C" int rl4co_mtsp_step(const int64_t* action, const float* locs, const int64_t* num_agents, int64_t* agent_idx,
+                               float* current_length, float* max_subtour_length, int64_t* current_node, uint8_t* action_mask,
+                               uint8_t* done, int B, int B_inst, int N, int32_t* err, void* stream) {
+  RL4CO_REQUIRE(action && locs && num_agents && agent_idx && current_length && max_subtour_length && current_node &&
+                action_mask && done);
+  RL4CO_REQUIRE(B > 0 && B_inst > 0 && B % B_inst == 0 && N > 1);
+  hipLaunchKernelGGL(mtsp_step_kernel, dim3(B), dim3(64), 0, rl4co::as_stream(stream), action, locs, num_agents, agent_idx,
+                     current_length, max_subtour_length, current_node, action_mask, done, B_inst, N, err);
+  RL4CO_HIP_TRY(hipGetLastError());
+  return RL4CO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Orienteering problem (envs/routing/op/env.py). Distances are (a - b).norm(p=2, dim=-1) on a size-2
 // dim, i.e. sqrt(fma(dy, dy, dx * dx)) — the arithmetic of the tour-length kernel.
 namespace {

@@ -19,7 +19,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .cache import EMBED_DIM, FoldedCache, fold_dynamic, fold_weights
+from .cache import EMBED_DIM, FoldedCache, fold_dynamic, fold_features, fold_weights
 from .envspec import customer_features, spec
 
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
@@ -99,6 +99,7 @@ class PackedEncoder:
         self.t: dict[str, Tensor] = {}
         self._tensors: list[Tensor] | None = None
         self.act_dtype = torch.bfloat16  # element type the weights are packed in (a regime switch re-packs)
+        self._zero_col: Tensor | None = None  # mTSP: the zero customer-feature column (encode)
 
     def _current_version(self):
         """Cheap change detector on the path of every rollout (it sits between the previous rollout's
@@ -139,6 +140,10 @@ class PackedEncoder:
             t["w_extra"], t["b_extra"] = f32(ie.init_embed_delivery.weight), f32(ie.init_embed_delivery.bias)
         else:
             t["w_init"], t["b_init"] = f32(ie.init_embed.weight), f32(ie.init_embed.bias)
+        if pol.env_name == "mtsp":
+            # MTSPInitEmbedding (init.py:363-379) is the VRP embedding without a customer feature: the kernels' depot |
+            # customers mode with a zero feature column against a zero weight column (x w0 + y w1 + 0 * 0: the same value)
+            t["w_init"] = torch.cat((t["w_init"], torch.zeros_like(t["w_init"][:, :1])), 1).contiguous()
         if pol.env_name != "tsp":
             t["w_depot"], t["b_depot"] = f32(ie.init_embed_depot.weight), f32(ie.init_embed_depot.bias)
         # the query rows of Wqkv (and their bias) carry head_dim^-1/2 * log2(e): the kernel's softmax is exp2(q . k)
@@ -190,6 +195,11 @@ class PackedEncoder:
         t["w_time"] = w_ctx[:, EMBED_DIM + 1].contiguous() if w_ctx.shape[1] > EMBED_DIM + 1 else None  # CVRPTW
         w_dyn = getattr(getattr(dec.dynamic_embedding, "projection", None), "weight", None)  # SDVRP
         t["dyn"] = None if w_dyn is None else fold_dynamic(w_dyn, dec.pointer.project_out.weight)
+        t["feat"] = None
+        sp = spec(pol.env_name)
+        if sp.feats is not None:  # mTSP: columns 128.. of W_ctx meet the running scalars' own layer (cache.fold_features)
+            t["feat"] = fold_features(w_ctx, getattr(dec.context_embedding, sp.feats.weight).weight)
+            t["w_cap"] = t["w_time"] = None
         self.num_layers = len(layers)
         self.t, self.version = t, ver
         return t
@@ -275,7 +285,8 @@ class PackedEncoder:
         sp = spec(pol.env_name)
         # the encoder kernels have three init-embedding modes, named by the environment that has it alone: TSP (every node
         # alike), PDP (depot | pickups | deliveries), CVRP (depot | customers with 1-4 feature columns behind x, y)
-        a.env = _lib.ENV_CVRP if sp.features else sp.env_id
+        no_feature = sp.name == "mtsp"  # depot | customers with (x, y) alone: one zero feature column (refresh: w_init)
+        a.env = _lib.ENV_CVRP if (sp.features or no_feature) else sp.env_id
         a.B, a.N, a.num_layers, a.norm = b, n, self.num_layers, self.norm_kind
         a.cache_dtype, a.act_dtype = _lib.dtype_id(cache_dtype), _lib.dtype_id(self.act_dtype)
         a.ctx_dtype = _lib.dtype_id(ctx_dt) if ctx_dt != torch.float32 else 0
@@ -286,6 +297,12 @@ class PackedEncoder:
             cols = [c.contiguous() for f in customer_features(sp, td) for c in f.unbind(-1)]
             for slot, c in zip(("demand", "feature4", "feature5", "feature6"), cols):
                 setattr(a, slot, c.data_ptr())
+            a.w_depot, a.b_depot = ptr(t["w_depot"]), ptr(t["b_depot"])
+        if no_feature:
+            zero_col = self._zero_col  # kept between calls: the kernels only read it
+            if zero_col is None or zero_col.numel() < b * (n - 1) or zero_col.device != dev:
+                zero_col = self._zero_col = torch.zeros(b * (n - 1), dtype=torch.float32, device=dev)
+            a.demand = zero_col.data_ptr()
             a.w_depot, a.b_depot = ptr(t["w_depot"]), ptr(t["b_depot"])
         if pol.env_name == "pdp":
             a.w_depot, a.b_depot = ptr(t["w_depot"]), ptr(t["b_depot"])
@@ -320,5 +337,6 @@ class PackedEncoder:
                                 w_out_t=dec.pointer.project_out.weight.detach().float().t().contiguous(),
                                 w_placeholder=None if ph is None else ph.detach().float().contiguous())
             return cache, hidden
-        cache = FoldedCache(pol.env_name, kvl, ctx_first, ctx_cur, q_bias, t["q_step0"], t["w_cap"], t["w_time"], t["dyn"])
+        cache = FoldedCache(pol.env_name, kvl, ctx_first, ctx_cur, q_bias, t["q_step0"], t["w_cap"], t["w_time"], t["dyn"],
+                            t["feat"])
         return cache, hidden

@@ -101,6 +101,22 @@ class CVRPGenerator(TSPGenerator):
         )
 
 
+class MTSPGenerator(TSPGenerator):
+    """mtsp/generator.py:14-70: ``num_loc`` uniform locations INCLUDING the depot (node 0), then the number of agents,
+    ``randint(min_num_agents, max_num_agents + 1)`` per instance on the global torch generator (the reference's stream)."""
+
+    def __init__(self, num_loc: int = 20, min_loc: float = 0.0, max_loc: float = 1.0, min_num_agents: int = 5,
+                 max_num_agents: int = 5, device="cpu", **unused):
+        super().__init__(num_loc, min_loc, max_loc, device)
+        self.min_num_agents = min_num_agents
+        self.max_num_agents = max_num_agents
+
+    def _generate(self, batch_size) -> TensorDict:
+        locs = self._uniform((*batch_size, self.num_loc, 2), self.min_loc, self.max_loc)
+        num_agents = torch.randint(self.min_num_agents, self.max_num_agents + 1, size=(*batch_size,))
+        return TensorDict({"locs": locs, "num_agents": num_agents.to(locs.device)}, batch_size=batch_size)
+
+
 class CVRPTWGenerator(CVRPGenerator):
     """cvrptw/generator.py:13-158: CVRP data (depot sampled on its own) plus integer-valued time windows inside
     [distance from the depot, max_time - distance back] and zero service times; unscaled unless ``scale``"""
@@ -528,6 +544,65 @@ class SDVRPEnv(CVRPEnv):
             raise AssertionError("All demand must be satisfied")
 
 
+class MTSPEnv(RL4COEnvBase):
+    """Multi-agent TSP with the min-max objective (envs/routing/mtsp/env.py:14-239): up to ``num_agents`` subtours from the
+    depot (node 0 of ``locs``), every customer once; the reward is minus the longest subtour and is carried in the state
+    (``max_subtour_length``). The rollout ends AT ``done`` — there is no closing depot action. ``cost_type="sum"`` is not
+    served (the reference's own form only works for rollouts of exactly ``num_loc`` steps).
+
+    As in the reference, ``get_reward`` reads the state, so it depends on how far a finished row was stepped: the first
+    step with action 0 after ``done`` adds the return leg to ``current_length`` once more before the maximum is taken
+    (mtsp/env.py:97-112). The policy's rollout applies that step to the rows that finished before the batch's longest row,
+    which is what the reference's loop does; a caller's own step loop that stops every row at its ``done`` gets the
+    unpadded value."""
+
+    name = "mtsp"
+    has_depot = True
+
+    def __init__(self, *, cost_type: str = "minmax", **kw):
+        if cost_type == "sum":
+            raise NotImplementedError('mtsp: cost_type="sum" is not served (the reference gathers `actions` with '
+                                      "expand_as(locs), which needs exactly num_loc steps); use cost_type=\"minmax\"")
+        if cost_type != "minmax":
+            raise ValueError(f"Cost type {cost_type} not supported")
+        self.cost_type = cost_type
+        super().__init__(**kw)
+
+    def _default_generator(self, **kw):
+        return MTSPGenerator(**kw)
+
+    def _reset(self, td: TensorDict, batch_size) -> TensorDict:
+        """mtsp/env.py:133-164 (+ torchrl's done flag)"""
+        locs = td["locs"].contiguous()
+        device = locs.device
+        b, n = locs.shape[0], locs.shape[-2]
+        z = _zero_state(device, agent_idx=((b,), torch.int64), max_subtour_length=((b,), torch.float32),
+                        current_length=((b,), torch.float32), first_node=((b,), torch.int64),
+                        current_node=((b,), torch.int64), i=((b,), torch.int64), done=((b, 1), torch.bool))
+        mask = torch.ones((b, n), dtype=torch.bool, device=device)
+        mask[:, 0] = False  # the depot is not available as first node
+        return TensorDict({"locs": locs, "num_agents": td["num_agents"].to(torch.int64).contiguous(), **z, "action_mask": mask},
+                          batch_size=[b])
+
+    def _step(self, td: TensorDict) -> TensorDict:
+        """mtsp/env.py:63-131 via rl4co_mtsp_step (in place); ``first_node`` / ``i`` are kept on the host side."""
+        action = td["action"].contiguous()
+        if "first_node" in td.keys() and "i" in td.keys():
+            td["first_node"].copy_(torch.where(td["i"] == 0, action, td["first_node"]))
+            td["i"].add_(1)
+        K.mtsp_step(action, td["locs"], td["num_agents"], td["agent_idx"], td["current_length"], td["max_subtour_length"],
+                    td["current_node"], td["action_mask"], td["done"])
+        td.set("reward", -td["max_subtour_length"])
+        return td
+
+    def _get_reward(self, td: TensorDict, actions: Tensor) -> Tensor:
+        """mtsp/env.py:218-221: the reward carried in the state."""
+        return -td["max_subtour_length"].reshape(-1)
+
+    def check_solution_validity(self, td: TensorDict, actions: Tensor, err: Tensor | None = None) -> None:
+        """mtsp/env.py:232-234: the reference checks nothing."""
+
+
 class CVRPTWEnv(CVRPEnv):
     """CVRP with time windows (envs/routing/cvrptw/env.py:16-199): a customer can only be entered while its window
     is open on arrival; the vehicle waits for the window to open, serves, and the clock restarts at the depot.
@@ -826,4 +901,4 @@ class PDPEnv(RL4COEnvBase):
 
 def get_env(name: str, **kw) -> RL4COEnvBase:
     return {"tsp": TSPEnv, "cvrp": CVRPEnv, "op": OPEnv, "pctsp": PCTSPEnv, "pdp": PDPEnv, "cvrptw": CVRPTWEnv,
-            "spctsp": SPCTSPEnv, "sdvrp": SDVRPEnv}[name](**kw)
+            "spctsp": SPCTSPEnv, "sdvrp": SDVRPEnv, "mtsp": MTSPEnv}[name](**kw)

@@ -19,7 +19,7 @@ class Field(NamedTuple):
     it; "inst": instance data — shared [B_inst, ...], contiguous, cast to ``dtype``. ``slot``: the field of
     ``rl4co_am_decode_args`` it rides in (the running context scalar rides in ``scalar`` of ``rl4co_env_replay_args``).
     ``shape``: "B" / "BN" as in the state; "B1": [B] in the state, [B, 1] in the final TensorDict; instance data: the
-    dims behind B_inst ("N-1" = one entry per customer)."""
+    dims behind B_inst ("N-1" = one entry per customer, "" = one value per instance)."""
     key: str
     kind: str
     dtype: str  # "i64" | "f32" | "u8" (bool or uint8: the same storage)
@@ -38,6 +38,16 @@ class Scalar(NamedTuple):
     clock: str | None = None
 
 
+class Features(NamedTuple):
+    """``Scalar``'s sibling for a context of SEVERAL running scalars behind a linear layer of their own (mTSP,
+    context.py:246-280: ``W_ctx [h_cur ; W_dyn f]``): ``names`` are the columns of ``f`` in the order of ``W_dyn``'s input —
+    state keys, or derived quantities the kernels and the stepwise replay compute ("remaining_agents" = num_agents -
+    agent_idx, "depot_distance" = |loc_cur - loc_0|). ``weight``: the layer's attribute on ``decoder.context_embedding``.
+    The fold is one fp32 [len(names), 128] table (``cache.fold_features``, ``rl4co_am_decode_args.mtsp_ctx``)."""
+    names: tuple[str, ...]
+    weight: str
+
+
 class EnvSpec(NamedTuple):
     name: str
     env_id: int  # RL4CO_ENV_* of include/rl4co_amd.h
@@ -50,6 +60,7 @@ class EnvSpec(NamedTuple):
     features: tuple[tuple[str, bool], ...] = ()  # customer init-embedding columns behind (x, y): (td key, drop the depot column)
     depot_embed: bool = True  # the depot has an init embedding of its own
     ctx_first: bool = False  # context = (first node, current node), placeholder at step 0; else current node (+ scalars)
+    feats: Features | None = None  # several running scalars through a second linear layer (instead of ``scalar``)
 
     def keys(self, kind: str | None = None) -> tuple[str, ...]:
         return tuple(f.key for f in self.fields if kind in (None, f.kind))
@@ -142,9 +153,35 @@ DYNAMIC_SPECS = {s.name: s for s in (
 )}
 
 
+# Environments whose REWARD is carried in the state (a min-max objective) and whose context holds several running scalars
+# (`Features`). Decode kernels alone, as DYNAMIC_SPECS, and with one trajectory per instance (no multistart rows).
+MINMAX_SPECS = {s.name: s for s in (
+    # mTSP (mtsp/env.py:63-131): n nodes INCLUDING the depot; up to num_agents subtours from the depot, the reward is the
+    # longest. The mask is the state (the reference's `available`). agent_idx rides in step_i, current_length in
+    # used_capacity, max_subtour_length in current_time. Horizon: n - 1 customer visits; every depot visit follows a
+    # customer visit (the depot is closed while the agent stands on it) and comes before done (the rollout ends AT done):
+    # at most 2 (n - 1) < 2 n steps.
+    EnvSpec("mtsp", _lib.ENV_MTSP, True, lambda n: 2 * n,
+            tuple(Field(*f) for f in (
+                ("action_mask", "traj", "u8", "action_mask", "BN"), ("current_node", "traj", "i64", "current_node", "B"),
+                ("done", "traj", "u8", "done", "B1"),
+                ("locs", "inst", "f32", "locs", "N2"), ("num_agents", "inst", "i64", "num_agents", ""),
+                ("agent_idx", "traj", "i64", "step_i", "B"), ("current_length", "traj", "f32", "used_capacity", "B"),
+                ("max_subtour_length", "traj", "f32", "current_time", "B"))),
+            None,
+            ("mtsp_step", ("locs", "num_agents", "agent_idx", "current_length", "max_subtour_length", "current_node",
+                           "action_mask", "done")),
+            ("locs", "num_agents"),
+            feats=Features(("remaining_agents", "current_length", "max_subtour_length", "depot_distance"), "proj_dynamic_feats")),
+)}
+
+
 def spec(env_name: str) -> EnvSpec:
     name = canonical_env(env_name)
-    return DYNAMIC_SPECS[name] if name in DYNAMIC_SPECS else SPECS[name]
+    for table in (DYNAMIC_SPECS, MINMAX_SPECS):
+        if name in table:
+            return table[name]
+    return SPECS[name]
 
 
 def rem_base(sp: EnvSpec, state: dict, b: int):

@@ -32,6 +32,9 @@ class GraphedRollout:
     def __init__(self, policy, env, example, decode_type: str = "greedy", warmup: int = 2, **forward_kwargs):
         if not example["locs"].is_cuda:
             raise RuntimeError("GraphedRollout needs CUDA tensors (HIP graph capture)")
+        if getattr(policy, "env_name", None) == "mtsp":
+            raise NotImplementedError("mtsp: captured-graph rollouts are not served (the padding step of the finished rows "
+                                      "follows the rollout's read-back)")
         self.policy, self.env = policy, env
         self.decode_type = decode_type
         self.kw = dict(forward_kwargs)

@@ -111,7 +111,7 @@ def bind_env_state(a, sp: EnvSpec, state: dict, b: int, n: int) -> int:
             b_inst = t.shape[0] if b_inst is None else b_inst
             if t.shape[0] != b_inst:
                 raise ValueError(f"{f.key} has {t.shape[0]} rows, expected {b_inst}")
-            dims = {"N-1": (n - 1,), "N": (n,), "N2": (n, 2)}[f.shape]
+            dims = {"N-1": (n - 1,), "N": (n,), "N2": (n, 2), "": ()}[f.shape]
             if tuple(t.shape[1:]) != dims:
                 raise ValueError(f"{f.key} must be [B_inst, {', '.join(map(str, dims))}], got {tuple(t.shape)}")
         if f.kind == "traj" and f.shape == "BN" and tuple(t.shape) != (b, n):  # (a short row would be read and written past its end)
@@ -250,6 +250,29 @@ def sdvrp_step(action: Tensor | None, demand_with_depot: Tensor, used_capacity: 
     _lib.check(st, "rl4co_sdvrp_step")
 
 
+def mtsp_step(action: Tensor, locs: Tensor, num_agents: Tensor, agent_idx: Tensor, current_length: Tensor,
+              max_subtour_length: Tensor, current_node: Tensor, action_mask: Tensor, done: Tensor,
+              err: Tensor | None = None) -> None:
+    """In-place MTSPEnv._step (mtsp/env.py:63-131): the mask is the state, the reward is ``-max_subtour_length``.
+    ``locs`` [B_inst, N, 2] / ``num_agents`` [B_inst] are instance data (trajectory b reads row b % B_inst)."""
+    mask = _u8(action_mask, "action_mask")
+    b, n = mask.shape
+    _check_rows(b, action=action, agent_idx=agent_idx, current_length=current_length, max_subtour_length=max_subtour_length,
+                current_node=current_node, done=done)
+    b_inst = locs.shape[0]
+    if tuple(locs.shape) != (b_inst, n, 2) or tuple(num_agents.shape) != (b_inst,) or b % b_inst:
+        raise ValueError(f"locs must be [B_inst, {n}, 2] and num_agents [B_inst] with {b} % B_inst == 0, got "
+                         f"{tuple(locs.shape)} and {tuple(num_agents.shape)}")
+    st = _lib.lib().rl4co_mtsp_step(
+        _ptr(_dev(action, torch.int64, "action")), _ptr(_dev(locs, torch.float32, "locs")),
+        _ptr(_dev(num_agents, torch.int64, "num_agents")), _ptr(_dev(agent_idx, torch.int64, "agent_idx")),
+        _ptr(_dev(current_length, torch.float32, "current_length")),
+        _ptr(_dev(max_subtour_length, torch.float32, "max_subtour_length")),
+        _ptr(_dev(current_node, torch.int64, "current_node")), _ptr(mask), _ptr(_u8(done, "done")), b, b_inst, n, _ptr(err),
+        _stream())
+    _lib.check(st, "rl4co_mtsp_step")
+
+
 def select_start_nodes(batch: int, num_starts: int, num_loc: int, has_depot: bool, device) -> Tensor:
     """ops.py:128-161: s-major ``arange(S).repeat_interleave(B) % num_loc (+1)``."""
     out = torch.empty((batch * num_starts,), dtype=torch.int64, device=device)
@@ -339,6 +362,16 @@ def am_decode(
         if tuple(dyn.shape) != (3, 128):
             raise ValueError(f"cache.dyn must be [3, 128], got {tuple(dyn.shape)}")
         a.dyn_vectors = dyn.data_ptr()
+    if sp.feats is not None:  # several running scalars: their folded context vectors, one row each (cache.fold_features)
+        if cache.unfold:
+            raise ValueError("the unfolded parity mode serves tsp / cvrp")
+        feat = _dev(cache.feat, torch.float32, "feat")
+        if tuple(feat.shape) != (len(sp.feats.names), 128):
+            raise ValueError(f"cache.feat must be [{len(sp.feats.names)}, 128], got {tuple(feat.shape)}")
+        if b != cache.num_instances:
+            raise ValueError(f"{sp.name} runs one trajectory per instance (no multistart rows): {b} trajectories over "
+                             f"{cache.num_instances} instances")
+        a.mtsp_ctx = feat.data_ptr()
     b_inst = bind_env_state(a, sp, state, b, n)
     assert b_inst == cache.num_instances or not sp.keys("inst"), "instance data rows must match cache instances"
     if exp_noise is not None:
@@ -467,6 +500,9 @@ def env_replay(env_name: str, state: dict, actions: Tensor, rem_base: Tensor | N
     capacity / length / prize), ``now`` (CVRPTW), ``mask_bits`` [B,T,W] int32 on request. The `evaluate` decoding's state
     sequence (decoding.py:448-461)."""
     sp = spec(env_name)
+    if sp.name not in SPECS:
+        raise NotImplementedError(f"the one-launch replay (rl4co_env_replay) serves {sorted(SPECS)}, not {sp.name}: use "
+                                  "env_replay_stepwise")
     b, n = state["action_mask"].shape
     acts = _dev(actions, torch.int64, "actions")
     if acts.dim() != 2 or acts.shape[0] != b:
@@ -506,7 +542,29 @@ def _replay_tables(sp: EnvSpec, b: int, t_len: int, n: int, dev) -> dict:
         out["rem"] = new(torch.float32)
         if sp.scalar.clock:
             out["now"] = new(torch.float32)
+    if sp.feats is not None:
+        out["feats"] = new(torch.float32, len(sp.feats.names))
     return out
+
+
+def context_features(sp: EnvSpec, state: dict) -> Tensor:
+    """The running scalars of ``sp.feats`` from a state, [B, len(names)] fp32 in the layer's column order
+    (env_embeddings/context.py:265-280). For the training re-evaluation: "depot_distance" is torch's ``norm`` on the
+    state's device, as the reference computes it there — NOT bound to the decode kernels' ``sqrt(fma(dy, dy, dx * dx))``
+    (the last bit may differ on the GPU; the re-evaluated log-probs are compared under a tolerance, never bit for bit)."""
+    b = state["current_node"].shape[0]
+    inst = lambda x: x if x.shape[0] == b else x.repeat(b // x.shape[0], *([1] * (x.dim() - 1)))  # noqa: E731
+    cols = []
+    for name in sp.feats.names:
+        if name == "remaining_agents":
+            cols.append((inst(state["num_agents"]) - state["agent_idx"]).float())
+        elif name == "depot_distance":
+            locs = inst(state["locs"])
+            here = locs.gather(1, state["current_node"].view(b, 1, 1).expand(b, 1, 2))[:, 0]
+            cols.append((here - locs[:, 0]).norm(p=2, dim=-1))
+        else:
+            cols.append(state[name].float())
+    return torch.stack(cols, -1)
 
 
 def env_replay_stepwise(env_name: str, state: dict, actions: Tensor, rem_base: Tensor | None, err: Tensor | None = None,
@@ -533,6 +591,8 @@ def env_replay_stepwise(env_name: str, state: dict, actions: Tensor, rem_base: T
             out["rem"][:, t] = torch.clamp(rem, min=0) if sp.scalar.clamp else rem
             if sp.scalar.clock:
                 out["now"][:, t] = state[sp.scalar.clock]
+        if sp.feats is not None:
+            out["feats"][:, t] = context_features(sp, state)
         env_step(env_name, state, actions[:, t].contiguous(), err)
     return out
 

@@ -257,6 +257,24 @@ class _VRPInit(nn.Module):
         return torch.cat((self.init_embed_depot(locs[:, :1, :]), self.init_embed(feats)), -2)
 
 
+class _MTSPInit(nn.Module):
+    """env_embeddings/init.py:363-379: the VRP embedding without a customer feature"""
+
+    def __init__(self, embed_dim):
+        super().__init__()
+        self.init_embed = nn.Linear(2, embed_dim, True)
+        self.init_embed_depot = nn.Linear(2, embed_dim, True)
+
+    def forward(self, td):
+        locs = td["locs"]
+        if _train_kernels_active(locs):
+            from . import train_ops
+
+            return torch.cat((train_ops.init_embed(locs[:, :1, :], self.init_embed_depot),
+                              train_ops.init_embed(locs[:, 1:, :].contiguous(), self.init_embed)), -2)
+        return torch.cat((self.init_embed_depot(locs[:, :1, :]), self.init_embed(locs[:, 1:, :])), -2)
+
+
 class _OPInit(_VRPInit):
     """env_embeddings/init.py:254-280: as the VRP embedding with the customers' PRIZE as third feature"""
 
@@ -358,7 +376,7 @@ class AttentionModelEncoder(nn.Module):
         super().__init__()
         self.env_name = env_name = canonical_env(env_name)
         self.init_embedding = {"tsp": _TSPInit, "cvrp": _VRPInit, "op": _OPInit, "pctsp": _PCTSPInit,
-                               "pdp": _PDPInit, "cvrptw": _VRPTWInit, "sdvrp": _VRPInit}[env_name](embed_dim)
+                               "pdp": _PDPInit, "cvrptw": _VRPTWInit, "sdvrp": _VRPInit, "mtsp": _MTSPInit}[env_name](embed_dim)
         self.net = _GraphAttentionNetwork(num_heads, embed_dim, num_layers, normalization, feedforward_hidden)
 
     def forward(self, td):
@@ -381,6 +399,16 @@ class _VRPContext(nn.Module):
     def __init__(self, embed_dim):
         super().__init__()
         self.project_context = nn.Linear(embed_dim + 1, embed_dim, bias=False)
+
+
+class _MTSPContext(nn.Module):
+    """env_embeddings/context.py:246-280 — parameters only: the current node's embedding and ``proj_dynamic_feats`` of the
+    four running scalars, side by side into ``project_context`` (folded: cache.fold_features)."""
+
+    def __init__(self, embed_dim):
+        super().__init__()
+        self.project_context = nn.Linear(2 * embed_dim, embed_dim, bias=False)
+        self.proj_dynamic_feats = nn.Linear(4, embed_dim, bias=False)
 
 
 class _SDVRPDynamic(nn.Module):
@@ -411,7 +439,8 @@ class AttentionModelDecoder(nn.Module):
         self.mask_inner = mask_inner
         self.check_nan = check_nan
         self.context_embedding = {"tsp": _TSPContext, "cvrp": _VRPContext, "op": _VRPContext, "pctsp": _VRPContext,
-                                  "pdp": _NodeContext, "cvrptw": _VRPTWContext, "sdvrp": _VRPContext}[env_name](embed_dim)
+                                  "pdp": _NodeContext, "cvrptw": _VRPTWContext, "sdvrp": _VRPContext,
+                                  "mtsp": _MTSPContext}[env_name](embed_dim)
         # StaticEmbedding (dynamic.py:47-57): no parameters; SDVRP: Linear(1 -> 3 * 128) on the remaining demand
         self.dynamic_embedding = _SDVRPDynamic(embed_dim) if env_name == "sdvrp" else nn.Module()
         self.pointer = _Pointer(embed_dim)
@@ -433,6 +462,7 @@ class AttentionModelDecoder(nn.Module):
             gemm_dtype=gemm_dtype,
             fold=fold,
             w_dyn=getattr(getattr(self.dynamic_embedding, "projection", None), "weight", None),
+            w_feat=getattr(getattr(self.context_embedding, "proj_dynamic_feats", None), "weight", None),
         )
 
 
@@ -642,7 +672,7 @@ class AttentionModelPolicy(nn.Module):
         for f in spec(self.env_name).fields:
             x = td[f.key]
             if f.kind == "inst":
-                st[f.key] = x.float().contiguous()
+                st[f.key] = (x.float() if f.dtype == "f32" else x).contiguous()
                 continue
             x = x if f.shape == "BN" else x.reshape(-1)
             st[f.key] = x.clone(memory_format=torch.contiguous_format) if s == 1 else x.unsqueeze(0).expand(s, *x.shape).reshape(s * x.shape[0], *x.shape[1:]).contiguous()
@@ -810,6 +840,13 @@ class AttentionModelPolicy(nn.Module):
         device = td["action_mask"].device
         b_inst, n = td["action_mask"].shape[0], td["action_mask"].shape[-1]
         b = b_inst * max(n_rep, 1)
+        if self.env_name == "mtsp":  # (DESIGN: what the min-max environment is not served with)
+            if n_rep > 0:
+                raise NotImplementedError("mtsp: multistart / multisample rollouts are not served (the multistart variant "
+                                          "does not carry the four-scalar context; one trajectory per instance)")
+            if decoding_kwargs.get("_defer_finish"):
+                raise NotImplementedError("mtsp: captured-graph rollouts are not served (the padding step of the finished "
+                                          "rows follows the rollout's read-back)")
         top_k, top_p = K.decoding_filter(opt.top_k, opt.top_p, n)
         filtered = bool(top_k or top_p)
         if filtered and not td["action_mask"].is_cuda:  # (the CPU specified-order oracle has no filter)
@@ -1002,8 +1039,13 @@ class AttentionModelPolicy(nn.Module):
             all_logps = all_logps[:, :t_used]
 
         # td mirrors the reference's final state (batchified rows when multistart)
+        if self.env_name == "mtsp":
+            self._mtsp_pad_finished(state, out_actions)
         td_out = td_early if td_early is not None else self._final_td(td, state, n_rep)
         td_out.set("action", out_actions[:, -1])
+        if self.env_name == "mtsp":  # the reference's loop counter and first action (state keys the kernels do not need)
+            td_out.set("i", torch.full((out_actions.shape[0],), out_actions.shape[1], dtype=torch.int64, device=device))
+            td_out.set("first_node", out_actions[:, 0].clone())
 
         # differentiable re-evaluation of the ROLLED-OUT rows (all s * b_inst of them: the replay needs the imposed
         # start nodes and the batchified state) — before any best-of selection narrows the rows
@@ -1028,6 +1070,7 @@ class AttentionModelPolicy(nn.Module):
 
                 t_max = __import__("rl4co_amd.teacher", fromlist=["max_nodes"]).max_nodes()
                 why = ("the dynamic embedding (remaining demand in keys and values) is not in the backward kernels" if self.env_name == "sdvrp" else
+                       "the four-scalar context (proj_dynamic_feats) and the min-max state are not in the backward kernels" if self.env_name == "mtsp" else
                        "fold=False keeps the reference's per-step association, which the backward kernels do not implement" if not self.fold else
                        f"{n} nodes are beyond the kernels' limit ({t_max})" if n > t_max else
                        f"{cache_dtype} planes are not served by the backward kernels (float32, bfloat16 or float16 planes) for this call")
@@ -1114,6 +1157,27 @@ class AttentionModelPolicy(nn.Module):
     def _env_step_state(self, state: dict, action: Tensor, err: Tensor) -> None:
         K.env_step(self.env_name, state, action, err)
 
+    def _mtsp_pad_finished(self, state: dict, actions: Tensor) -> None:
+        """The reference steps a finished row with action 0 until the whole batch is done (constructive/base.py:226-240);
+        for mTSP the FIRST such step is not neutral: it adds the return leg to ``current_length`` once more and
+        ``max_subtour_length`` — the reward — takes the maximum before the agent change resets the length
+        (mtsp/env.py:97-112). The kernels stop a row at ``done``; here the rows that finished before the rollout's last
+        step (own length = 1 + index of the last non-zero action < T) take exactly that one step on ``rl4co_mtsp_step``
+        (the kernels' rounding), and ``agent_idx`` the remaining padding steps' increments. In place."""
+        t_used = actions.shape[1]
+        last = t_used - 1 - (actions != 0).flip(1).to(torch.int8).argmax(1)  # index of the last non-zero action
+        pad = (t_used - 1) - last  # padding steps the reference applied to the row
+        rows = (pad > 0).nonzero()[:, 0]  # (behind the rollout's read-back: the host is in step already)
+        if rows.numel() == 0:
+            return
+        sp = spec("mtsp")
+        part = {f.key: state[f.key][rows].contiguous() for f in sp.fields}  # the padded rows alone, instance data included
+        K.env_step("mtsp", part, torch.zeros(rows.numel(), dtype=torch.int64, device=actions.device),
+                   K.new_error_word(actions.device))
+        part["agent_idx"] += pad[rows] - 1
+        for key in sp.keys("traj"):
+            state[key][rows] = part[key]
+
     def _final_td(self, td, state: dict, n_rep: int) -> TensorDict:
         s = max(n_rep, 1)
         b_inst = td["action_mask"].shape[0]
@@ -1149,11 +1213,14 @@ class AttentionModelPolicy(nn.Module):
         # starts of an instance, the mask as bits from the same replay launch); otherwise torch's SDPA in fp32
         regime = self._encoder_regime()
         dynamic = self.env_name == "sdvrp"  # keys and values move with the state: torch, in the reference's association
+        stepwise = spec(self.env_name).feats is not None  # mTSP: the four running scalars tabulated step by step
         glimpse_kernel = (hidden.is_cuda and regime in (torch.bfloat16, torch.float16) and dec.mask_inner and dec.num_heads == 8
-                          and d == 128 and self.fused_backward and not dynamic)
+                          and d == 128 and self.fused_backward and not dynamic and not stepwise)
         if dynamic:
             masks, ctx_nodes, extras, demands = self._replay_by(K.env_replay_stepwise, td, actions, n_rep, False, record="demand_with_depot")
             mask_bits = None
+        elif stepwise:
+            masks, ctx_nodes, extras, mask_bits = self._replay_stepwise(td, actions, n_rep)
         else:
             masks, ctx_nodes, extras, mask_bits = self._replay(td, actions, n_rep, mask_bits=glimpse_kernel)
         h = hidden if s == 1 else hidden.unsqueeze(0).expand(s, b_inst, n, d).reshape(b, n, d)
@@ -1171,6 +1238,8 @@ class AttentionModelPolicy(nn.Module):
             ctx = h.gather(1, prev[..., None].expand(b, t_len, d))
             if sp.scalar is not None:  # + remaining capacity / length / prize (, current time)
                 ctx = torch.cat([ctx, extras if sp.scalar.clock else extras[..., None]], -1)
+            if sp.feats is not None:  # context.py:265-275: + proj_dynamic_feats(the four running scalars)
+                ctx = torch.cat([ctx, getattr(dec.context_embedding, sp.feats.weight)(extras)], -1)
         q = F.linear(ctx, w_ctx)
         if dec.use_graph_context:
             g = dec.project_fixed_context(hidden.mean(1))
@@ -1273,4 +1342,6 @@ class AttentionModelPolicy(nn.Module):
         if sp.ctx_first:
             return r["masks"], (r["first"], r["prev"]), r["use_placeholder"], r.get("mask_bits")
         extras = None if sp.scalar is None else (torch.stack((r["rem"], r["now"]), -1) if sp.scalar.clock else r["rem"])
+        if sp.feats is not None:
+            extras = r["feats"]  # [B, T, 4] (the stepwise form)
         return r["masks"], (r["prev"],), extras, r.get("mask_bits")

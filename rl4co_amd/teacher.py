@@ -53,7 +53,16 @@ def supports(env_name: str, cache_dtype: torch.dtype, num_nodes: int) -> bool:
     MMA one needs bf16 planes; fp32 planes take the replay kernel)."""
     if num_nodes > max_nodes() or cache_dtype not in (torch.float32, torch.bfloat16, torch.float16):
         return False
-    return env_name in ("tsp", "cvrp", "op", "pctsp", "pdp", "cvrptw")
+    return env_name in TEACHER_ENVS
+
+
+TEACHER_ENVS = ("tsp", "cvrp", "op", "pctsp", "pdp", "cvrptw")
+
+
+def _require_served(env_name: str) -> None:
+    if env_name not in TEACHER_ENVS:
+        raise NotImplementedError(f"the teacher-forced backward kernels serve {', '.join(TEACHER_ENVS)}, not {env_name}: its "
+                                  "training step differentiates policy.evaluate_log_probs")
 
 
 backward_events: list | None = None  # set to [] by bench.py to time the teacher-forced backward launches
@@ -69,6 +78,7 @@ def run_backward(cache: FoldedCache, actions: Tensor, grad_logp: Tensor, meta: d
     ``d_planes``: a bf16 [3, B_inst, N, 128] view (any plane / instance / node strides, unit channel stride) that
     receives the three plane gradients instead of a fresh fp32 ``d_kvl`` (MMA variant only).
     """
+    _require_served(cache.env_name)
     b, t = actions.shape
     b_inst, n = cache.num_instances, cache.num_nodes
     dev = actions.device
@@ -275,6 +285,7 @@ class TeacherForcedFoldLogLik(torch.autograd.Function):
 def teacher_forced_logps(env_name: str, g: dict[str, Tensor], cache: FoldedCache, actions: Tensor, logps: Tensor,
                          meta: dict) -> Tensor:
     """Differentiable per-step log-probs of ``actions`` (values = ``logps`` from the rollout)."""
+    _require_served(env_name)
     extra = g["q_step0"] if env_name == "tsp" else g.get("w_cap")  # None for PDP (no context scalar)
     if g.get("fused"):
         return TeacherForcedFoldLogLik.apply(g["h"], g["w_all"], g.get("q_bias"), extra, g.get("w_time"), logps, cache,
