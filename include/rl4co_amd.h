@@ -79,11 +79,11 @@ extern "C" {
 /* Split-delivery VRP (envs/routing/sdvrp/env.py): the one environment with a dynamic embedding (the remaining demand moves
  * the keys and values every step). Decode only — STREAM / LDS / WIDE; not the multistart variant, the unfolded mode, the
  * replay or the teacher kernels, whose six environments are the ids above. */
-#define RL4CO_ENV_SDVRP (RL4CO_ENV_CVRPTW + 1)
+#define RL4CO_ENV_SDVRP 6
 /* Multi-agent TSP, min-max (envs/routing/mtsp/env.py): up to num_agents subtours from the depot (node 0), the reward is the
  * longest subtour and is carried in the state. Decode only — STREAM / LDS / WIDE; not the multistart variant, the unfolded
  * mode, the replay or the teacher kernels. */
-#define RL4CO_ENV_MTSP (RL4CO_ENV_CVRPTW + 2)
+#define RL4CO_ENV_MTSP 7
 
 #define RL4CO_DECODE_GREEDY 0   /* utils/decoding.py:387-397 */
 #define RL4CO_DECODE_SAMPLE 1   /* utils/decoding.py:399-413 */

@@ -26,15 +26,9 @@ from dataclasses import dataclass
 import torch
 from torch import Tensor
 
+from .envspec import KERNEL_ENV, EnvSpec, canonical_env, spec  # noqa: F401  (the first and third: this module's names too)
+
 EMBED_DIM = 128
-
-# environments that share another one's kernels (same state, masks, embeddings): stochastic PCTSP only
-# differs in which generated prize its reset() calls "real" (spctsp/env.py:8-21)
-KERNEL_ENV = {"spctsp": "pctsp"}
-
-
-def canonical_env(env_name: str) -> str:
-    return KERNEL_ENV.get(env_name, env_name)
 
 
 @dataclass
@@ -92,11 +86,9 @@ def fold_weights(env_name: str, w_node: Tensor, w_out: Tensor, w_ctx: Tensor) ->
     d = EMBED_DIM
     wk, wv, wl = w_node[:d], w_node[d : 2 * d], w_node[2 * d :]
     wl_folded = w_out.t() @ wl  # logits = heads^T W_out^T (Wl h_j)
-    if env_name == "tsp":
+    if spec(env_name).ctx_first:
         return [wk, wv, wl_folded, w_ctx[:, :d], w_ctx[:, d : 2 * d]]
-    if env_name in ("cvrp", "op", "pctsp", "pdp", "cvrptw", "sdvrp", "mtsp"):  # current-node embedding (+ scalars: capacity / remaining length / prize; mtsp: fold_features)
-        return [wk, wv, wl_folded, w_ctx[:, :d]]
-    raise ValueError(f"fused decode supports tsp/cvrp/op, got {env_name!r}")
+    return [wk, wv, wl_folded, w_ctx[:, :d]]  # current-node embedding (the columns behind it: fold_constants)
 
 
 def fold_dynamic(w_dyn: Tensor, w_out: Tensor) -> Tensor:
@@ -115,6 +107,29 @@ def fold_features(w_ctx: Tensor, w_feat: Tensor) -> Tensor:
     d = EMBED_DIM
     g = w_ctx.detach().double()[:, d : 2 * d] @ w_feat.detach().double()  # [128, 4]
     return g.t().float().contiguous()
+
+
+def fold_constants(sp: EnvSpec, w_ctx: Tensor, w_out: Tensor, w_placeholder: Tensor | None = None,
+                   w_dyn: Tensor | None = None, w_feat: Tensor | None = None) -> tuple:
+    """The folded cache's batch-shared vectors ``(q_step0, w_cap, w_time, dyn, feat)``, fp32, by the record's context layout
+    (None: the environment has no such term): the step-0 query ``W_ctx W_placeholder`` of a (first, current) context; the
+    context scalar's column 128 of ``W_ctx`` and the clock's column 129; ``fold_dynamic``; ``fold_features`` (whose
+    environments' columns 128.. of ``W_ctx`` meet the running scalars' own layer: not scalar columns)."""
+    d = EMBED_DIM
+    w_ctx = w_ctx.detach().float()
+    q_step0 = torch.mv(w_ctx, w_placeholder.detach().float()).contiguous() if sp.ctx_first else None
+    w_cap = w_ctx[:, d].contiguous() if sp.scalar is not None else None
+    w_time = w_ctx[:, d + 1].contiguous() if sp.scalar is not None and sp.scalar.clock else None
+    dyn = feat = None
+    if sp.dynamic is not None:
+        if w_dyn is None:
+            raise ValueError(f"{sp.name} needs the dynamic embedding's weight (decoder.dynamic_embedding.{sp.dynamic.weight}.weight)")
+        dyn = fold_dynamic(w_dyn, w_out)
+    if sp.feats is not None:
+        if w_feat is None:
+            raise ValueError(f"{sp.name} needs the running scalars' weight (decoder.context_embedding.{sp.feats.weight}.weight)")
+        feat = fold_features(w_ctx, w_feat)
+    return q_step0, w_cap, w_time, dyn, feat
 
 
 def _fold_tables_f32(h: Tensor, blocks: list[Tensor], w_fixed: Tensor | None):
@@ -165,7 +180,7 @@ def build_folded_cache(
     if not fold:
         # reference association (zoo/am/decoder.py:201-228): the cache is project_node_embeddings(h) chunked in three,
         # the graph context project_fixed_context(h.mean(1)); context / output projections stay per-step GEMVs
-        if env_name not in ("tsp", "cvrp"):
+        if not spec(env_name).unfold:
             raise ValueError("the unfolded parity mode serves tsp / cvrp")
         kvl = torch.empty((3, b, n, d), dtype=cache_dtype, device=h.device)
         h32 = h.reshape(b * n, d).float()
@@ -201,23 +216,6 @@ def build_folded_cache(
         q_bias = None
         if w_fixed is not None:
             q_bias = torch.matmul(h.mean(1, dtype=torch.float32), w_fixed.float().t()).contiguous()
-    if env_name == "tsp":
-        ctx_first, ctx_cur = ctx
-        q_step0 = torch.mv(w_ctx.float(), w_placeholder.float()).contiguous()
-        w_cap = None
-    else:
-        ctx_first, ctx_cur = None, ctx[0]
-        q_step0 = None
-        w_cap = w_ctx.float()[:, d].contiguous() if w_ctx.shape[1] > d else None  # PDP: no context scalar
-    w_time = w_ctx.float()[:, d + 1].contiguous() if w_ctx.shape[1] > d + 1 else None  # CVRPTW: current time
-    dyn = None
-    if env_name == "sdvrp":
-        if w_dyn is None:
-            raise ValueError("sdvrp needs the dynamic embedding's weight (decoder.dynamic_embedding.projection.weight)")
-        dyn = fold_dynamic(w_dyn, w_out)
-    feat = None
-    if env_name == "mtsp":
-        if w_feat is None:
-            raise ValueError("mtsp needs the running scalars' weight (decoder.context_embedding.proj_dynamic_feats.weight)")
-        feat, w_cap, w_time = fold_features(w_ctx, w_feat), None, None  # (columns 128.. of W_ctx are not scalar columns here)
+    ctx_first, ctx_cur = ctx if len(ctx) == 2 else (None, ctx[0])
+    q_step0, w_cap, w_time, dyn, feat = fold_constants(spec(env_name), w_ctx, w_out, w_placeholder, w_dyn, w_feat)
     return FoldedCache(env_name, kvl, ctx_first, ctx_cur, q_bias, q_step0, w_cap, w_time, dyn, feat)

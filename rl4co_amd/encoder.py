@@ -19,7 +19,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .cache import EMBED_DIM, FoldedCache, fold_dynamic, fold_features, fold_weights
+from .cache import EMBED_DIM, FoldedCache, fold_constants, fold_weights
 from .envspec import customer_features, spec
 
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
@@ -134,17 +134,17 @@ class PackedEncoder:
         exact = self.act_dtype == torch.float32  # csrc/am_encoder_f32.hip: fp32 MFMA, the reference's own arithmetic order
         pack_weight = (pack_weight_f32 if exact else lambda w: globals()["pack_weight"](w, self.act_dtype))  # noqa: E731
         t: dict[str, Tensor] = {}
-        ie = enc.init_embedding
-        if pol.env_name == "pdp":
+        ie, sp = enc.init_embedding, spec(pol.env_name)
+        if sp.init == "pairs":
             t["w_init"], t["b_init"] = f32(ie.init_embed_pick.weight), f32(ie.init_embed_pick.bias)
             t["w_extra"], t["b_extra"] = f32(ie.init_embed_delivery.weight), f32(ie.init_embed_delivery.bias)
         else:
             t["w_init"], t["b_init"] = f32(ie.init_embed.weight), f32(ie.init_embed.bias)
-        if pol.env_name == "mtsp":
+        if sp.init == "depot" and not sp.features:
             # MTSPInitEmbedding (init.py:363-379) is the VRP embedding without a customer feature: the kernels' depot |
             # customers mode with a zero feature column against a zero weight column (x w0 + y w1 + 0 * 0: the same value)
             t["w_init"] = torch.cat((t["w_init"], torch.zeros_like(t["w_init"][:, :1])), 1).contiguous()
-        if pol.env_name != "tsp":
+        if sp.init != "all":
             t["w_depot"], t["b_depot"] = f32(ie.init_embed_depot.weight), f32(ie.init_embed_depot.bias)
         # the query rows of Wqkv (and their bias) carry head_dim^-1/2 * log2(e): the kernel's softmax is exp2(q . k)
         # (fp32 kernel: only the power of two — exact — and exp(s - max) as exp2((s - max) * log2 e) in the kernel)
@@ -181,25 +181,12 @@ class PackedEncoder:
         blocks = fold_weights(pol.env_name, dec.project_node_embeddings.weight.detach().float(),
                               dec.pointer.project_out.weight.detach().float(), w_ctx)
         t["wfold"] = torch.stack([pack_weight(b) for b in blocks]).contiguous()
-        if exact and pol.env_name in ("tsp", "cvrp"):
+        if exact and sp.unfold:
             # fold=False (the reference's own association of the decoder, cache.py): the three raw planes K_g, V_g, K_l
             w_node = dec.project_node_embeddings.weight.detach().float()
             t["wnode"] = torch.stack([pack_weight(w_node[i * EMBED_DIM:(i + 1) * EMBED_DIM]) for i in range(3)]).contiguous()
         t["w_fixed"] = f32(dec.project_fixed_context.weight) if dec.use_graph_context else None
-        if pol.env_name == "tsp":
-            t["q_step0"] = torch.mv(w_ctx, dec.context_embedding.W_placeholder.detach().float()).contiguous()
-            t["w_cap"] = None
-        else:
-            t["q_step0"] = None
-            t["w_cap"] = w_ctx[:, EMBED_DIM].contiguous() if w_ctx.shape[1] > EMBED_DIM else None  # PDP: no scalar
-        t["w_time"] = w_ctx[:, EMBED_DIM + 1].contiguous() if w_ctx.shape[1] > EMBED_DIM + 1 else None  # CVRPTW
-        w_dyn = getattr(getattr(dec.dynamic_embedding, "projection", None), "weight", None)  # SDVRP
-        t["dyn"] = None if w_dyn is None else fold_dynamic(w_dyn, dec.pointer.project_out.weight)
-        t["feat"] = None
-        sp = spec(pol.env_name)
-        if sp.feats is not None:  # mTSP: columns 128.. of W_ctx meet the running scalars' own layer (cache.fold_features)
-            t["feat"] = fold_features(w_ctx, getattr(dec.context_embedding, sp.feats.weight).weight)
-            t["w_cap"] = t["w_time"] = None
+        t["q_step0"], t["w_cap"], t["w_time"], t["dyn"], t["feat"] = fold_constants(sp, **dec.constant_weights())
         self.num_layers = len(layers)
         self.t, self.version = t, ver
         return t
@@ -278,15 +265,15 @@ class PackedEncoder:
         if not exact and not tokens and cache_dtype == self.act_dtype and not os.environ.get("RL4CO_CTX_FP32"):
             ctx_dt = self.act_dtype
         ctx_cur = torch.empty((b, n, d), dtype=ctx_dt, device=dev) if fold else None
-        ctx_first = torch.empty((b, n, d), dtype=ctx_dt, device=dev) if (fold and pol.env_name == "tsp") else None
+        sp = spec(pol.env_name)
+        ctx_first = torch.empty((b, n, d), dtype=ctx_dt, device=dev) if (fold and sp.ctx_first) else None
         q_bias = torch.empty((b, d), dtype=torch.float32, device=dev) if t["w_fixed"] is not None else None
         hidden = torch.empty((b, n, d), dtype=torch.float32, device=dev) if (want_hidden or not fold) else None
         a = AmEncoderArgs()
-        sp = spec(pol.env_name)
         # the encoder kernels have three init-embedding modes, named by the environment that has it alone: TSP (every node
         # alike), PDP (depot | pickups | deliveries), CVRP (depot | customers with 1-4 feature columns behind x, y)
-        no_feature = sp.name == "mtsp"  # depot | customers with (x, y) alone: one zero feature column (refresh: w_init)
-        a.env = _lib.ENV_CVRP if (sp.features or no_feature) else sp.env_id
+        a.env = {"all": _lib.ENV_TSP, "pairs": _lib.ENV_PDP, "depot": _lib.ENV_CVRP}[sp.init]
+        no_feature = sp.init == "depot" and not sp.features  # (x, y) alone: one zero feature column (refresh: w_init)
         a.B, a.N, a.num_layers, a.norm = b, n, self.num_layers, self.norm_kind
         a.cache_dtype, a.act_dtype = _lib.dtype_id(cache_dtype), _lib.dtype_id(self.act_dtype)
         a.ctx_dtype = _lib.dtype_id(ctx_dt) if ctx_dt != torch.float32 else 0
@@ -297,16 +284,13 @@ class PackedEncoder:
             cols = [c.contiguous() for f in customer_features(sp, td) for c in f.unbind(-1)]
             for slot, c in zip(("demand", "feature4", "feature5", "feature6"), cols):
                 setattr(a, slot, c.data_ptr())
-            a.w_depot, a.b_depot = ptr(t["w_depot"]), ptr(t["b_depot"])
         if no_feature:
             zero_col = self._zero_col  # kept between calls: the kernels only read it
             if zero_col is None or zero_col.numel() < b * (n - 1) or zero_col.device != dev:
                 zero_col = self._zero_col = torch.zeros(b * (n - 1), dtype=torch.float32, device=dev)
             a.demand = zero_col.data_ptr()
-            a.w_depot, a.b_depot = ptr(t["w_depot"]), ptr(t["b_depot"])
-        if pol.env_name == "pdp":
-            a.w_depot, a.b_depot = ptr(t["w_depot"]), ptr(t["b_depot"])
-            a.w_extra, a.b_extra = ptr(t["w_extra"]), ptr(t["b_extra"])
+        a.w_depot, a.b_depot = ptr(t.get("w_depot")), ptr(t.get("b_depot"))
+        a.w_extra, a.b_extra = ptr(t.get("w_extra")), ptr(t.get("b_extra"))
         a.w_init, a.b_init = ptr(t["w_init"]), ptr(t["b_init"])
         a.wqkv_packed, a.bqkv, a.wo_packed, a.bo = ptr(t["wqkv"]), ptr(t["bqkv"]), ptr(t["wo"]), ptr(t["bo"])
         a.n1_scale, a.n1_shift, a.n2_scale, a.n2_shift = (ptr(t[k]) for k in ("n1_scale", "n1_shift", "n2_scale", "n2_shift"))

@@ -4,14 +4,25 @@ The kernels take the environment as a template parameter and a fixed set of argu
 ``demand``, ``used_capacity``, ``vehicle_capacity``, ``visited``, ``locs``, ...). Which state tensor of which environment
 rides in which slot is stated HERE, once; ``kernels.bind_env_state`` / ``kernels.env_step``, ``policy`` (state, final
 TensorDict, replay, horizon), ``teacher.run_backward`` and the encoder's feature columns read it. Adding an environment
-means adding a record below. Data only: nothing here touches the GPU or loads the library.
+means adding a record below: what the code must know about an environment — its context layout, its init embedding, which
+kernels serve it — is a field here, and no binding asks for an environment by name. Data only: nothing here touches the GPU or
+loads the library.
 """
 from __future__ import annotations
 
 from typing import Callable, NamedTuple
 
+import torch
+
 from . import _lib
-from .cache import canonical_env
+
+# environments that share another one's kernels (same state, masks, embeddings): stochastic PCTSP only
+# differs in which generated prize its reset() calls "real" (spctsp/env.py:8-21)
+KERNEL_ENV = {"spctsp": "pctsp"}
+
+
+def canonical_env(env_name: str) -> str:
+    return KERNEL_ENV.get(env_name, env_name)
 
 
 class Field(NamedTuple):
@@ -48,6 +59,15 @@ class Features(NamedTuple):
     weight: str
 
 
+class Dynamic(NamedTuple):
+    """Keys and values that move with a per-trajectory state tensor (SDVRP, zoo/am/decoder.py:142-152: a dynamic embedding
+    ``Linear(1 -> 3 * 128)`` of state ``key``). ``weight``: the layer's attribute on ``decoder.dynamic_embedding``; ``slot``:
+    where its fold (``cache.fold_dynamic``, fp32 [3, 128]) rides in ``rl4co_am_decode_args``."""
+    key: str
+    weight: str
+    slot: str
+
+
 class EnvSpec(NamedTuple):
     name: str
     env_id: int  # RL4CO_ENV_* of include/rl4co_amd.h
@@ -57,10 +77,33 @@ class EnvSpec(NamedTuple):
     scalar: Scalar | None
     step: tuple[str, tuple[str, ...]]  # the ``kernels`` step entry and the state keys it takes between action and err
     passthrough: tuple[str, ...]  # td keys the final TensorDict repeats over the starts as they are
-    features: tuple[tuple[str, bool], ...] = ()  # customer init-embedding columns behind (x, y): (td key, drop the depot column)
-    depot_embed: bool = True  # the depot has an init embedding of its own
+    # customer init-embedding columns behind (x, y): (td key, drop the depot column, columns)
+    features: tuple[tuple[str, bool, int], ...] = ()
+    # init embedding: "all" every node alike | "depot" depot | customers with ``features`` behind (x, y), possibly none |
+    # "pairs" depot | pickups | deliveries (the encoder kernels' three modes)
+    init: str = "depot"
     ctx_first: bool = False  # context = (first node, current node), placeholder at step 0; else current node (+ scalars)
     feats: Features | None = None  # several running scalars through a second linear layer (instead of ``scalar``)
+    dynamic: Dynamic | None = None
+    # the reward is carried in the state and ONE non-neutral padding step follows the read-back: one trajectory per
+    # instance (no multistart / multisample rows), no captured graph
+    state_reward: bool = False
+    fixed_horizon: bool = False  # every row takes exactly horizon(n) steps: a training step's status read-back may be asynchronous
+    length_reward: bool = False  # the reward is a tour length: it can go out before the read-back (get_reward(horizon=...))
+    depot_flag: str | None = None  # env attribute: the tour starts at the depot; without it the depot is never visited (n - 1 steps)
+    # what serves it besides the decode kernels: the unfolded parity mode, the one-launch rl4co_env_replay, the
+    # teacher-forced backward kernels (else ``no_teacher``: why not, as the fallback warning says it)
+    unfold: bool = False
+    replay: bool = True
+    no_teacher: str | None = None
+
+    @property
+    def teacher(self) -> bool:
+        return self.no_teacher is None
+
+    @property
+    def feature_width(self) -> int:
+        return sum(width for _, _, width in self.features)
 
     def keys(self, kind: str | None = None) -> tuple[str, ...]:
         return tuple(f.key for f in self.fields if kind in (None, f.kind))
@@ -88,12 +131,12 @@ SPECS = {s.name: s for s in (
     EnvSpec("tsp", _lib.ENV_TSP, False, lambda n: n,
             _fields("B", ("first_node", "traj", "i64", "first_node", "B"), ("i", "traj", "i64", "step_i", "B1")),
             None, ("tsp_step", ("action_mask", "first_node", "current_node", "i", "done")),
-            ("locs",), depot_embed=False, ctx_first=True),
+            ("locs",), init="all", ctx_first=True, fixed_horizon=True, length_reward=True, unfold=True),
     # CVRP: every customer + at most one depot visit per customer + 1
     EnvSpec("cvrp", _lib.ENV_CVRP, True, lambda n: 2 * n, _fields("B1", *_CVRP_FIELDS),
             Scalar("used_capacity", "vehicle_capacity"),
             ("cvrp_step", ("demand", "used_capacity", "vehicle_capacity", "visited", "current_node", "action_mask", "done")),
-            ("locs", "demand"), features=(("demand", False),)),
+            ("locs", "demand"), features=(("demand", False, 1),), length_reward=True, unfold=True),
     # OP: every customer once, the closing depot visit, and a depot pick at step 0 costs one more. The tour length rides
     # in the used_capacity slot; the per-node entry limits (max_length table) and the coordinates are instance data
     EnvSpec("op", _lib.ENV_OP, True, lambda n: n + 2,
@@ -101,7 +144,7 @@ SPECS = {s.name: s for s in (
                     ("tour_length", "traj", "f32", "used_capacity", "B"), _I, _VISITED),
             Scalar("tour_length", "max_length", base_col0=True),
             ("op_step", ("locs", "max_length", "tour_length", "visited", "current_node", "i", "action_mask", "done")),
-            ("locs", "prize", "max_length"), features=(("prize", True),)),
+            ("locs", "prize", "max_length"), features=(("prize", True, 1),)),
     # PCTSP: every customer once and the closing depot visit (the depot is masked at step 0). The real prize per node
     # (depot column 0) rides in the demand slot, the prize collected so far in used_capacity, prize_required in
     # vehicle_capacity
@@ -110,13 +153,14 @@ SPECS = {s.name: s for s in (
                     ("prize_required", "traj", "f32", "vehicle_capacity", "B"), _I, _VISITED),
             Scalar("cur_total_prize", "prize_required", clamp=True),
             ("pctsp_step", ("real_prize", "cur_total_prize", "visited", "current_node", "i", "action_mask", "done")),
-            ("locs", "real_prize", "expected_prize", "penalty"), features=(("expected_prize", False), ("penalty", True))),
-    # PDP: every node once (the depot too under force_start_at_depot). `available` rides in the visited slot; no scalar
+            ("locs", "real_prize", "expected_prize", "penalty"), features=(("expected_prize", False, 1), ("penalty", True, 1))),
+    # PDP: every node once (the depot too under force_start_at_depot: else it is never visited and a rollout is exactly one
+    # step per location). `available` rides in the visited slot; no scalar
     EnvSpec("pdp", _lib.ENV_PDP, True, lambda n: n,
             _fields("B1", ("available", "traj", "u8", "visited", "BN"), ("to_deliver", "traj", "u8", "to_deliver", "BN"),
                     ("i", "traj", "i64", "step_i", "B1")),
             None, ("pdp_step", ("available", "to_deliver", "current_node", "i", "action_mask", "done")),
-            ("locs",)),
+            ("locs",), init="pairs", length_reward=True, depot_flag="force_start_at_depot"),
     # CVRPTW: CVRP + clock; coordinates, (start, end) windows and service times as fp32 instance data (the reference
     # keeps integer-valued windows)
     EnvSpec("cvrptw", _lib.ENV_CVRPTW, True, lambda n: 2 * n,
@@ -127,16 +171,10 @@ SPECS = {s.name: s for s in (
             ("cvrptw_step", ("demand", "locs", "time_windows", "durations", "used_capacity", "vehicle_capacity", "current_time",
                              "visited", "current_node", "action_mask", "done")),
             ("locs", "demand", "time_windows", "durations"),
-            features=(("demand", False), ("time_windows", True), ("durations", True))),
-)}
-
-
-# Environments with a DYNAMIC embedding (zoo/am/decoder.py:142-152): the state moves the keys and values every step, so the
-# per-trajectory state tensor is also an operand of the attention. Served by the decode kernels (STREAM / LDS / WIDE) alone —
-# not by the multistart variant, the unfolded mode, the one-launch replay or the teacher kernels, whose environments are the
-# six of SPECS — hence a table of their own; `spec` resolves both.
-DYNAMIC_SPECS = {s.name: s for s in (
-    # SDVRP (sdvrp/env.py:56-123): CVRP's instance, but a visit delivers min(remaining demand, remaining capacity) and a
+            features=(("demand", False, 1), ("time_windows", True, 2), ("durations", True, 1)), length_reward=True),
+    # SDVRP (sdvrp/env.py:56-123), a DYNAMIC embedding (zoo/am/decoder.py:142-152): the state moves the keys and values
+    # every step, so the per-trajectory state tensor is also an operand of the attention. Served by the decode kernels
+    # (STREAM / LDS / WIDE) alone. CVRP's instance, but a visit delivers min(remaining demand, remaining capacity) and a
     # customer stays until its demand is 0. `demand_with_depot` [B, N] is per trajectory and written by the kernels; the
     # init embedding reads the INITIAL `demand`. Horizon: a customer visit either zeroes that customer's demand (at most
     # n - 1 such visits, a zeroed customer is masked for good) or fills the vehicle (used = cap). After a fill, cap - used
@@ -149,14 +187,11 @@ DYNAMIC_SPECS = {s.name: s for s in (
                     ("vehicle_capacity", "traj", "f32", "vehicle_capacity", "B1")),
             Scalar("used_capacity", "vehicle_capacity"),
             ("sdvrp_step", ("demand_with_depot", "used_capacity", "vehicle_capacity", "current_node", "action_mask", "done")),
-            ("locs", "demand"), features=(("demand", False),)),
-)}
-
-
-# Environments whose REWARD is carried in the state (a min-max objective) and whose context holds several running scalars
-# (`Features`). Decode kernels alone, as DYNAMIC_SPECS, and with one trajectory per instance (no multistart rows).
-MINMAX_SPECS = {s.name: s for s in (
-    # mTSP (mtsp/env.py:63-131): n nodes INCLUDING the depot; up to num_agents subtours from the depot, the reward is the
+            ("locs", "demand"), features=(("demand", False, 1),), length_reward=True, replay=False,
+            dynamic=Dynamic("demand_with_depot", "projection", "dyn_vectors"),
+            no_teacher="the dynamic embedding (remaining demand in keys and values) is not in the backward kernels"),
+    # mTSP (mtsp/env.py:63-131), a min-max objective: the REWARD is carried in the state and the context holds several
+    # running scalars (`Features`). Decode kernels alone, one trajectory per instance. n nodes INCLUDING the depot; up to num_agents subtours from the depot, the reward is the
     # longest. The mask is the state (the reference's `available`). agent_idx rides in step_i, current_length in
     # used_capacity, max_subtour_length in current_time. Horizon: n - 1 customer visits; every depot visit follows a
     # customer visit (the depot is closed while the agent stands on it) and comes before done (the rollout ends AT done):
@@ -172,16 +207,14 @@ MINMAX_SPECS = {s.name: s for s in (
             ("mtsp_step", ("locs", "num_agents", "agent_idx", "current_length", "max_subtour_length", "current_node",
                            "action_mask", "done")),
             ("locs", "num_agents"),
-            feats=Features(("remaining_agents", "current_length", "max_subtour_length", "depot_distance"), "proj_dynamic_feats")),
+            feats=Features(("remaining_agents", "current_length", "max_subtour_length", "depot_distance"), "proj_dynamic_feats"),
+            state_reward=True, replay=False,
+            no_teacher="the four-scalar context (proj_dynamic_feats) and the min-max state are not in the backward kernels"),
 )}
 
 
 def spec(env_name: str) -> EnvSpec:
-    name = canonical_env(env_name)
-    for table in (DYNAMIC_SPECS, MINMAX_SPECS):
-        if name in table:
-            return table[name]
-    return SPECS[name]
+    return SPECS[canonical_env(env_name)]
 
 
 def rem_base(sp: EnvSpec, state: dict, b: int):
@@ -195,8 +228,8 @@ def rem_base(sp: EnvSpec, state: dict, b: int):
     return base
 
 
-def customer_features(sp: EnvSpec, td) -> list:
-    """The customers' init-embedding features behind the coordinates (env_embeddings/init.py), fp32 [B, n - 1, k] each in
-    the order of the embedding's input columns."""
-    cols = [(td[key][:, 1:] if drop_depot else td[key]).float() for key, drop_depot in sp.features]
+def customer_features(sp: EnvSpec, td, dtype=torch.float32) -> list:
+    """The customers' init-embedding features behind the coordinates (env_embeddings/init.py), ``dtype`` [B, n - 1, k] each
+    in the order of the embedding's input columns."""
+    cols = [(td[key][:, 1:] if drop_depot else td[key]).to(dtype) for key, drop_depot, _ in sp.features]
     return [c if c.dim() == 3 else c[..., None] for c in cols]

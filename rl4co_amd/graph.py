@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import torch
 
+from .envspec import spec
 from .tensordict import TensorDict
 
 
@@ -32,8 +33,9 @@ class GraphedRollout:
     def __init__(self, policy, env, example, decode_type: str = "greedy", warmup: int = 2, **forward_kwargs):
         if not example["locs"].is_cuda:
             raise RuntimeError("GraphedRollout needs CUDA tensors (HIP graph capture)")
-        if getattr(policy, "env_name", None) == "mtsp":
-            raise NotImplementedError("mtsp: captured-graph rollouts are not served (the padding step of the finished rows "
+        name = getattr(policy, "env_name", None)
+        if name is not None and spec(name).state_reward:
+            raise NotImplementedError(f"{name}: captured-graph rollouts are not served (the padding step of the finished rows "
                                       "follows the rollout's read-back)")
         self.policy, self.env = policy, env
         self.decode_type = decode_type

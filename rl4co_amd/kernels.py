@@ -355,16 +355,14 @@ def am_decode(
             a.w_cap = _ptr(_dev(cache.w_cap, torch.float32, "w_cap"))
             if sp.scalar.clock:
                 a.w_time = _ptr(_dev(cache.w_time, torch.float32, "w_time"))
-    if sp.name == "sdvrp":  # the dynamic embedding, folded to three vectors (cache.fold_dynamic)
-        if cache.unfold:
-            raise ValueError("the unfolded parity mode serves tsp / cvrp")
+    if cache.unfold and not sp.unfold:
+        raise ValueError("the unfolded parity mode serves tsp / cvrp")
+    if sp.dynamic is not None:  # the dynamic embedding, folded to three vectors (cache.fold_dynamic)
         dyn = _dev(cache.dyn, torch.float32, "dyn")
         if tuple(dyn.shape) != (3, 128):
             raise ValueError(f"cache.dyn must be [3, 128], got {tuple(dyn.shape)}")
-        a.dyn_vectors = dyn.data_ptr()
+        setattr(a, sp.dynamic.slot, dyn.data_ptr())
     if sp.feats is not None:  # several running scalars: their folded context vectors, one row each (cache.fold_features)
-        if cache.unfold:
-            raise ValueError("the unfolded parity mode serves tsp / cvrp")
         feat = _dev(cache.feat, torch.float32, "feat")
         if tuple(feat.shape) != (len(sp.feats.names), 128):
             raise ValueError(f"cache.feat must be [{len(sp.feats.names)}, 128], got {tuple(feat.shape)}")
@@ -500,8 +498,9 @@ def env_replay(env_name: str, state: dict, actions: Tensor, rem_base: Tensor | N
     capacity / length / prize), ``now`` (CVRPTW), ``mask_bits`` [B,T,W] int32 on request. The `evaluate` decoding's state
     sequence (decoding.py:448-461)."""
     sp = spec(env_name)
-    if sp.name not in SPECS:
-        raise NotImplementedError(f"the one-launch replay (rl4co_env_replay) serves {sorted(SPECS)}, not {sp.name}: use "
+    if not sp.replay:
+        served = sorted(name for name, s in SPECS.items() if s.replay)
+        raise NotImplementedError(f"the one-launch replay (rl4co_env_replay) serves {served}, not {sp.name}: use "
                                   "env_replay_stepwise")
     b, n = state["action_mask"].shape
     acts = _dev(actions, torch.int64, "actions")

@@ -222,150 +222,77 @@ def _train_kernels_active(x: Tensor) -> bool:
             and torch.get_autocast_dtype("cuda") in (torch.bfloat16, torch.float16))
 
 
-class _TSPInit(nn.Module):
-    """env_embeddings/init.py:55-68"""
+class _InitEmbedding(nn.Module):
+    """env_embeddings/init.py, by the record's ``init`` mode (envspec.py): "all" every node through ``init_embed`` (55-68);
+    "depot" the depot (x, y) through ``init_embed_depot``, the customers (x, y, the record's feature columns) through
+    ``init_embed`` (115-153, 254-312, 363-379); "pairs" depot (x, y) | pickups (x, y, x', y' of the delivery) | deliveries (x, y),
+    a layer each (335-360). Layers are created in the reference's order."""
 
-    def __init__(self, embed_dim):
+    def __init__(self, env_name, embed_dim):
         super().__init__()
-        self.init_embed = nn.Linear(2, embed_dim, True)
-
-    def forward(self, td):
-        locs = td["locs"]
-        if _train_kernels_active(locs):
-            from . import train_ops
-
-            return train_ops.init_embed(locs, self.init_embed)
-        return self.init_embed(locs)
-
-
-class _VRPInit(nn.Module):
-    """env_embeddings/init.py:115-136"""
-
-    def __init__(self, embed_dim):
-        super().__init__()
-        self.init_embed = nn.Linear(3, embed_dim, True)
-        self.init_embed_depot = nn.Linear(2, embed_dim, True)
-
-    def forward(self, td):
-        locs = td["locs"]
-        feats = torch.cat((locs[:, 1:, :], td["demand"][..., None]), -1)
-        if _train_kernels_active(locs):
-            from . import train_ops
-
-            return torch.cat((train_ops.init_embed(locs[:, :1, :], self.init_embed_depot),
-                              train_ops.init_embed(feats, self.init_embed)), -2)
-        return torch.cat((self.init_embed_depot(locs[:, :1, :]), self.init_embed(feats)), -2)
-
-
-class _MTSPInit(nn.Module):
-    """env_embeddings/init.py:363-379: the VRP embedding without a customer feature"""
-
-    def __init__(self, embed_dim):
-        super().__init__()
-        self.init_embed = nn.Linear(2, embed_dim, True)
-        self.init_embed_depot = nn.Linear(2, embed_dim, True)
-
-    def forward(self, td):
-        locs = td["locs"]
-        if _train_kernels_active(locs):
-            from . import train_ops
-
-            return torch.cat((train_ops.init_embed(locs[:, :1, :], self.init_embed_depot),
-                              train_ops.init_embed(locs[:, 1:, :].contiguous(), self.init_embed)), -2)
-        return torch.cat((self.init_embed_depot(locs[:, :1, :]), self.init_embed(locs[:, 1:, :])), -2)
-
-
-class _OPInit(_VRPInit):
-    """env_embeddings/init.py:254-280: as the VRP embedding with the customers' PRIZE as third feature"""
-
-    def forward(self, td):
-        locs = td["locs"]
-        feats = torch.cat((locs[:, 1:, :], td["prize"][..., 1:, None]), -1)
-        if _train_kernels_active(locs):
-            from . import train_ops
-
-            return torch.cat((train_ops.init_embed(locs[:, :1, :], self.init_embed_depot),
-                              train_ops.init_embed(feats, self.init_embed)), -2)
-        return torch.cat((self.init_embed_depot(locs[:, :1, :]), self.init_embed(feats)), -2)
-
-
-class _PCTSPInit(nn.Module):
-    """env_embeddings/init.py:283-312: customers (x, y, expected prize, penalty), depot (x, y)"""
-
-    def __init__(self, embed_dim):
-        super().__init__()
-        self.init_embed = nn.Linear(4, embed_dim, True)
-        self.init_embed_depot = nn.Linear(2, embed_dim, True)
-
-    def forward(self, td):
-        locs = td["locs"]
-        feats = torch.cat((locs[:, 1:, :], td["expected_prize"][..., None], td["penalty"][..., 1:, None]), -1)
-        if _train_kernels_active(locs):
-            from . import train_ops
-
-            return torch.cat((train_ops.init_embed(locs[:, :1, :], self.init_embed_depot),
-                              train_ops.init_embed(feats, self.init_embed)), -2)
-        return torch.cat((self.init_embed_depot(locs[:, :1, :]), self.init_embed(feats)), -2)
-
-
-class _VRPTWInit(nn.Module):
-    """env_embeddings/init.py:139-153: customers (x, y, demand, tw start, tw end, service time), depot (x, y)"""
-
-    def __init__(self, embed_dim):
-        super().__init__()
-        self.init_embed = nn.Linear(6, embed_dim, True)
-        self.init_embed_depot = nn.Linear(2, embed_dim, True)
-
-    def forward(self, td):
-        locs = td["locs"]
-        feats = torch.cat((locs[:, 1:, :], td["demand"][..., None], td["time_windows"][..., 1:, :].to(locs.dtype),
-                           td["durations"][..., 1:, None].to(locs.dtype)), -1)
-        if _train_kernels_active(locs):
-            from . import train_ops
-
-            return torch.cat((train_ops.init_embed(locs[:, :1, :], self.init_embed_depot),
-                              train_ops.init_embed(feats, self.init_embed)), -2)
-        return torch.cat((self.init_embed_depot(locs[:, :1, :]), self.init_embed(feats)), -2)
-
-
-class _VRPTWContext(nn.Module):
-    """env_embeddings/context.py:152-166: current node embedding, remaining capacity, current time"""
-
-    def __init__(self, embed_dim):
-        super().__init__()
-        self.project_context = nn.Linear(embed_dim + 2, embed_dim, bias=False)
-
-
-class _PDPInit(nn.Module):
-    """env_embeddings/init.py:335-360: depot (x, y) | pickups (x, y, x', y' of the delivery) | deliveries (x, y)"""
-
-    def __init__(self, embed_dim):
-        super().__init__()
-        self.init_embed_depot = nn.Linear(2, embed_dim, True)
-        self.init_embed_pick = nn.Linear(4, embed_dim, True)
-        self.init_embed_delivery = nn.Linear(2, embed_dim, True)
+        self.env_name = env_name
+        sp = spec(env_name)
+        if sp.init == "pairs":
+            self.init_embed_depot = nn.Linear(2, embed_dim, True)
+            self.init_embed_pick = nn.Linear(4, embed_dim, True)
+            self.init_embed_delivery = nn.Linear(2, embed_dim, True)
+            return
+        self.init_embed = nn.Linear(2 + sp.feature_width, embed_dim, True)
+        if sp.init == "depot":
+            self.init_embed_depot = nn.Linear(2, embed_dim, True)
 
     def features(self, td):
-        locs = td["locs"]
-        half = (locs.shape[-2] - 1) // 2
-        pick = torch.cat((locs[:, 1 : half + 1, :], locs[:, half + 1 :, :]), -1)
-        return ((locs[:, :1, :], self.init_embed_depot), (pick, self.init_embed_pick),
-                (locs[:, half + 1 :, :], self.init_embed_delivery))
+        """(input, layer) of every group of nodes, in node order."""
+        sp, locs = spec(self.env_name), td["locs"]
+        if sp.init == "all":
+            return ((locs, self.init_embed),)
+        if sp.init == "pairs":
+            half = (locs.shape[-2] - 1) // 2
+            pick = torch.cat((locs[:, 1 : half + 1, :], locs[:, half + 1 :, :]), -1)
+            return ((locs[:, :1, :], self.init_embed_depot), (pick, self.init_embed_pick),
+                    (locs[:, half + 1 :, :], self.init_embed_delivery))
+        cols = customer_features(sp, td, locs.dtype)
+        customers = torch.cat((locs[:, 1:, :], *cols), -1) if cols else locs[:, 1:, :]
+        return ((locs[:, :1, :], self.init_embed_depot), (customers, self.init_embed))
 
     def forward(self, td):
         if _train_kernels_active(td["locs"]):
             from . import train_ops
 
-            return torch.cat([train_ops.init_embed(f.contiguous(), lin) for f, lin in self.features(td)], -2)
-        return torch.cat([lin(f) for f, lin in self.features(td)], -2)
+            out = [train_ops.init_embed(f, lin) for f, lin in self.features(td)]
+        else:
+            out = [lin(f) for f, lin in self.features(td)]
+        return out[0] if len(out) == 1 else torch.cat(out, -2)
 
 
-class _NodeContext(nn.Module):
-    """env_embeddings/context.py:232-243 (PDP): the current node embedding alone"""
+class _ContextEmbedding(nn.Module):
+    """env_embeddings/context.py:105-280 — parameters only; the arithmetic is in the kernel. ``project_context`` takes the
+    current node's embedding and, by the record (envspec.py): the first node's (+ ``W_placeholder`` for step 0), the context
+    scalar (and the clock), or ``proj_dynamic_feats`` of several running scalars (folded: cache.fold_features)."""
 
-    def __init__(self, embed_dim):
+    def __init__(self, env_name, embed_dim):
         super().__init__()
-        self.project_context = nn.Linear(embed_dim, embed_dim, bias=False)
+        sp = spec(env_name)
+        if sp.ctx_first or sp.feats is not None:
+            width = 2 * embed_dim
+        else:
+            width = embed_dim + (0 if sp.scalar is None else 2 if sp.scalar.clock else 1)
+        self.project_context = nn.Linear(width, embed_dim, bias=False)
+        if sp.ctx_first:
+            self.W_placeholder = nn.Parameter(torch.Tensor(2 * embed_dim).uniform_(-1, 1))
+        if sp.feats is not None:
+            setattr(self, sp.feats.weight, nn.Linear(len(sp.feats.names), embed_dim, bias=False))
+
+
+class _DynamicEmbedding(nn.Module):
+    """env_embeddings/dynamic.py:47-78 — parameters only. StaticEmbedding: none; a record with ``dynamic``: Linear(1 -> 3 *
+    128) on its state tensor (SDVRP: the remaining demand), the kernel adds d_j (x . u) (cache.fold_dynamic)."""
+
+    def __init__(self, env_name, embed_dim):
+        super().__init__()
+        sp = spec(env_name)
+        if sp.dynamic is not None:
+            setattr(self, sp.dynamic.weight, nn.Linear(1, 3 * embed_dim, bias=False))
 
 
 class AttentionModelEncoder(nn.Module):
@@ -375,48 +302,12 @@ class AttentionModelEncoder(nn.Module):
                  feedforward_hidden=512):
         super().__init__()
         self.env_name = env_name = canonical_env(env_name)
-        self.init_embedding = {"tsp": _TSPInit, "cvrp": _VRPInit, "op": _OPInit, "pctsp": _PCTSPInit,
-                               "pdp": _PDPInit, "cvrptw": _VRPTWInit, "sdvrp": _VRPInit, "mtsp": _MTSPInit}[env_name](embed_dim)
+        self.init_embedding = _InitEmbedding(env_name, embed_dim)
         self.net = _GraphAttentionNetwork(num_heads, embed_dim, num_layers, normalization, feedforward_hidden)
 
     def forward(self, td):
         init_h = self.init_embedding(td)
         return self.net(init_h), init_h
-
-
-class _TSPContext(nn.Module):
-    """env_embeddings/context.py:105-134 — parameters only; the arithmetic is in the kernel."""
-
-    def __init__(self, embed_dim):
-        super().__init__()
-        self.project_context = nn.Linear(2 * embed_dim, embed_dim, bias=False)
-        self.W_placeholder = nn.Parameter(torch.Tensor(2 * embed_dim).uniform_(-1, 1))
-
-
-class _VRPContext(nn.Module):
-    """env_embeddings/context.py:137-149"""
-
-    def __init__(self, embed_dim):
-        super().__init__()
-        self.project_context = nn.Linear(embed_dim + 1, embed_dim, bias=False)
-
-
-class _MTSPContext(nn.Module):
-    """env_embeddings/context.py:246-280 — parameters only: the current node's embedding and ``proj_dynamic_feats`` of the
-    four running scalars, side by side into ``project_context`` (folded: cache.fold_features)."""
-
-    def __init__(self, embed_dim):
-        super().__init__()
-        self.project_context = nn.Linear(2 * embed_dim, embed_dim, bias=False)
-        self.proj_dynamic_feats = nn.Linear(4, embed_dim, bias=False)
-
-
-class _SDVRPDynamic(nn.Module):
-    """env_embeddings/dynamic.py:60-78 — parameters only; the kernel adds d_j (x . u) (cache.fold_dynamic)."""
-
-    def __init__(self, embed_dim):
-        super().__init__()
-        self.projection = nn.Linear(1, 3 * embed_dim, bias=False)
 
 
 class _Pointer(nn.Module):
@@ -438,11 +329,8 @@ class AttentionModelDecoder(nn.Module):
         self.num_heads = num_heads
         self.mask_inner = mask_inner
         self.check_nan = check_nan
-        self.context_embedding = {"tsp": _TSPContext, "cvrp": _VRPContext, "op": _VRPContext, "pctsp": _VRPContext,
-                                  "pdp": _NodeContext, "cvrptw": _VRPTWContext, "sdvrp": _VRPContext,
-                                  "mtsp": _MTSPContext}[env_name](embed_dim)
-        # StaticEmbedding (dynamic.py:47-57): no parameters; SDVRP: Linear(1 -> 3 * 128) on the remaining demand
-        self.dynamic_embedding = _SDVRPDynamic(embed_dim) if env_name == "sdvrp" else nn.Module()
+        self.context_embedding = _ContextEmbedding(env_name, embed_dim)
+        self.dynamic_embedding = _DynamicEmbedding(env_name, embed_dim)
         self.pointer = _Pointer(embed_dim)
         self.project_node_embeddings = nn.Linear(embed_dim, 3 * embed_dim, bias=False)
         self.project_fixed_context = nn.Linear(embed_dim, embed_dim, bias=False)
@@ -454,15 +342,23 @@ class AttentionModelDecoder(nn.Module):
         return build_folded_cache(
             self.env_name, h,
             w_node=self.project_node_embeddings.weight,
-            w_out=self.pointer.project_out.weight,
-            w_ctx=self.context_embedding.project_context.weight,
             w_fixed=self.project_fixed_context.weight if self.use_graph_context else None,
-            w_placeholder=getattr(self.context_embedding, "W_placeholder", None),
             cache_dtype=cache_dtype,
             gemm_dtype=gemm_dtype,
             fold=fold,
-            w_dyn=getattr(getattr(self.dynamic_embedding, "projection", None), "weight", None),
-            w_feat=getattr(getattr(self.context_embedding, "proj_dynamic_feats", None), "weight", None),
+            **self.constant_weights(),
+        )
+
+    def constant_weights(self) -> dict:
+        """The weights behind the cache's batch-shared vectors (the arguments of ``cache.fold_constants``)."""
+        sp = spec(self.env_name)
+        ctx = self.context_embedding
+        return dict(
+            w_ctx=ctx.project_context.weight,
+            w_out=self.pointer.project_out.weight,
+            w_placeholder=getattr(ctx, "W_placeholder", None),
+            w_dyn=getattr(self.dynamic_embedding, sp.dynamic.weight).weight if sp.dynamic is not None else None,
+            w_feat=getattr(ctx, sp.feats.weight).weight if sp.feats is not None else None,
         )
 
 
@@ -592,19 +488,10 @@ class AttentionModelPolicy(nn.Module):
         from . import train_ops as T
 
         enc = self.encoder
-        init = enc.init_embedding
         bf = self._encoder_regime()  # the 16-bit autocast type this rollout computes in (bfloat16 or float16)
         assert bf in (torch.bfloat16, torch.float16)
-        embed = lambda f, lin: T.init_embed(f, lin, dtype=bf)  # noqa: E731
-        sp, locs = spec(self.env_name), td["locs"]
-        if hasattr(init, "features"):  # PDP: depot | pickups | deliveries, an embedding each
-            x = torch.cat([embed(f.contiguous(), lin) for f, lin in init.features(td)], -2)
-        elif sp.depot_embed:
-            feats = torch.cat((locs[:, 1:, :], *customer_features(sp, td)), -1)
-            x = torch.cat((embed(locs[:, :1, :], init.init_embed_depot), embed(feats, init.init_embed)), -2)
-        else:
-            x = embed(locs, init.init_embed)
-        init_h = x
+        x = [T.init_embed(f, lin, dtype=bf) for f, lin in enc.init_embedding.features(td)]  # an embedding per node group
+        init_h = x = x[0] if len(x) == 1 else torch.cat(x, -2)
         b, n, d = x.shape
         for layer in enc.net.layers:
             attn, norm1, ffn, norm2 = layer[0].module, layer[1].normalizer, layer[2].module, layer[3].normalizer
@@ -709,7 +596,7 @@ class AttentionModelPolicy(nn.Module):
         # fp32 regime (no autocast: the bit-identical configuration): the exact-fp32 MFMA encoder (csrc/am_encoder_f32.hip),
         # planes in any type, also with fold=False (tsp / cvrp: the reference's own association of the decoder)
         use_fused_f32 = (self.fused_encoder and self._encoder_regime() is None and not grad_path and td["locs"].is_cuda
-                         and (self.fold or self.env_name in ("tsp", "cvrp")) and ie_ok
+                         and (self.fold or spec(self.env_name).unfold) and ie_ok
                          and self._packed_encoder().supported(td, torch.float32))
         if use_fused_f32:
             use_fused, regime16 = True, torch.float32
@@ -840,12 +727,13 @@ class AttentionModelPolicy(nn.Module):
         device = td["action_mask"].device
         b_inst, n = td["action_mask"].shape[0], td["action_mask"].shape[-1]
         b = b_inst * max(n_rep, 1)
-        if self.env_name == "mtsp":  # (DESIGN: what the min-max environment is not served with)
+        sp = spec(self.env_name)
+        if sp.state_reward:  # (DESIGN: what the min-max environment is not served with)
             if n_rep > 0:
-                raise NotImplementedError("mtsp: multistart / multisample rollouts are not served (the multistart variant "
+                raise NotImplementedError(f"{sp.name}: multistart / multisample rollouts are not served (the multistart variant "
                                           "does not carry the four-scalar context; one trajectory per instance)")
             if decoding_kwargs.get("_defer_finish"):
-                raise NotImplementedError("mtsp: captured-graph rollouts are not served (the padding step of the finished "
+                raise NotImplementedError(f"{sp.name}: captured-graph rollouts are not served (the padding step of the finished "
                                           "rows follows the rollout's read-back)")
         top_k, top_p = K.decoding_filter(opt.top_k, opt.top_p, n)
         filtered = bool(top_k or top_p)
@@ -873,7 +761,7 @@ class AttentionModelPolicy(nn.Module):
         self.last_ctx_elem_bytes = cache.ctx_cur.element_size() if cache.ctx_cur is not None else 4
         state = self._initial_state(td, n_rep)
         horizon = min(self._max_horizon(self.env_name, n), max_steps)
-        if self.env_name == "pdp" and not getattr(env, "force_start_at_depot", False):
+        if sp.depot_flag is not None and not getattr(env, sp.depot_flag, False):
             horizon = min(horizon, n - 1)  # the depot is never visited: exactly one step per location (no padding
             #                                column: a trailing 0 would read as a depot visit in check_solution_validity)
         # status words read back ONCE per rollout: [sticky error bits, -, longest trajectory, streamed instance-steps,
@@ -943,7 +831,7 @@ class AttentionModelPolicy(nn.Module):
         # possible rollout and trailing zeros would change the association of the reference-ordered sums, so the kernel
         # takes the real horizon from the device (the decode launch's own step count, kernels.tour_length(horizon=))
         td_early = reward_early = None
-        if (native_env and self.env_name in ("tsp", "pdp", "cvrp", "cvrptw", "sdvrp") and calc_reward and mode != "evaluate"
+        if (native_env and sp.length_reward and calc_reward and mode != "evaluate"
                 and (checked or not env.check_solution) and not (n_rep > 0 and select_best)
                 and env.accepts_reward_horizon()):
             td_early = self._final_td(td, state, n_rep)
@@ -981,39 +869,15 @@ class AttentionModelPolicy(nn.Module):
         differentiable re-evaluation of a training step, best-of selection, reward and the output dict (constructive/base.py:
         240-263). Re-runnable: ``graph.GraphedRollout`` calls it after every replay of the captured launches — it only reads
         the buffers they wrote (``r``: what ``_forward`` enqueued)."""
-        out_actions, logps, all_logps, td_early, reward_early = r.launched  # re-runnable: a graph replay refills the same buffers
-        status = r.status
-        t0 = r.t0
-        td = r.td
-        env = r.env
-        state = r.state
-        n_rep = r.n_rep
-        b_inst = r.b_inst
-        n = r.n
-        device = r.device
-        grad_path = r.grad_path
-        cache_g = r.cache_g
-        cache = r.cache
-        cache_dtype = r.cache_dtype
-        hidden = r.hidden
-        init_embeds = r.init_embeds
-        mask_logits = r.mask_logits
-        tanh_clipping = r.tanh_clipping
-        temperature = r.temperature
-        return_entropy = r.return_entropy
-        select_best = r.select_best
-        calc_reward = r.calc_reward
-        checked = r.checked
-        return_sum_log_likelihood = r.return_sum_log_likelihood
-        return_actions = r.return_actions
-        return_all_logp = r.return_all_logp
-        return_hidden = r.return_hidden
-        return_init_embeds = r.return_init_embeds
         from . import _lib as _l
 
+        out_actions, logps, all_logps, td_early, reward_early = r.launched  # re-runnable: a graph replay refills the same buffers
+        status, t0, td, env, state, n_rep, device = r.status, r.t0, r.td, r.env, r.state, r.n_rep, r.device
+        grad_path, cache_g, hidden, return_entropy = r.grad_path, r.cache_g, r.hidden, r.return_entropy
+        sp = spec(self.env_name)
         self._drain_status()  # an earlier training step's words (copied long ago: no wait) — its assertions come first
-        if (self.async_train_status and grad_path and cache_g is not None and self.env_name == "tsp" and status.is_cuda
-                and not select_best):
+        if (self.async_train_status and grad_path and cache_g is not None and sp.fixed_horizon and status.is_cuda
+                and not r.select_best):
             # fixed horizon: nothing below depends on the status words; they travel to pinned memory behind the launches
             if len(self._status_host) < 2:
                 self._status_host.append(torch.empty(6, dtype=torch.int32, pin_memory=True))
@@ -1039,11 +903,11 @@ class AttentionModelPolicy(nn.Module):
             all_logps = all_logps[:, :t_used]
 
         # td mirrors the reference's final state (batchified rows when multistart)
-        if self.env_name == "mtsp":
+        if sp.state_reward:
             self._mtsp_pad_finished(state, out_actions)
         td_out = td_early if td_early is not None else self._final_td(td, state, n_rep)
         td_out.set("action", out_actions[:, -1])
-        if self.env_name == "mtsp":  # the reference's loop counter and first action (state keys the kernels do not need)
+        if sp.state_reward:  # the reference's loop counter and first action (state keys its reward reads, the kernels do not)
             td_out.set("i", torch.full((out_actions.shape[0],), out_actions.shape[1], dtype=torch.int64, device=device))
             td_out.set("first_node", out_actions[:, 0].clone())
 
@@ -1055,10 +919,10 @@ class AttentionModelPolicy(nn.Module):
 
             if self._bwd_err is None or self._bwd_err.device != device:
                 self._bwd_err = torch.zeros(1, dtype=torch.int32, device=device)
-            meta = dict(t0=t0, mask_inner=self.decoder.mask_inner, mask_logits=mask_logits, err_sink=self._bwd_err,
-                        tanh_clipping=tanh_clipping, temperature=temperature, teacher_variant=self.teacher_variant)
-            meta.update((k, td[k]) for k in spec(self.env_name).teacher_keys)  # the instance data the backward replays on
-            step_logps = teacher.teacher_forced_logps(self.env_name, cache_g, cache, out_actions, logps, meta)
+            meta = dict(t0=t0, mask_inner=self.decoder.mask_inner, mask_logits=r.mask_logits, err_sink=self._bwd_err,
+                        tanh_clipping=r.tanh_clipping, temperature=r.temperature, teacher_variant=self.teacher_variant)
+            meta.update((k, td[k]) for k in sp.teacher_keys)  # the instance data the backward replays on
+            step_logps = teacher.teacher_forced_logps(self.env_name, cache_g, r.cache, out_actions, logps, meta)
         elif grad_path:
             kept = r.kept_bits[:, :t_used].contiguous() if r.kept_bits is not None else None
             if kept is not None and hidden.is_cuda and self.fused_backward:
@@ -1066,41 +930,38 @@ class AttentionModelPolicy(nn.Module):
                                  f"teacher-forced backward for {self.env_name}: the top-k / top-p filter is not in the backward "
                                  "kernels — dense re-evaluation of all steps with autograd, the rollout's kept sets as the logit mask")
             elif hidden.is_cuda and self.fused_backward and not return_entropy:
-                from . import _lib as _l
-
                 t_max = __import__("rl4co_amd.teacher", fromlist=["max_nodes"]).max_nodes()
-                why = ("the dynamic embedding (remaining demand in keys and values) is not in the backward kernels" if self.env_name == "sdvrp" else
-                       "the four-scalar context (proj_dynamic_feats) and the min-max state are not in the backward kernels" if self.env_name == "mtsp" else
+                why = (sp.no_teacher if sp.no_teacher is not None else
                        "fold=False keeps the reference's per-step association, which the backward kernels do not implement" if not self.fold else
-                       f"{n} nodes are beyond the kernels' limit ({t_max})" if n > t_max else
-                       f"{cache_dtype} planes are not served by the backward kernels (float32, bfloat16 or float16 planes) for this call")
-                _l.warn_fallback(f"teacher/{self.env_name}/{n}/{cache_dtype}",
+                       f"{r.n} nodes are beyond the kernels' limit ({t_max})" if r.n > t_max else
+                       f"{r.cache_dtype} planes are not served by the backward kernels (float32, bfloat16 or float16 planes) for this call")
+                _l.warn_fallback(f"teacher/{self.env_name}/{r.n}/{r.cache_dtype}",
                                  f"teacher-forced backward for {self.env_name}: {why} — dense re-evaluation of all steps with autograd "
                                  "(16-bit regimes: glimpse attention and log-prob kernels between library GEMMs; fp32: torch)")
-            step_logps = self.evaluate_log_probs(td, hidden, out_actions, n_rep, tanh_clipping, temperature,
-                                                 mask_logits, skip_first=(t0 == 1), return_full=return_entropy, kept_bits=kept)
+            step_logps = self.evaluate_log_probs(td, hidden, out_actions, n_rep, r.tanh_clipping, r.temperature,
+                                                 r.mask_logits, skip_first=(t0 == 1), return_full=return_entropy, kept_bits=kept)
             if return_entropy:
                 step_logps, full_logp = step_logps
         else:
             step_logps = logps
 
-        if n_rep > 0 and select_best:
+        if n_rep > 0 and r.select_best:
             rewards = env.get_reward(td_out, out_actions)
-            best = rewards.view(n_rep, b_inst).transpose(0, 1).max(dim=-1)[1]  # unbatchify + max
-            rows = best * b_inst + torch.arange(b_inst, device=device)
+            best = rewards.view(n_rep, r.b_inst).transpose(0, 1).max(dim=-1)[1]  # unbatchify + max
+            rows = best * r.b_inst + torch.arange(r.b_inst, device=device)
             out_actions, logps, step_logps = out_actions[rows], logps[rows], step_logps[rows]
             if all_logps is not None:
                 all_logps = all_logps[rows]
             if full_logp is not None:
                 full_logp = full_logp[rows]
             td_out = td_out[rows] if hasattr(td_out, "__getitem__") else td_out
-            reward = rewards[rows] if calc_reward else None
+            reward = rewards[rows] if r.calc_reward else None
         elif reward_early is not None:
             reward = reward_early
         else:
-            reward = (env.get_reward(td_out, out_actions, check_solution=False if checked else None)
-                      if calc_reward else td_out.get("reward", None))
-        if calc_reward:
+            reward = (env.get_reward(td_out, out_actions, check_solution=False if r.checked else None)
+                      if r.calc_reward else td_out.get("reward", None))
+        if r.calc_reward:
             td_out.set("reward", reward)
         # decoding.py:56: on the kernel path this is the RL4CO_EBIT_NEG_INF_LOGP sticky bit (already
         # raised above); only the autograd re-evaluation needs its own check
@@ -1108,9 +969,9 @@ class AttentionModelPolicy(nn.Module):
             raise AssertionError("Logprobs should not be -inf, check sampling procedure!")
         outdict = {
             "reward": reward,
-            "log_likelihood": step_logps.sum(1) if return_sum_log_likelihood else step_logps,
+            "log_likelihood": step_logps.sum(1) if r.return_sum_log_likelihood else step_logps,
         }
-        if return_actions:
+        if r.return_actions:
             outdict["actions"] = out_actions
         if return_entropy:
             # ops.py:103-111 on the [B, T, N] log-probs. Under autograd the reference's entropy carries history (PPO's
@@ -1123,12 +984,12 @@ class AttentionModelPolicy(nn.Module):
             entropy = -(lp.exp() * lp).sum(dim=-1).sum(dim=1)
             assert entropy.isfinite().all(), "Entropy is not finite"
             outdict["entropy"] = entropy
-        if return_all_logp:
+        if r.return_all_logp:
             outdict["all_logp"] = all_logps
-        if return_hidden:
+        if r.return_hidden:
             outdict["hidden"] = hidden
-        if return_init_embeds:
-            outdict["init_embeds"] = init_embeds
+        if r.return_init_embeds:
+            outdict["init_embeds"] = r.init_embeds
         return outdict
 
     def _drain_status(self) -> None:
@@ -1170,9 +1031,9 @@ class AttentionModelPolicy(nn.Module):
         rows = (pad > 0).nonzero()[:, 0]  # (behind the rollout's read-back: the host is in step already)
         if rows.numel() == 0:
             return
-        sp = spec("mtsp")
+        sp = spec(self.env_name)
         part = {f.key: state[f.key][rows].contiguous() for f in sp.fields}  # the padded rows alone, instance data included
-        K.env_step("mtsp", part, torch.zeros(rows.numel(), dtype=torch.int64, device=actions.device),
+        K.env_step(sp.name, part, torch.zeros(rows.numel(), dtype=torch.int64, device=actions.device),
                    K.new_error_word(actions.device))
         part["agent_idx"] += pad[rows] - 1
         for key in sp.keys("traj"):
@@ -1212,12 +1073,13 @@ class AttentionModelPolicy(nn.Module):
         # 16-bit regime on the GPU: the masked glimpse attention of all steps on csrc/am_cross_attn.hip (keys shared by the
         # starts of an instance, the mask as bits from the same replay launch); otherwise torch's SDPA in fp32
         regime = self._encoder_regime()
-        dynamic = self.env_name == "sdvrp"  # keys and values move with the state: torch, in the reference's association
-        stepwise = spec(self.env_name).feats is not None  # mTSP: the four running scalars tabulated step by step
+        sp = spec(self.env_name)
+        dynamic = sp.dynamic is not None  # keys and values move with the state: torch, in the reference's association
+        stepwise = sp.feats is not None  # mTSP: the four running scalars tabulated step by step
         glimpse_kernel = (hidden.is_cuda and regime in (torch.bfloat16, torch.float16) and dec.mask_inner and dec.num_heads == 8
                           and d == 128 and self.fused_backward and not dynamic and not stepwise)
         if dynamic:
-            masks, ctx_nodes, extras, demands = self._replay_by(K.env_replay_stepwise, td, actions, n_rep, False, record="demand_with_depot")
+            masks, ctx_nodes, extras, demands = self._replay_by(K.env_replay_stepwise, td, actions, n_rep, False, record=sp.dynamic.key)
             mask_bits = None
         elif stepwise:
             masks, ctx_nodes, extras, mask_bits = self._replay_stepwise(td, actions, n_rep)
@@ -1225,7 +1087,6 @@ class AttentionModelPolicy(nn.Module):
             masks, ctx_nodes, extras, mask_bits = self._replay(td, actions, n_rep, mask_bits=glimpse_kernel)
         h = hidden if s == 1 else hidden.unsqueeze(0).expand(s, b_inst, n, d).reshape(b, n, d)
         w_ctx = dec.context_embedding.project_context.weight
-        sp = spec(self.env_name)
         if sp.ctx_first:
             first, prev = ctx_nodes  # [B,T] each (t = 0 is the placeholder)
             idx = torch.stack([first, prev], -1).view(b, t_len * 2)
@@ -1253,7 +1114,7 @@ class AttentionModelPolicy(nn.Module):
             # zoo/am/decoder.py:142-152: (K, V, L) + projection(remaining demand, the depot's taken as 0), per step
             dem = demands.clone()
             dem[..., 0] = 0
-            dk, dv, dl = dec.dynamic_embedding.projection(dem[..., None]).chunk(3, dim=-1)  # [B, T, N, 128] each
+            dk, dv, dl = getattr(dec.dynamic_embedding, sp.dynamic.weight)(dem[..., None]).chunk(3, dim=-1)  # [B, T, N, 128] each
             split = lambda x: x.view(b, t_len, n, nh, d // nh).transpose(2, 3)  # noqa: E731
             kh, vh, k_lt = split(k_g[:, None] + dk), split(v_g[:, None] + dv), k_l[:, None] + dl
             attn_mask = masks[:, :, None, None, :] if dec.mask_inner else None

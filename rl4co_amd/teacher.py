@@ -16,7 +16,7 @@ from torch import Tensor
 
 from . import _lib
 from .cache import EMBED_DIM, FoldedCache, fold_weights
-from .envspec import spec
+from .envspec import SPECS, spec
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -56,7 +56,7 @@ def supports(env_name: str, cache_dtype: torch.dtype, num_nodes: int) -> bool:
     return env_name in TEACHER_ENVS
 
 
-TEACHER_ENVS = ("tsp", "cvrp", "op", "pctsp", "pdp", "cvrptw")
+TEACHER_ENVS = tuple(name for name, sp in SPECS.items() if sp.teacher)  # (a view of the table: envspec.py)
 
 
 def _require_served(env_name: str) -> None:
@@ -82,18 +82,17 @@ def run_backward(cache: FoldedCache, actions: Tensor, grad_logp: Tensor, meta: d
     b, t = actions.shape
     b_inst, n = cache.num_instances, cache.num_nodes
     dev = actions.device
-    tsp = cache.env_name == "tsp"
+    sp = spec(cache.env_name)
     f32 = dict(dtype=torch.float32, device=dev)
     d_kvl = torch.empty((3, b_inst, n, EMBED_DIM), **f32) if d_planes is None else None
     d_ctx_cur = torch.empty((b_inst, n, EMBED_DIM), **f32)
-    d_ctx_first = torch.zeros((b_inst, n, EMBED_DIM), **f32) if tsp else None
+    d_ctx_first = torch.zeros((b_inst, n, EMBED_DIM), **f32) if sp.ctx_first else None
     d_q_bias = torch.empty((b_inst, EMBED_DIM), **f32) if cache.q_bias is not None else None
     d_extra = torch.zeros((EMBED_DIM,), **f32)
     d_time = torch.zeros((EMBED_DIM,), **f32) if cache.w_time is not None else None
     logp = torch.zeros((b, t), **f32) if want_logp else None
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     a = AmTeacherArgs()
-    sp = spec(cache.env_name)
     a.env = sp.env_id
     a.B, a.B_inst, a.N, a.T, a.t0 = b, b_inst, n, t, int(meta["t0"])
     a.mask_inner, a.mask_logits = int(meta["mask_inner"]), int(meta["mask_logits"])
@@ -129,13 +128,13 @@ def run_backward(cache: FoldedCache, actions: Tensor, grad_logp: Tensor, meta: d
     if d_planes is not None:
         # [3, ...]: the three plane gradients; [5, ...] (TSP) / [4, ...] (depot environments): the context-table gradients as
         # well, converted by the kernel into planes 3 / 4 (d_ctx_in_planes) — the fp32 tensors below are then its scratch
-        nblk = 5 if tsp else 4
+        nblk = 5 if sp.ctx_first else 4
         assert d_planes.dtype == cache.kvl.dtype and d_planes.shape[1:] == (b_inst, n, EMBED_DIM) and d_planes.stride(3) == 1
         assert d_planes.shape[0] in (3, nblk)
         a.d_planes_bf16 = d_planes.data_ptr()
         a.d_planes_plane_stride, a.d_planes_batch_stride, a.d_planes_row_stride = d_planes.stride()[:3]
         a.d_ctx_in_planes = int(d_planes.shape[0] == nblk)
-    if tsp:
+    if sp.ctx_first:  # (the step-0 query takes the extra vector's place)
         a.d_q_step0 = d_extra.data_ptr()
     else:
         a.d_w_cap = d_extra.data_ptr()
@@ -163,6 +162,7 @@ def build_cache_autograd(env_name: str, h: Tensor, decoder, fused_planes: bool =
     gradient GEMM and ONE weight-gradient launch on the bf16 gradient matrix the teacher kernel writes in place
     (``TeacherForcedFoldLogLik``): no per-plane autograd nodes, no stack, no fp32 plane gradients, no gradient adds."""
     d = EMBED_DIM
+    first = spec(env_name).ctx_first  # context = (first, current): the blocks end [.., ctx_first, ctx_cur], else [.., ctx_cur]
     w_ctx = decoder.context_embedding.project_context.weight.float()
     blocks = fold_weights(env_name, decoder.project_node_embeddings.weight.float(),
                           decoder.pointer.project_out.weight.float(), w_ctx)
@@ -179,8 +179,8 @@ def build_cache_autograd(env_name: str, h: Tensor, decoder, fused_planes: bool =
         out["kvl"] = planes.permute(2, 0, 1, 3)[:3]                       # [3, B, N, 128] strided view, bf16
         # (r06) the context tables stay columns of the same matrix: the multistart rollout and the MMA teacher backward read
         # 16-bit rows at its row stride and widen them on load (two 68 us fp32 copies per step less)
-        out["ctx_cur"] = planes[:, :, 4 if env_name == "tsp" else 3]
-        if env_name == "tsp":
+        out["ctx_cur"] = planes[:, :, 4 if first else 3]
+        if first:
             out["ctx_first"] = planes[:, :, 3]
     else:
         if h.is_cuda and h.dtype in (torch.bfloat16, torch.float16):
@@ -192,10 +192,10 @@ def build_cache_autograd(env_name: str, h: Tensor, decoder, fused_planes: bool =
             planes = planes[:3] + [p.float() for p in planes[3:]]     # the context tables are read as fp32
         else:
             planes = [torch.matmul(h.float(), w.t()) for w in blocks]
-        out.update(kvl=torch.stack(planes[:3], 0), ctx_cur=planes[4] if env_name == "tsp" else planes[-1])
-        if env_name == "tsp":
+        out.update(kvl=torch.stack(planes[:3], 0), ctx_cur=planes[-1])
+        if first:
             out["ctx_first"] = planes[3]
-    if env_name == "tsp":
+    if first:
         out["q_step0"] = torch.mv(w_ctx, decoder.context_embedding.W_placeholder.float())
     elif w_ctx.shape[1] > d:  # PDP has no context scalar
         out["w_cap"] = w_ctx[:, d]
@@ -286,7 +286,7 @@ def teacher_forced_logps(env_name: str, g: dict[str, Tensor], cache: FoldedCache
                          meta: dict) -> Tensor:
     """Differentiable per-step log-probs of ``actions`` (values = ``logps`` from the rollout)."""
     _require_served(env_name)
-    extra = g["q_step0"] if env_name == "tsp" else g.get("w_cap")  # None for PDP (no context scalar)
+    extra = g["q_step0"] if spec(env_name).ctx_first else g.get("w_cap")  # None for PDP (no context scalar)
     if g.get("fused"):
         return TeacherForcedFoldLogLik.apply(g["h"], g["w_all"], g.get("q_bias"), extra, g.get("w_time"), logps, cache,
                                              actions, meta, g)

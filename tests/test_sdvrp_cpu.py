@@ -85,19 +85,20 @@ def test_envspec_record_and_binding(sdvrp_cpu, monkeypatch):
     from rl4co_amd.policy import AttentionModelPolicy
 
     sp = envspec.spec("sdvrp")
-    assert sp is envspec.DYNAMIC_SPECS["sdvrp"] and sp.env_id == _lib.ENV_SDVRP == 6 and sp.has_depot
-    # ... and the header's value: "(RL4CO_ENV_CVRPTW + 1)" evaluated over the header's own defines
+    assert sp is envspec.SPECS["sdvrp"] and sp.env_id == _lib.ENV_SDVRP == 6 and sp.has_depot
+    # ... and the header's value, a plain integer like the other ids
     import pathlib
     import re
 
     header = (pathlib.Path(__file__).resolve().parents[1] / "include" / "rl4co_amd.h").read_text()
     ids = {k: int(v) for k, v in re.findall(r"#define (RL4CO_ENV_\w+) (\d+)\b", header)}
-    expr = re.search(r"#define RL4CO_ENV_SDVRP (.+)", header).group(1)
-    assert eval(expr, {"__builtins__": {}}, ids) == sp.env_id  # noqa: S307
-    assert sp.env_id not in ids.values()
-    assert "sdvrp" not in envspec.SPECS  # the six static environments of the replay / teacher kernels
+    assert ids["RL4CO_ENV_SDVRP"] == sp.env_id == 6 and list(ids.values()).count(6) == 1
+    # the decode kernels alone serve it: not the unfolded mode, the one-launch replay or the teacher kernels
+    assert not sp.unfold and not sp.replay and not sp.teacher and "dynamic embedding" in sp.no_teacher
+    assert sp.dynamic == ("demand_with_depot", "projection", "dyn_vectors") and sp.dynamic.key in sp.keys("traj")
+    assert sp.length_reward and not sp.state_reward and not sp.fixed_horizon and not sp.ctx_first and sp.init == "depot"
     assert sp.horizon(21) == 126 == AttentionModelPolicy._max_horizon("sdvrp", 21)
-    assert sp.features == (("demand", False),) and sp.passthrough == ("locs", "demand")
+    assert sp.features == (("demand", False, 1),) and sp.passthrough == ("locs", "demand")
     assert callable(getattr(K, sp.step[0])) and set(sp.step[1]) <= set(sp.keys())
     decode = {f[0] for f in _lib.AmDecodeArgs._fields_}
     assert all(f.slot in decode for f in sp.fields) and len({f.slot for f in sp.fields}) == len(sp.fields)
