@@ -105,13 +105,21 @@ def clone_td(td: dict) -> dict:
 
 def decoder_weights(pol) -> dict:
     dec = pol.decoder
-    return dict(
+    w = dict(
         w_node=dec.project_node_embeddings.weight.detach(),
         w_out=dec.pointer.project_out.weight.detach(),
         w_ctx=dec.context_embedding.project_context.weight.detach(),
         w_fixed=dec.project_fixed_context.weight.detach() if dec.use_graph_context else None,
         w_placeholder=getattr(dec.context_embedding, "W_placeholder", None),
     )
+    # SDVRP's dynamic embedding and mTSP's running scalars' layer, where the decoder has them (cache.fold_constants)
+    dyn = getattr(getattr(dec, "dynamic_embedding", None), "projection", None)
+    feat = getattr(dec.context_embedding, "proj_dynamic_feats", None)
+    if dyn is not None:
+        w["w_dyn"] = dyn.weight.detach()
+    if feat is not None:
+        w["w_feat"] = feat.weight.detach()
+    return w
 
 
 def fold_cache(pol, env_name: str, h: torch.Tensor, dtype=torch.float32, device="cpu", fold=True):

@@ -139,7 +139,7 @@ def decoder_step_logps(dec, hidden, st0: dict, actions, tanh_clipping=10.0, temp
         cur = st["current_node"].view(-1)
         h_cur = hidden.gather(1, cur[:, None, None].expand(b, 1, d))[:, 0]
         q = dec.context_embedding.project_context(
-            torch.cat((h_cur, dec.context_embedding.proj_dynamic_feats(features(st))), -1)) + graph
+            torch.cat((h_cur, dec.context_embedding.proj_dynamic_feats(features(st).to(hidden.dtype))), -1)) + graph
         mask = st["action_mask"].bool()
         heads = torch.nn.functional.scaled_dot_product_attention(split(q[:, None]), split(k_g), split(v_g),
                                                                  attn_mask=mask[:, None, None, :])

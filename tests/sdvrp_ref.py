@@ -91,8 +91,8 @@ def decoder_step_logps(dec, hidden, st0: dict, actions, tanh_clipping=10.0, temp
         cur = st["current_node"].view(-1).clone()  # (the state is stepped in place below: autograd keeps these)
         h_cur = hidden.gather(1, cur[:, None, None].expand(b, 1, d))[:, 0]
         rem = (st["vehicle_capacity"].view(-1) - st["used_capacity"].view(-1))[:, None]
-        q = dec.context_embedding.project_context(torch.cat((h_cur, rem), -1)) + graph
-        dem = st["demand_with_depot"].clone()
+        q = dec.context_embedding.project_context(torch.cat((h_cur, rem.to(hidden.dtype)), -1)) + graph
+        dem = st["demand_with_depot"].to(hidden.dtype, copy=True)  # (the decoder may be evaluated in float64)
         dem[:, 0] = 0
         dk, dv, dl = dec.dynamic_embedding.projection(dem[..., None]).chunk(3, dim=-1)
         mask = st["action_mask"].bool().clone()
