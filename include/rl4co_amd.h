@@ -41,8 +41,10 @@ extern "C" {
  *  14: rl4co_am_decode_args carries the split-delivery VRP's dynamic-embedding vectors and per-trajectory remaining
  *      demand (dyn_vectors, demand_state, behind w_time); rl4co_sdvrp_step.
  *  15: rl4co_am_decode_args carries the multi-agent TSP's folded context table and agent counts (mtsp_ctx, num_agents,
- *      behind err); rl4co_mtsp_step. */
-#define RL4CO_ABI_VERSION 15
+ *      behind err); rl4co_mtsp_step.
+ *  16: rl4co_am_decode_beam / rl4co_am_decode_beam_max_width (beam search, rl4co_am_decode_beam_args);
+ *      RL4CO_EBIT_BEAM_INFEASIBLE. */
+#define RL4CO_ABI_VERSION 16
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -68,6 +70,7 @@ extern "C" {
 #define RL4CO_EBIT_TW_DURATION 16384   /* cvrptw/env.py:158 "Service durations must be non-negative."  */
 #define RL4CO_EBIT_TW_EMPTY 32768      /* cvrptw/env.py:159-161 "there are unfeasible time windows"    */
 #define RL4CO_EBIT_TW_DEADLINE 65536   /* cvrptw/env.py:176-179 "vehicle cannot start service before deadline" */
+#define RL4CO_EBIT_BEAM_INFEASIBLE 131072 /* utils/decoding.py:485 "infeasible action selected": beam search kept a -inf candidate (fewer than beam_width finite ones) */
 
 /* ---- enums --------------------------------------------------------------- */
 #define RL4CO_ENV_TSP 0
@@ -468,6 +471,74 @@ int rl4co_am_decode_lds_bytes(int N, int env);
 int rl4co_am_decode_row_groups(const rl4co_am_decode_args* args); /* 0: variant without such a contract (MS) */
 /* The variant (RL4CO_VARIANT_STREAM / _LDS) rl4co_am_decode will run for `args`. */
 int rl4co_am_decode_variant(const rl4co_am_decode_args* args);
+
+/* --------------------------------------------------------------------------
+ * Beam-search decoding: BeamSearch (utils/decoding.py:464-600 — pre_decoder_hook's start nodes, _make_beam_step's
+ * torch.topk over the beam_width * N candidates, the re-indexing of the state by beam parent, _backtrack) with the decode
+ * step of rl4co_am_decode, as ONE launch: one workgroup per instance carries its beam_width beams through the whole
+ * rollout (am_decode_beam.hip). TSP and CVRP; fp32 / bf16 / fp16 planes; fp32 dense context tables.
+ *
+ * Rows are beam-major (s-major, the reference's batchify): row j * B_inst + b is beam j of instance b, in the state
+ * tensors ([beam_width * B_inst, ...], the state AFTER the imposed start step, read at entry and written back at exit) and
+ * in every output. Column 0 of the outputs is the start node (current_node at entry) with log-prob 0 and parent 0; the
+ * decode steps fill columns 1 .. T, T <= max_steps. T is PER INSTANCE: the step at which the instance's last beam is done
+ * (a finished CVRP beam keeps offering the depot at log-prob 0 until then). Columns behind an instance's own T are not
+ * written, in the aligned and in the per-step outputs: zero-initialised actions / logps read as the reference's padding
+ * (depot, log-prob 0); parents / cum_logp there are NOT the padding's values (identity, unchanged). steps_summary[0] is
+ * the batch's longest T. Equal candidates are ordered by the lower flat index parent * N + node.
+ * A beam's per-step log-probs are bit for bit those of rl4co_am_decode(RL4CO_DECODE_EVALUATE, RL4CO_VARIANT_STREAM) on
+ * the same actions. Sticky bits: RL4CO_EBIT_BEAM_INFEASIBLE (fewer than beam_width finite candidates at a step),
+ * RL4CO_EBIT_INFEASIBLE, RL4CO_EBIT_NAN_LOGIT, RL4CO_EBIT_NEG_INF_LOGP, RL4CO_EBIT_MAX_STEPS.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_am_decode_beam_args {
+  int32_t env;         /* RL4CO_ENV_TSP | RL4CO_ENV_CVRP                         */
+  int32_t B_inst;      /* instances (= workgroups)                               */
+  int32_t N;           /* nodes incl. depot                                      */
+  int32_t beam_width;  /* 2 .. rl4co_am_decode_beam_max_width(N)                 */
+  int32_t max_steps;   /* decode steps after the start node, <= out_stride - 1   */
+  int32_t mask_inner;  /* as rl4co_am_decode_args                                */
+  int32_t mask_logits;
+  int32_t cache_dtype; /* RL4CO_DT_F32 | RL4CO_DT_BF16 | RL4CO_DT_F16            */
+  float tanh_clipping;
+  float temperature;
+  /* folded cache, as rl4co_am_decode_args (16-byte aligned planes) */
+  const void* glimpse_key;
+  const void* glimpse_val;
+  const void* logit_key;
+  int64_t kvl_row_stride;
+  int64_t kvl_batch_stride;
+  const float* ctx_first;   /* [B_inst,N,128] TSP                                          */
+  const float* ctx_cur;     /* [B_inst,N,128]                                              */
+  const float* q_bias;      /* [B_inst,128] or NULL                                        */
+  const float* q_step0;     /* [128] TSP                                                   */
+  const float* w_cap;       /* [128] CVRP                                                  */
+  /* environment state of the beam_width * B_inst beam rows (the slots of rl4co_am_decode_args) */
+  uint8_t* action_mask;     /* [W*B_inst,N] 1 = feasible                                   */
+  int64_t* first_node;      /* [W*B_inst] TSP                                              */
+  int64_t* current_node;    /* [W*B_inst]                                                  */
+  int64_t* step_i;          /* [W*B_inst] TSP                                              */
+  uint8_t* done;            /* [W*B_inst]                                                  */
+  const float* demand;      /* [B_inst,N-1] CVRP                                           */
+  float* used_capacity;     /* [W*B_inst] CVRP                                             */
+  const float* vehicle_capacity; /* [W*B_inst] CVRP (row b is read for every beam of instance b) */
+  uint8_t* visited;         /* [W*B_inst,N] CVRP                                           */
+  /* outputs, all [W*B_inst, out_stride] */
+  int32_t out_stride;
+  int32_t reserved0;
+  int64_t* actions;         /* aligned (backtracked) actions of the final beams, best first */
+  float* logps;             /* aligned log p(a_t)                                          */
+  int32_t* step_nodes;      /* per step, before alignment: node chosen by beam j           */
+  float* step_logps;        /* ... its log-prob under its parent                           */
+  int32_t* parents;         /* ... the beam of the previous column it extends              */
+  float* cum_logp;          /* ... its cumulative log-prob (the kept top-W values, descending in j) */
+  int32_t* steps_summary;   /* [2] or NULL (zero-initialised by the caller): [0] = max, [1] += T per instance */
+  int32_t* err;             /* sticky error bits                                           */
+} rl4co_am_decode_beam_args;
+
+int rl4co_am_decode_beam(const rl4co_am_decode_beam_args* args, void* stream);
+/* Largest beam_width rl4co_am_decode_beam serves for N nodes (the kernel's LDS budget, am_decode_beam.hip header); 0 if N
+ * itself is out of range. */
+int rl4co_am_decode_beam_max_width(int N);
 
 /* --------------------------------------------------------------------------
  * a11-a13  fused encoder + decoder-cache fold on the matrix cores (inference rollouts).

@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 15  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 16  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -31,6 +31,7 @@ EBIT_NOT_ALL_NODES = 512
 EBIT_DEPOT_MIDDLE = 1024
 EBIT_NO_PICKUP = 2048
 EBIT_TW_NEGATIVE, EBIT_TW_RETURN, EBIT_TW_DURATION, EBIT_TW_EMPTY, EBIT_TW_DEADLINE = 4096, 8192, 16384, 32768, 65536
+EBIT_BEAM_INFEASIBLE = 131072
 
 # Reference assertion messages (file:line in the reference checkout) per sticky bit.
 ERROR_MESSAGES = {
@@ -51,6 +52,7 @@ ERROR_MESSAGES = {
     EBIT_TW_DURATION: "Service durations must be non-negative.",  # cvrptw/env.py:158
     EBIT_TW_EMPTY: "there are unfeasible time windows",  # cvrptw/env.py:159-161
     EBIT_TW_DEADLINE: "vehicle cannot start service before deadline",  # cvrptw/env.py:176-179
+    EBIT_BEAM_INFEASIBLE: "infeasible action selected",  # utils/decoding.py:485 (beam search kept a -inf candidate)
 }
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -83,6 +85,24 @@ class AmDecodeArgs(C.Structure):
         ("mtsp_ctx", _vp), ("num_agents", _vp),
         ("ctx_dtype", _i32), ("reserved0", _i32), ("ctx_row_stride", _i64), ("ctx_batch_stride", _i64),
         ("top_k", _i32), ("top_p", _f32), ("kept_bits", _vp), ("kept_words", _i32), ("reserved1", _i32),
+    ]
+
+
+class AmDecodeBeamArgs(C.Structure):
+    """Mirror of ``struct rl4co_am_decode_beam_args`` (field order and types must match the header)."""
+
+    _fields_ = [
+        ("env", _i32), ("B_inst", _i32), ("N", _i32), ("beam_width", _i32),
+        ("max_steps", _i32), ("mask_inner", _i32), ("mask_logits", _i32), ("cache_dtype", _i32),
+        ("tanh_clipping", _f32), ("temperature", _f32),
+        ("glimpse_key", _vp), ("glimpse_val", _vp), ("logit_key", _vp),
+        ("kvl_row_stride", _i64), ("kvl_batch_stride", _i64),
+        ("ctx_first", _vp), ("ctx_cur", _vp), ("q_bias", _vp), ("q_step0", _vp), ("w_cap", _vp),
+        ("action_mask", _vp), ("first_node", _vp), ("current_node", _vp), ("step_i", _vp), ("done", _vp),
+        ("demand", _vp), ("used_capacity", _vp), ("vehicle_capacity", _vp), ("visited", _vp),
+        ("out_stride", _i32), ("reserved0", _i32),
+        ("actions", _vp), ("logps", _vp), ("step_nodes", _vp), ("step_logps", _vp), ("parents", _vp), ("cum_logp", _vp),
+        ("steps_summary", _vp), ("err", _vp),
     ]
 
 
@@ -182,6 +202,8 @@ SYMBOLS = {
     "rl4co_am_decode_lds_bytes": (C.c_int, [C.c_int, C.c_int]),
     "rl4co_am_decode_row_groups": (C.c_int, [C.POINTER(AmDecodeArgs)]),
     "rl4co_am_decode_variant": (C.c_int, [C.POINTER(AmDecodeArgs)]),
+    "rl4co_am_decode_beam": (C.c_int, [C.POINTER(AmDecodeBeamArgs), _vp]),
+    "rl4co_am_decode_beam_max_width": (C.c_int, [C.c_int]),
     "rl4co_select_start_nodes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "rl4co_augment_dihedral8_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_augment_symmetric_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp]),

@@ -37,6 +37,9 @@ class GraphedRollout:
         if name is not None and spec(name).state_reward:
             raise NotImplementedError(f"{name}: captured-graph rollouts are not served (the padding step of the finished rows "
                                       "follows the rollout's read-back)")
+        if decode_type == "beam_search":
+            raise NotImplementedError("beam search is not served inside captured graphs (its ragged horizon and best-beam "
+                                      "selection follow the rollout's read-back)")
         self.policy, self.env = policy, env
         self.decode_type = decode_type
         self.kw = dict(forward_kwargs)

@@ -407,6 +407,102 @@ def am_decode(
     _lib.check(st, "rl4co_am_decode")
 
 
+def beam_max_width(n: int) -> int:
+    """Largest ``beam_width`` the beam-search kernel serves for ``n`` nodes (its LDS budget; a host query)."""
+    return int(_lib.lib().rl4co_am_decode_beam_max_width(int(n)))
+
+
+def beam_served(sp: EnvSpec) -> bool:
+    """The environments rl4co_am_decode_beam accepts, by the ids its argument check admits."""
+    return sp.env_id in (_lib.ENV_TSP, _lib.ENV_CVRP)
+
+
+def am_decode_beam(
+    cache: FoldedCache,
+    state: dict,
+    beam_width: int,
+    max_steps: int,
+    *,
+    actions: Tensor,
+    logps: Tensor,
+    step_nodes: Tensor,
+    step_logps: Tensor,
+    parents: Tensor,
+    cum_logp: Tensor,
+    err: Tensor,
+    tanh_clipping: float = 10.0,
+    temperature: float = 1.0,
+    mask_inner: bool = True,
+    mask_logits: bool = True,
+    steps_summary: Tensor | None = None,
+) -> None:
+    """Beam search (utils/decoding.py:464-600) over ``beam_width`` beams per instance in one launch (rl4co_am_decode_beam).
+
+    ``state``: the environment's tensors (envspec.py) of the ``beam_width * B`` beam rows, beam-major, AFTER the imposed
+    start step; updated in place. Outputs are ``[beam_width * B, T]`` with ``T >= max_steps + 1``: column 0 is the start
+    node, the steps fill columns 1 .. ; ``actions`` / ``logps`` (int64 / fp32) are the aligned final beams, best first,
+    ``step_nodes`` / ``parents`` (int32), ``step_logps`` / ``cum_logp`` (fp32) the per-step selections before alignment."""
+    sp = spec(cache.env_name)
+    if not beam_served(sp):
+        raise NotImplementedError(f"beam search is not served for {sp.name} (tsp and cvrp are)")
+    if cache.unfold:
+        raise NotImplementedError("beam search needs the folded cache (fold=True)")
+    a = _lib.AmDecodeBeamArgs()
+    b, n = state["action_mask"].shape
+    w = int(beam_width)
+    assert w > 1, "beam width must be larger than 1"  # decoding.py:494
+    assert n == cache.num_nodes, (n, cache.num_nodes)
+    if b != w * cache.num_instances:
+        raise ValueError(f"{b} state rows for {w} beams over {cache.num_instances} instances")
+    if w > beam_max_width(n):
+        raise NotImplementedError(f"beam search with {w} beams over {n} nodes is beyond the kernel's limit of "
+                                  f"{beam_max_width(n)} beams at that size")
+    a.env, a.B_inst, a.N, a.beam_width, a.max_steps = sp.env_id, cache.num_instances, n, w, int(max_steps)
+    a.mask_inner, a.mask_logits = int(mask_inner), int(mask_logits)
+    a.tanh_clipping, a.temperature = float(tanh_clipping), float(temperature)
+    kvl = cache.kvl
+    if not kvl.is_cuda:
+        raise _lib.Rl4coLibraryError(f"cache.kvl lives on {kvl.device}; the rl4co_amd kernels only run on the MI355X (no CPU fallback)")
+    if not (kvl.dim() == 4 and kvl.stride(3) == 1):
+        raise ValueError("cache.kvl must be [3, B, N, 128] with unit stride along the channels")
+    a.cache_dtype = _lib.dtype_id(kvl.dtype)
+    a.glimpse_key, a.glimpse_val, a.logit_key = (cache.plane(i).data_ptr() for i in range(3))
+    a.kvl_row_stride, a.kvl_batch_stride = cache.row_stride, cache.batch_stride
+
+    def table(t: Tensor, name: str) -> Tensor:  # dense fp32 (a 16-bit table is widened: exact)
+        return _dev(t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous(), torch.float32, name)
+
+    keep = [table(cache.ctx_cur, "ctx_cur")]
+    a.ctx_cur = _ptr(keep[0])
+    a.q_bias = _ptr(None if cache.q_bias is None else _dev(cache.q_bias, torch.float32, "q_bias"))
+    if sp.ctx_first:
+        keep.append(table(cache.ctx_first, "ctx_first"))
+        a.ctx_first = _ptr(keep[-1])
+        a.q_step0 = _ptr(_dev(cache.q_step0, torch.float32, "q_step0"))
+    if sp.scalar is not None:
+        a.w_cap = _ptr(_dev(cache.w_cap, torch.float32, "w_cap"))
+    b_inst = bind_env_state(a, sp, state, b, n)
+    assert b_inst == cache.num_instances or not sp.keys("inst"), "instance data rows must match cache instances"
+    t_len = actions.shape[1]
+    if t_len < int(max_steps) + 1:
+        raise ValueError(f"outputs hold {t_len} columns, {int(max_steps)} steps need {int(max_steps) + 1}")
+    for name, t, dt in (("actions", actions, torch.int64), ("logps", logps, torch.float32), ("step_nodes", step_nodes, torch.int32),
+                        ("step_logps", step_logps, torch.float32), ("parents", parents, torch.int32), ("cum_logp", cum_logp, torch.float32)):
+        _dev(t, dt, name)
+        if tuple(t.shape) != (b, t_len):
+            raise ValueError(f"{name} must be [{b}, {t_len}], got {tuple(t.shape)}")
+        setattr(a, name, t.data_ptr())
+    a.out_stride = t_len
+    if steps_summary is not None:
+        _dev(steps_summary, torch.int32, "steps_summary")
+        if steps_summary.numel() < 2:
+            raise ValueError("steps_summary must hold 2 int32 words")
+    a.steps_summary = _ptr(steps_summary)
+    a.err = _ptr(_dev(err, torch.int32, "err"))
+    st = _lib.lib().rl4co_am_decode_beam(C.byref(a), _stream())
+    _lib.check(st, "rl4co_am_decode_beam")
+
+
 def decoding_filter(top_k, top_p, n: int) -> tuple[int, float]:
     """The top-k / top-p arguments of utils/decoding.py:109-188 as the kernel takes them: ``top_k <= 0`` is off and is
     clamped to ``n`` (k >= n removes nothing: 0); ``top_p <= 0`` or ``>= 1`` is off (0.0); ``top_p > 1`` raises the

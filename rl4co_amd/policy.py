@@ -383,9 +383,9 @@ def _cuda_tensors(objs):
 
 
 def _parse_decode_type(decode_type: str):
+    if decode_type == "beam_search":  # decoding.py:464-600: a strategy of its own (policy._forward_beam, am_decode_beam.hip)
+        return "beam_search", False
     if decode_type not in _KNOWN_DECODE_TYPES:
-        if decode_type == "beam_search":
-            raise NotImplementedError("beam_search is outside the accelerated hot path (SURVEY.md §2 row 2)")
         decode_type = "sampling"  # decoding.py:27-35 falls back to Sampling
     multistart = "multistart" in decode_type
     mode = "greedy" if "greedy" in decode_type else ("evaluate" if decode_type == "evaluate" else "sampling")
@@ -696,6 +696,12 @@ class AttentionModelPolicy(nn.Module):
                  return_hidden: bool = False, return_init_embeds: bool = False,
                  return_sum_log_likelihood: bool = True, actions: Tensor | None = None,
                  max_steps: int = 1_000_000, **decoding_kwargs) -> dict:
+        if actions is None and (decoding_kwargs.get("decode_type") or getattr(self, f"{phase}_decode_type")) == "beam_search":
+            decoding_kwargs.pop("decode_type", None)
+            if return_entropy or return_hidden or return_init_embeds:
+                raise NotImplementedError("beam search does not return entropy, hidden or init_embeds")
+            return self._forward_beam(td, env, calc_reward, return_actions, return_sum_log_likelihood, max_steps,
+                                      decoding_kwargs)
         grad_path = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         # fold=False (the reference's own association of the decoder, tsp / cvrp) also trains since r06: the rollout runs on the
         # unfolded decode kernel, the gradient comes from the dense torch re-evaluation of the same trajectories
@@ -863,6 +869,101 @@ class AttentionModelPolicy(nn.Module):
         if defer:
             return lambda: self._finish_rollout(r)
         return self._finish_rollout(r)
+
+    def _forward_beam(self, td: TensorDict, env, calc_reward: bool, return_actions: bool, return_sum_log_likelihood: bool,
+                      max_steps: int, kw: dict) -> dict:
+        """``decode_type="beam_search"`` (BeamSearch, utils/decoding.py:464-600): ``beam_width`` beams per instance from
+        ``env.select_start_nodes``, one launch of the beam kernel (csrc/am_decode_beam.hip), then the reward of all
+        ``beam_width * B`` aligned beams. ``select_best=True`` (the reference's default) returns per instance the beam of
+        largest reward, the lowest beam index on equal rewards; ``False`` all rows, beam-major. No gradient, in every phase."""
+        from . import _lib as _l
+
+        sp = spec(self.env_name)
+        if not K.beam_served(sp):
+            raise NotImplementedError(f"beam search (decode_type='beam_search') is not served for {sp.name}: the beam kernel "
+                                      "is built for tsp and cvrp")
+        if not self.fold:
+            raise NotImplementedError("beam search needs the folded cache: fold=False is not served")
+        if (kw.get("top_k") or 0) > 0 or (kw.get("top_p") or 0.0) > 0:
+            raise NotImplementedError("top-k / top-p filtering is not served together with beam search")
+        if kw.get("_defer_finish"):
+            raise NotImplementedError("beam search is not served inside captured graphs (GraphedRollout)")
+        if not td["action_mask"].is_cuda:
+            raise NotImplementedError("beam search runs inside the MI355X decode kernels only")
+        beam_width, select_best = kw.pop("beam_width", None), bool(kw.pop("select_best", True))
+        temperature = kw.pop("temperature", self.temperature)
+        tanh_clipping = kw.pop("tanh_clipping", self.tanh_clipping)
+        mask_logits = kw.pop("mask_logits", self.mask_logits)
+        start_fn = kw.pop("select_start_nodes_fn", None)
+        for k in ("top_k", "top_p", "_defer_finish"):  # (checked above: off)
+            kw.pop(k, None)
+        if kw:  # num_starts, multisample, store_all_logp, seed, ...: arguments of the other strategies
+            raise NotImplementedError(f"beam search does not take {sorted(kw)}")
+        if isinstance(env, str) or env is None:
+            env = get_env(self.env_name if env is None else env)
+        device = td["action_mask"].device
+        b_inst, n = td["action_mask"].shape[0], td["action_mask"].shape[-1]
+        width = int(env.get_num_starts(td) if beam_width is None else beam_width)
+        assert width > 1, "beam width must be larger than 1"  # decoding.py:494
+        limit = K.beam_max_width(n)
+        if width > limit:
+            raise NotImplementedError(f"beam search with beam_width={width} over {n} nodes is beyond the beam kernel's "
+                                      f"limit of {limit} beams at that size")
+        with torch.no_grad():
+            cache_dtype = self._plane_dtype(False)
+            cache, hidden, _ = self._encode_for_rollout(td, False, cache_dtype, False, False)
+            if cache is None:
+                regime = self._encoder_regime()
+                cache = self.decoder.precompute_cache(hidden.detach(), cache_dtype,
+                                                      torch.bfloat16 if (regime == torch.bfloat16 and cache_dtype != torch.float16)
+                                                      else torch.float32, fold=True)
+            state = self._initial_state(td, width)
+            tmax = min(self._max_horizon(self.env_name, n), max(int(max_steps), 2))
+            status = torch.zeros(4, dtype=torch.int32, device=device)
+            err = status[:1]
+            # pre_decoder_hook (decoding.py:491-516): the imposed start node of every beam, log-prob 0
+            if start_fn is not None:
+                first = start_fn(td, env, width).to(device=device, dtype=torch.int64).contiguous()
+            else:
+                first = env.select_start_nodes(td, num_starts=width)
+            self._env_step_state(state, first, err)
+            rows = width * b_inst
+            out_actions = torch.zeros((rows, tmax), dtype=torch.int64, device=device)
+            logps = torch.zeros((rows, tmax), dtype=torch.float32, device=device)
+            raw = {k: torch.zeros((rows, tmax), dtype=dt, device=device)
+                   for k, dt in (("step_nodes", torch.int32), ("step_logps", torch.float32), ("parents", torch.int32),
+                                 ("cum_logp", torch.float32))}
+            K.am_decode_beam(cache, state, width, tmax - 1, actions=out_actions, logps=logps, err=err,
+                             tanh_clipping=tanh_clipping, temperature=temperature, mask_inner=self.decoder.mask_inner,
+                             mask_logits=mask_logits, steps_summary=status[2:4], **raw)
+            native_env = isinstance(env, RL4COEnvBase)
+            checked = bool(native_env and calc_reward and env.check_solution)
+            if checked:
+                env.check_solution_validity(td, out_actions, err=err)
+            self.last_beam_steps = raw  # (tests: the per-step selections before alignment, [beam_width * B, T] each)
+            err_bits, _, steps, _ = status.tolist()  # the rollout's one read-back
+            _l.raise_for_error_bits(int(err_bits))
+            t_used = 1 + int(steps)
+            out_actions, logps = out_actions[:, :t_used].contiguous(), logps[:, :t_used]
+            td_out = self._final_td(td, state, width)
+            td_out.set("action", out_actions[:, -1])
+            reward = None
+            if calc_reward or select_best:
+                reward = env.get_reward(td_out, out_actions, check_solution=False if checked else None)
+            if select_best:  # _select_best_beam (decoding.py:559-565); equal rewards: the lowest beam index
+                per = reward.view(width, b_inst)
+                beams = torch.arange(width, device=device).view(width, 1).expand(width, b_inst)
+                best = torch.where(per == per.max(dim=0).values, beams, width).min(dim=0).values
+                keep = best * b_inst + torch.arange(b_inst, device=device)
+                out_actions, logps, reward = out_actions[keep], logps[keep], reward[keep]
+                td_out = td_out[keep] if hasattr(td_out, "__getitem__") else td_out
+            if calc_reward:
+                td_out.set("reward", reward)
+            outdict = {"reward": reward if calc_reward else td_out.get("reward", None),
+                       "log_likelihood": logps.sum(1) if return_sum_log_likelihood else logps}
+            if return_actions:
+                outdict["actions"] = out_actions
+            return outdict
 
     def _finish_rollout(self, r) -> dict:
         """Step 4 of ``_forward``: the rollout's ONE host read-back (status words), the reference's assertions, the
