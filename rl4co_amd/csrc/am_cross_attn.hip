@@ -46,11 +46,6 @@ __device__ inline bf16x4 lds_tr(const elem_t* p) {
   return __builtin_bit_cast(bf16x4, v);
 }
 __device__ inline bf16x4 to_e4(const f32x4& v) { return rl4co_e16::cvt4(v[0], v[1], v[2], v[3]); }
-__device__ inline void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 __device__ inline float rg_sum(float v) { return rl4co::bfly_sum<16, 64>(v); }
 
 // ---- forward: one workgroup = (trajectory, block of kQT * 16 steps); wave h owns head h -----------------------------------
@@ -281,7 +276,7 @@ __global__ void __launch_bounds__(kBwdThreads, 3) cross_bwd_kernel(const rl4co_c
     *reinterpret_cast<bf16x4*>(qd + tl * kQD + 4 * g) = dof;
     *reinterpret_cast<bf16x4*>(qd + tl * kQD + 16 + 4 * g) = qf;
     if (g == 0) ld[tl] = make_float2(L, dsum);
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     const float4 s01 = *reinterpret_cast<const float4*>(ld + 4 * g), s23 = *reinterpret_cast<const float4*>(ld + 4 * g + 2);
     const float Lr[4] = {s01.x, s01.z, s23.x, s23.z};
     const f32x4 negD = {s01.y, s01.w, s23.y, s23.w};
@@ -325,13 +320,13 @@ __global__ void __launch_bounds__(kBwdThreads, 3) cross_bwd_kernel(const rl4co_c
         *reinterpret_cast<bf16x4*>(dsb + (16 * (j0 + j) + tl) * kSS + 4 * g) = dsf[j];
       }
     }
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     f32x4 dq = zero4();
 #pragma clang loop unroll(full)
     for (int jt = 0; jt < NT; ++jt)
       dq = mfma16(lds_tr(kv + 16 * jt * kKH + 16 * w + tro), lds_tr(dsb + 16 * jt * kSS + tro_s), dq);
     if (tv) *reinterpret_cast<f32x4*>(a.dq_partial + (((int64_t)kc * a.B + traj) * T + t) * kD + 16 * h + 4 * g) = dq;
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
   }
   __syncthreads();
   elem_t* os = reinterpret_cast<elem_t*>(smem);

@@ -81,63 +81,14 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "decode_wave.h"
 #include "rl4co_math.h"
 #include "topkp.h"
 
 namespace {
 
-constexpr int kD = RL4CO_EMBED_DIM;
-constexpr int kH = RL4CO_NUM_HEADS;
-constexpr int kDH = kD / kH;
-constexpr int kUnroll = 4;  // wave-wide 1 KiB loads kept in flight per pass
 constexpr int kLdsWaves = 4;    // four-wave kernels (LDS / WIDE, below): waves per trajectory
 constexpr int kLdsGroups = 16;  // ... and their row groups
-constexpr float kNegInf = -__builtin_huge_valf();
-constexpr float kSqrtD = 11.3137084989847604f;  // fl32(sqrt(128)), attention.py:293
-
-struct CacheF32 {
-  using elem = float;
-  using raw = float4;
-  static constexpr int EPL = 4;
-  __device__ static inline raw zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-  __device__ static inline raw ld(const elem* p) { return *reinterpret_cast<const float4*>(p); }
-  __device__ static inline void cvt(const raw& t, float (&v)[4]) {
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-};
-
-struct CacheBF16 {
-  using elem = uint16_t;
-  using raw = uint4;
-  static constexpr int EPL = 8;
-  __device__ static inline raw zero() { return make_uint4(0u, 0u, 0u, 0u); }
-  __device__ static inline raw ld(const elem* p) { return *reinterpret_cast<const uint4*>(p); }
-  __device__ static inline void cvt(const raw& t, float (&v)[8]) {
-    v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
-    v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
-    v[4] = __uint_as_float(t.z << 16); v[5] = __uint_as_float(t.z & 0xffff0000u);
-    v[6] = __uint_as_float(t.w << 16); v[7] = __uint_as_float(t.w & 0xffff0000u);
-  }
-};
-
-// IEEE half planes (torch.float16: the reference's default "16-mixed" precision, utils/trainer.py:57): same 16-byte
-// lanes as bf16, converted with v_cvt_f32_f16 — exact, like the bf16 shift
-struct CacheF16 {
-  using elem = uint16_t;
-  using raw = uint4;
-  static constexpr int EPL = 8;
-  typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-  __device__ static inline raw zero() { return make_uint4(0u, 0u, 0u, 0u); }
-  __device__ static inline raw ld(const elem* p) { return *reinterpret_cast<const uint4*>(p); }
-  __device__ static inline void cvt(const raw& t, float (&v)[8]) {
-    const half2_t a = __builtin_bit_cast(half2_t, t.x), b = __builtin_bit_cast(half2_t, t.y);
-    const half2_t c = __builtin_bit_cast(half2_t, t.z), d = __builtin_bit_cast(half2_t, t.w);
-    v[0] = (float)a[0]; v[1] = (float)a[1]; v[2] = (float)b[0]; v[3] = (float)b[1];
-    v[4] = (float)c[0]; v[5] = (float)c[1]; v[6] = (float)d[0]; v[7] = (float)d[1];
-  }
-};
-
-__host__ __device__ inline int lds_pad(int N) { return (N + 63) & ~63; }
 
 // The folded context tables of one instance, EPL dims from e0 on, as fp32: dense fp32 [N,128] rows (the default), or — r06,
 // ctx_dtype — rows in the planes' 16-bit element type with the caller's strides (e.g. column blocks of the one 16-bit
@@ -179,42 +130,6 @@ __device__ inline int trajectory_of_block(int b, int B, int B_inst) {
   if (S == 1 || (B_inst & 7) != 0) return b;
   const int xcd = b & 7, k = b >> 3;
   return (k % S) * B_inst + (k / S) * 8 + xcd;
-}
-
-// LDS ordering inside ONE wave (cross-lane hand-off through LDS, no other wave involved)
-__device__ inline void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-struct TrajState {
-  int cur, first;
-  long long step_i;
-  float used;
-  float time;  // CVRPTW: current time
-  bool done;
-  uint32_t errbits;
-  float ent_acc;
-};
-
-// One wave: compact the nodes this step has to read (ascending) into fl[0..F).
-__device__ inline int build_list(const rl4co_am_decode_args& a, const uint8_t* mk, uint16_t* fl, int N, int lane) {
-  int F = 0;
-  if (a.mask_inner && a.mask_logits) {
-    for (int j0 = 0; j0 < N; j0 += 64) {
-      const int j = j0 + lane;
-      const bool f = j < N && mk[j] != 0;
-      const unsigned long long bal = __ballot(f);
-      if (f) fl[F + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)j;
-      F += __popcll(bal);
-    }
-  } else {
-    for (int j = lane; j < N; j += 64) fl[j] = (uint16_t)j;
-    F = N;
-  }
-  wave_lds_sync();
-  return F;
 }
 
 template <int ENV>
@@ -290,7 +205,7 @@ __device__ inline int finalize_and_step(const rl4co_am_decode_args& a, TrajState
   }
   rl4co::bfly_argmax(best, bc);
   if (a.entropy) st.ent_acc = st.ent_acc - rl4co::bfly_sum<1, 64>(ent);
-  wave_lds_sync();
+  rl4co::lds_barrier_wave();
   return commit_and_step<ENV>(a, st, lg, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur, bc, dd);
 }
 
@@ -325,7 +240,7 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
     a.actions[(int64_t)r * a.out_stride + tcol] = bi;
     a.logps[(int64_t)r * a.out_stride + tcol] = logp;
   }
-  wave_lds_sync();
+  rl4co::lds_barrier_wave();
 
   // ---- environment transition -------------------------------------------------------
   if constexpr (ENV == RL4CO_ENV_MTSP) {  // (discarded in every other instantiation: their code is what it was)
@@ -336,7 +251,7 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
     const float bx = oplocs[2 * bi], by = oplocs[2 * bi + 1];
     const bool depot_open = (bi != 0) && (st.step_i < nag - 1);  // mtsp/env.py:86-88 (agent_idx before the step)
     if (lane == 0) mk[bi] = 0;
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     bool left = false;
     for (int j = lane; j < N; j += 64) left |= (j >= 1) && mk[j] != 0;
     st.done = !__any(left);                                      // mtsp/env.py:91
@@ -359,7 +274,7 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
     st.cur = bi;
     if (lane == 0) mk[bi] = 0;
     st.step_i += 1;
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     bool any_left = false;
     for (int j = lane; j < N; j += 64) any_left |= mk[j] != 0;
     st.done = !__any(any_left);  // tsp/env.py:71
@@ -372,7 +287,7 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
     }
     st.step_i += 1;
     st.cur = bi;
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     bool left = false;
     for (int j = lane; j < N; j += 64) {
       const uint8_t v = vis[j];
@@ -386,9 +301,9 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
     const float delivered = fminf(da, cap - st.used);
     st.used = (st.used + delivered) * (bi != 0 ? 1.0f : 0.0f);
     st.cur = bi;
-    wave_lds_sync();  // every lane has read dd[bi]
+    rl4co::lds_barrier_wave();  // every lane has read dd[bi]
     if (lane == 0) dd[bi] = da - delivered;
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     bool any_feasible = false, any_left = false;
     for (int j = lane; j < N; j += 64) {
       const float dj = dd[j];
@@ -410,7 +325,7 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
     st.done = (bi == 0) && (st.step_i > 0);
     st.step_i += 1;
     st.cur = bi;
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     const bool depot_visited = vis[0] != 0;
     bool unvisited = false;
     for (int j = lane; j < N; j += 64) {
@@ -434,7 +349,7 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
     st.done = (bi == 0) && (st.step_i > 0);
     st.step_i += 1;
     st.cur = bi;
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     const bool depot_visited = vis[0] != 0;
     for (int j = lane; j < N; j += 64) {
       const float dx = oplocs[2 * j] - bx, dy = oplocs[2 * j + 1] - by;
@@ -453,7 +368,7 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
     st.used = (st.used + dem[di]) * (bi != 0 ? 1.0f : 0.0f);         // cvrp/env.py:76
     st.cur = bi;
     if (lane == 0) vis[bi] = 1;
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     const float thr = cap + 1e-5f;  // cvrp/env.py:128
     bool any_feasible = false, all_visited = true;
     for (int j = lane; j < N; j += 64) {
@@ -468,7 +383,7 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
     st.done = __all(all_visited);  // cvrp/env.py:83
     if (lane == 0) mk[0] = ((st.cur == 0) && any_feasible) ? 0 : 1;  // cvrp/env.py:134-135
     if (ENV == RL4CO_ENV_CVRPTW) {  // cvrptw/env.py:91-95: only nodes whose window is still open on arrival
-      wave_lds_sync();
+      rl4co::lds_barrier_wave();
       const float bx = oplocs[2 * bi], by = oplocs[2 * bi + 1];
       for (int j = lane; j < N; j += 64) {
         const float dx = oplocs[2 * j] - bx, dy = oplocs[2 * j + 1] - by;
@@ -476,7 +391,7 @@ __device__ inline int commit_and_step(const rl4co_am_decode_args& a, TrajState& 
       }
     }
   }
-  wave_lds_sync();
+  rl4co::lds_barrier_wave();
   return bi;
 }
 
@@ -593,7 +508,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   const float* dem = kCvrpLike                  ? a.demand + (int64_t)cb * (N - 1)
                      : (ENV == RL4CO_ENV_PCTSP) ? a.demand + (int64_t)cb * N
                                                 : nullptr;
-  wave_lds_sync();
+  rl4co::lds_barrier_wave();
 
   // ---- row cache: the S highest-index candidates, all pending --------------------------------
   const bool list_all = !(a.mask_inner && a.mask_logits);
@@ -603,7 +518,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   const bool caching = kRowCache && S > 0;
   if (caching) {
     for (int j = lane; j < Np; j += 64) rslot[j] = (uint8_t)kRowCacheNone;
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     int k = 0;
     for (int j0 = N - 1; j0 >= 0 && k < S; j0 -= 64) {  // lane l takes node j0 - l: descending in lane order
       const int j = j0 - lane;
@@ -616,7 +531,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
       }
       k += __popcll(bal);
     }
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
   }
   auto lds_row = [&](int j, int plane) -> const elem* { return rc + (rslot[j] * 3 + plane) * kD + e0; };
   auto fill_row = [&](int j, int plane, const raw_t& v) {  // a pending (or already filled) slot gets its row
@@ -673,11 +588,11 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
           if (li == 0) cv[kD] = cap - st.used;
         }
       }
-      wave_lds_sync();
+      rl4co::lds_barrier_wave();
       gemv_t<EPL>(q, a.w_ctx_t, cv, a.ctx_width, e0);
 #pragma unroll
       for (int e = 0; e < EPL; ++e) q[e] = q[e] + qb[e];
-      wave_lds_sync();  // cv is overwritten by this step's scores
+      rl4co::lds_barrier_wave();  // cv is overwritten by this step's scores
     } else if constexpr (kMtsp) {  // context.py:246-280, folded: ctx_cur[cur] + sum_k f_k g_k
       const float f0 = (float)(nag - st.step_i);
       const float ddx = oplocs[2 * st.cur] - oplocs[0], ddy = oplocs[2 * st.cur + 1] - oplocs[1];
@@ -763,14 +678,14 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
     }
     m = rl4co::bfly_max<LPR, 64>(m);
     if (rg == 0 && (li % LPH) == 0) mh[hd] = m;
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     // softmax numerators once per (list entry, head) — lane-strided over the F*8 scores, so
     // each exp is evaluated exactly once (index % 8 = head is fixed per lane: 64 % 8 == 0)
     {
       const float mm = mh[lane & (kH - 1)];
       for (int idx = lane; idx < F * kH; idx += 64) sc[idx] = rl4co_expf(sc[idx] - mm);
     }
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
 
     // ---- pass 2: softmax-weighted value sum ------------------------------------------------
     float lacc[NG], pdacc[NG];
@@ -830,12 +745,12 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
       for (int e = 0; e < EPL; ++e) o[e] = tree([&](int g) { return oacc[g][e]; }) * l;
     }
     if constexpr (UNFOLD) {  // glimpse = project_out(heads) (attention.py:287), heads broadcast through LDS
-      wave_lds_sync();       // every lane is done with the softmax numerators in sc
+      rl4co::lds_barrier_wave();       // every lane is done with the softmax numerators in sc
       if (rg == 0) {
 #pragma unroll
         for (int e = 0; e < EPL; ++e) sc[e0 + e] = o[e];
       }
-      wave_lds_sync();
+      rl4co::lds_barrier_wave();
       gemv_t<EPL>(o, a.w_out_t, sc, kD, e0);
     }
 
@@ -880,7 +795,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
         if (s != kRowCacheNone) rpend[s] = 0;
       }
     }
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
 
     const int bi = finalize_and_step<ENV, FILT>(a, st, lg, sc, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur, dd);
     if (caching && rslot[bi] != kRowCacheNone && !candidate(bi)) {
@@ -891,7 +806,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
         if (candidate(j) && rslot[j] == kRowCacheNone) nxt = j;
       nxt = rl4co::bfly_i_max(nxt);
       const int s = rslot[bi];
-      wave_lds_sync();
+      rl4co::lds_barrier_wave();
       if (lane == 0) {
         rslot[bi] = (uint8_t)kRowCacheNone;
         if (nxt >= 0) {
@@ -899,7 +814,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
           rpend[s] = 1;
         }
       }
-      wave_lds_sync();
+      rl4co::lds_barrier_wave();
     }
   }
   if (!single && !st.done && t >= a.max_steps) st.errbits |= RL4CO_EBIT_MAX_STEPS;
@@ -1044,7 +959,7 @@ __device__ inline int wide_scores(const rl4co_am_decode_args& a, TrajState& st, 
     }
     rl4co::bfly_argmax(best, bc);
     if (a.entropy) st.ent_acc = st.ent_acc - rl4co::bfly_sum<1, 64>(ent);
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
   }
   return bc;
 }
@@ -1273,7 +1188,7 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
         }
       }
     }
-    wave_lds_sync();  // the numerators are consumed by this same wave only
+    rl4co::lds_barrier_wave();  // the numerators are consumed by this same wave only
 
     // ---- pass 2: softmax weights and weighted values ---------------------------------------------
     float l = 0.0f, pd = 0.0f;

@@ -3,8 +3,11 @@
 // One workgroup of four waves per INSTANCE carries all W beams of that instance through the whole rollout: per step the
 // masked log-prob row of every beam, the top-W selection over the W * N (parent, node) candidates, the re-parenting of
 // the beam states and the environment transition; after the last step the parent chain is walked back and the aligned
-// actions / log-probs are written. An entry point of its own (rl4co_am_decode_beam): no variant id, no code shared
-// with the launches of am_decode.hip, TSP and CVRP.
+// actions / log-probs are written. An entry point of its own (rl4co_am_decode_beam): no variant id, TSP and CVRP.
+// Shared with am_decode.hip through decode_wave.h: the plane element types (CacheF32 / CacheBF16 / CacheF16), the layout
+// constants, the 64-padding and the feasible-list compaction (build_list); the wave barrier is common.h's. The query, the
+// three passes, the clip / log-softmax and the two transitions are this file's own text of the STREAM kernel's order:
+// an edit to either text must be made in both (tests/test_gpu_beam.py::test_logps_equal_stream_evaluate).
 //
 // Work split
 //   A  log-probs   wave w takes beams w, w + 4, ...: one beam at a time with exactly the one-wave arithmetic of the
@@ -55,74 +58,21 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "decode_wave.h"
 #include "rl4co_math.h"
 
 namespace {
 
-constexpr int kD = RL4CO_EMBED_DIM;
-constexpr int kH = RL4CO_NUM_HEADS;
-constexpr int kDH = kD / kH;
-constexpr int kUnroll = 4;     // wave-wide 1 KiB loads kept in flight per pass (the STREAM kernel's)
 constexpr int kWaves = 4;
 constexpr int kThreads = 64 * kWaves;
 constexpr int kCandPerThread = 64;
 constexpr int kCuLds = 160 * 1024;
 constexpr int kStaticLds = 256;  // static LDS of every instantiation beside the dynamic bytes (checked at launch)
-constexpr float kNegInf = -__builtin_huge_valf();
-constexpr float kSqrtD = 11.3137084989847604f;  // fl32(sqrt(128)), attention.py:293
-
-struct CacheF32 {
-  using elem = float;
-  using raw = float4;
-  static constexpr int EPL = 4;
-  __device__ static inline raw zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-  __device__ static inline raw ld(const elem* p) { return *reinterpret_cast<const float4*>(p); }
-  __device__ static inline void cvt(const raw& t, float (&v)[4]) {
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-};
-
-struct CacheBF16 {
-  using elem = uint16_t;
-  using raw = uint4;
-  static constexpr int EPL = 8;
-  __device__ static inline raw zero() { return make_uint4(0u, 0u, 0u, 0u); }
-  __device__ static inline raw ld(const elem* p) { return *reinterpret_cast<const uint4*>(p); }
-  __device__ static inline void cvt(const raw& t, float (&v)[8]) {
-    v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
-    v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
-    v[4] = __uint_as_float(t.z << 16); v[5] = __uint_as_float(t.z & 0xffff0000u);
-    v[6] = __uint_as_float(t.w << 16); v[7] = __uint_as_float(t.w & 0xffff0000u);
-  }
-};
-
-struct CacheF16 {
-  using elem = uint16_t;
-  using raw = uint4;
-  static constexpr int EPL = 8;
-  typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-  __device__ static inline raw zero() { return make_uint4(0u, 0u, 0u, 0u); }
-  __device__ static inline raw ld(const elem* p) { return *reinterpret_cast<const uint4*>(p); }
-  __device__ static inline void cvt(const raw& t, float (&v)[8]) {
-    const half2_t a = __builtin_bit_cast(half2_t, t.x), b = __builtin_bit_cast(half2_t, t.y);
-    const half2_t c = __builtin_bit_cast(half2_t, t.z), d = __builtin_bit_cast(half2_t, t.w);
-    v[0] = (float)a[0]; v[1] = (float)a[1]; v[2] = (float)b[0]; v[3] = (float)b[1];
-    v[4] = (float)c[0]; v[5] = (float)c[1]; v[6] = (float)d[0]; v[7] = (float)d[1];
-  }
-};
 
 __host__ __device__ inline int pad4(int N) { return (N + 3) & ~3; }
-__host__ __device__ inline int pad64(int N) { return (N + 63) & ~63; }
-__host__ __device__ inline int wave_scratch_bytes(int N) { return 38 * pad64(N) + 32; }
+__host__ __device__ inline int wave_scratch_bytes(int N) { return 38 * lds_pad(N) + 32; }
 __host__ __device__ inline int64_t beam_lds_bytes(int64_t W, int N) {
   return 8 * W * pad4(N) + 56 * W + kWaves * wave_scratch_bytes(N) + 80;
-}
-
-// LDS ordering inside ONE wave (cross-lane hand-off through LDS, no other wave involved)
-__device__ inline void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 // order-preserving image of a float (NaN below everything)
@@ -158,7 +108,7 @@ __global__ void __launch_bounds__(kThreads) am_decode_beam_kernel(const rl4co_am
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x, B = a.B_inst, W = a.beam_width, N = a.N;
-  const int nw = pad4(N), Np = pad64(N);
+  const int nw = pad4(N), Np = lds_pad(N);
   const int64_t os = a.out_stride;
 
   float* lp = reinterpret_cast<float*>(smem);        // [W][nw] log-prob rows by node
@@ -241,27 +191,13 @@ __global__ void __launch_bounds__(kThreads) am_decode_beam_kernel(const rl4co_am
       float* row = lp + j * nw;
       for (int n = lane; n < nw; n += 64) row[n] = kNegInf;
       if (idone(p)[j] != 0) {  // finished (CVRP): the padding step offers the depot alone, log-prob 0
-        wave_lds_sync();
+        rl4co::lds_barrier_wave();
         if (lane == 0) row[0] = 0.0f;
         continue;
       }
       const int cur = icur(p)[j], first = ifirst(p)[j], step_i = istep(p)[j];
       const float used = usedb[p * W + j];
-      // feasible nodes, ascending (or all nodes when either mask flag is off)
-      int F = 0;
-      if (a.mask_inner && a.mask_logits) {
-        for (int j0 = 0; j0 < N; j0 += 64) {
-          const int n = j0 + lane;
-          const bool f = n < N && mk[n] != 0;
-          const unsigned long long bal = __ballot(f);
-          if (f) fl[F + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)n;
-          F += __popcll(bal);
-        }
-      } else {
-        for (int n = lane; n < N; n += 64) fl[n] = (uint16_t)n;
-        F = N;
-      }
-      wave_lds_sync();
+      const int F = build_list(a, mk, fl, N, lane);  // feasible nodes, ascending (or all nodes when either mask flag is off)
 
       // ---- query: folded context row(s) + scalar + graph context, * 1/sqrt(16) ------------------------------------
       float q[EPL];
@@ -310,12 +246,12 @@ __global__ void __launch_bounds__(kThreads) am_decode_beam_kernel(const rl4co_am
       }
       m = rl4co::bfly_max<LPR, 64>(m);
       if (rg == 0 && (li % LPH) == 0) mh[hd] = m;
-      wave_lds_sync();
+      rl4co::lds_barrier_wave();
       {
         const float mm = mh[lane & (kH - 1)];
         for (int idx = lane; idx < F * kH; idx += 64) sc[idx] = rl4co_expf(sc[idx] - mm);
       }
-      wave_lds_sync();
+      rl4co::lds_barrier_wave();
 
       // ---- pass 2: softmax-weighted value sum -----------------------------------------------------------------
       float lacc = 0.0f;
@@ -367,7 +303,7 @@ __global__ void __launch_bounds__(kThreads) am_decode_beam_kernel(const rl4co_am
           if (c < F && li == 0) lg[c] = acc;
         }
       }
-      wave_lds_sync();
+      rl4co::lds_barrier_wave();
 
       // ---- clip, mask, log-softmax (finalize_and_step's order) ------------------------------------------------------
       bool nan_seen = false;
@@ -388,7 +324,7 @@ __global__ void __launch_bounds__(kThreads) am_decode_beam_kernel(const rl4co_am
       zsum = rl4co::bfly_sum<1, 64>(zsum);
       const float lse = rl4co_logf(zsum);
       for (int c = lane; c < F; c += 64) row[fl[c]] = (lg[c] - zmax) - lse;
-      wave_lds_sync();
+      rl4co::lds_barrier_wave();
     }
     __syncthreads();
 
@@ -496,7 +432,7 @@ __global__ void __launch_bounds__(kThreads) am_decode_beam_kernel(const rl4co_am
           istep(q_)[i] = min(istep(q_)[i] + 1, 0x3fffffff);
           mk[bi] = 0;
         }
-        wave_lds_sync();
+        rl4co::lds_barrier_wave();
         bool any_left = false;
         for (int n = lane; n < N; n += 64) any_left |= mk[n] != 0;
         const bool dn = !__any(any_left);  // tsp/env.py:71
@@ -504,13 +440,13 @@ __global__ void __launch_bounds__(kThreads) am_decode_beam_kernel(const rl4co_am
       } else {
         const int di = min(max(bi - 1, 0), N - 2);                                      // cvrp/env.py:71-73
         const float used = (usedb[q_ * W + i] + dem[di]) * (bi != 0 ? 1.0f : 0.0f);     // cvrp/env.py:76
-        wave_lds_sync();  // every lane has read the beam's used capacity
+        rl4co::lds_barrier_wave();  // every lane has read the beam's used capacity
         if (lane == 0) {
           usedb[q_ * W + i] = used;
           icur(q_)[i] = bi;
           vis[bi] = 1;
         }
-        wave_lds_sync();
+        rl4co::lds_barrier_wave();
         const float thr = cap + 1e-5f;  // cvrp/env.py:128
         bool any_feasible = false, all_visited = true;
         for (int n = lane; n < N; n += 64) {

@@ -70,12 +70,6 @@ __device__ inline bf16x4 pack4(const f32x2& a, const f32x2& b) {  // two v_cvt_p
   return __builtin_bit_cast(bf16x4, u32x2{rl4co_e16::pack(a[0], a[1]), rl4co_e16::pack(b[0], b[1])});
 }
 __device__ inline bf16x4 to_bf16(const f32x4& v) { return rl4co_e16::cvt4(v[0], v[1], v[2], v[3]); }  // two pair conversions (elem16.h)
-// LDS hand-off inside ONE wave
-__device__ inline void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 // across the four row groups of a wave (lanes differing in bits 4, 5)
 __device__ inline float rg_sum(float v) { return rl4co::bfly_sum<16, 64>(v); }
 __device__ inline float rg_max(float v) { return rl4co::bfly_max<16, 64>(v); }
@@ -909,14 +903,14 @@ __global__ void __launch_bounds__(kThreads, 2) am_teacher_mma_kernel(const rl4co
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) ada = fmaf(o[rr], (float)dof[rr], ada);
         ada = rg_sum(ada);
-        wave_lds_sync();  // this wave's P block, dO and Q columns are in LDS
+        rl4co::lds_barrier_wave();  // this wave's P block, dO and Q columns are in LDS
         {
           const bf16x4 dt = lds_tr(dob + 16 * h + tro);  // (dO_h / l)^T[d][steps]
 #pragma unroll
           for (int jt = 0; jt < NT; ++jt)
             dvg[jt] = mfma16(dt, lds_tr(pbw + 16 * jt + tro), dvg[jt]);
         }
-        wave_lds_sync();  // the transpose reads of P are done: the block is reused for dS
+        rl4co::lds_barrier_wave();  // the transpose reads of P are done: the block is reused for dS
         const f32x2 il2 = {inv_l, inv_l}, nada2 = {-ada * inv_l, -ada * inv_l};
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt) {
@@ -931,7 +925,7 @@ __global__ void __launch_bounds__(kThreads, 2) am_teacher_mma_kernel(const rl4co
             dq = mfma16(lds_tr(kgs + 16 * jt * kRS + 16 * h + tro), dsf, dq);
           }
         }
-        wave_lds_sync();
+        rl4co::lds_barrier_wave();
         {
           const bf16x4 qt = lds_tr(qb + 16 * h + tro);  // Q_h^T[d][steps]
 #pragma unroll

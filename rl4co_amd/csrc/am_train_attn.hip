@@ -47,11 +47,6 @@ __device__ inline bf16x4 lds_tr(const elem_t* p) {
   return __builtin_bit_cast(bf16x4, v);
 }
 __device__ inline bf16x4 to_bf16(const f32x4& v) { return rl4co_e16::cvt4(v[0], v[1], v[2], v[3]); }  // two pair conversions (elem16.h)
-__device__ inline void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 __device__ inline float rg_sum(float v) { return rl4co::bfly_sum<16, 64>(v); }
 __device__ inline float rg_max(float v) { return rl4co::bfly_max<16, 64>(v); }
 
@@ -299,7 +294,7 @@ __global__ void __launch_bounds__(kBwdThreads, 3) attn_bwd_kernel(const uint16_t
     *reinterpret_cast<bf16x4*>(qd + tl * kQD + 4 * g) = dof;
     *reinterpret_cast<bf16x4*>(qd + tl * kQD + 16 + 4 * g) = qf;
     if (g == 0) ld[tl] = make_float2(L, dsum);
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     // this lane's accumulator rows are queries 4 g .. 4 g + 3 of the block: their (L, -D)
     const float4 s01 = *reinterpret_cast<const float4*>(ld + 4 * g), s23 = *reinterpret_cast<const float4*>(ld + 4 * g + 2);
     const float Lr[4] = {s01.x, s01.z, s23.x, s23.z};
@@ -358,7 +353,7 @@ __global__ void __launch_bounds__(kBwdThreads, 3) attn_bwd_kernel(const uint16_t
           *reinterpret_cast<bf16x4*>(dsb + (16 * (j0 + j) + tl) * kSS + 4 * g) = dsf[j];  // [key][queries 4 g ..]
         }
     }
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     f32x4 dq = zero4();
 #pragma clang loop unroll(full)
     for (int jt = 0; jt < NT; ++jt)
@@ -366,7 +361,7 @@ __global__ void __launch_bounds__(kBwdThreads, 3) attn_bwd_kernel(const uint16_t
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) dq[rr] *= 0.25f;
     dqv[tb] = to_bf16(dq);
-    wave_lds_sync();  // the next query block rewrites this wave's staging block
+    rl4co::lds_barrier_wave();  // the next query block rewrites this wave's staging block
   }
   RL4CO_ABP_MARK(1)
   __syncthreads();  // every wave is done with k | v: the whole LDS becomes [16 NT][d q | d k | d v] of the four heads
@@ -484,7 +479,7 @@ __global__ void __launch_bounds__(kBwdThreads, 3) attn_bwd_wide_kernel(const uin
     *reinterpret_cast<bf16x4*>(qd + tl * kQD + 4 * g) = dof;
     *reinterpret_cast<bf16x4*>(qd + tl * kQD + 16 + 4 * g) = qf;
     if (g == 0) ld[tl] = make_float2(L, dsum);
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     const float4 s01 = *reinterpret_cast<const float4*>(ld + 4 * g), s23 = *reinterpret_cast<const float4*>(ld + 4 * g + 2);
     const float Lr[4] = {s01.x, s01.z, s23.x, s23.z};
     const f32x4 negD = {s01.y, s01.w, s23.y, s23.w};
@@ -525,13 +520,13 @@ __global__ void __launch_bounds__(kBwdThreads, 3) attn_bwd_wide_kernel(const uin
         *reinterpret_cast<bf16x4*>(dsb + (16 * (j0 + j) + tl) * kSS + 4 * g) = dsf[j];  // [key][queries 4 g ..]
       }
     }
-    wave_lds_sync();
+    rl4co::lds_barrier_wave();
     f32x4 dq = zero4();
 #pragma clang loop unroll(full)
     for (int jt = 0; jt < NT; ++jt)
       dq = mfma16(lds_tr(kv + 16 * jt * kKH + 16 * w + tro), lds_tr(dsb + 16 * jt * kSS + tro_s), dq);
     if (tv) *reinterpret_cast<f32x4*>(dqp + (int64_t)t * kD) = dq;  // this chunk's share, unscaled: [dims 4 g ..] of query t
-    wave_lds_sync();  // the next query block rewrites this wave's staging block
+    rl4co::lds_barrier_wave();  // the next query block rewrites this wave's staging block
   }
   __syncthreads();  // every wave is done with k | v: the LDS becomes [128][d k | d v] of the four heads
   elem_t* os = reinterpret_cast<elem_t*>(smem);

@@ -283,6 +283,36 @@ def select_start_nodes(batch: int, num_starts: int, num_loc: int, has_depot: boo
     return out
 
 
+def _bind_cache_and_state(a, sp: EnvSpec, cache: FoldedCache, state: dict, b: int, n: int, ctx_table) -> list:
+    """What ``rl4co_am_decode_args`` and ``rl4co_am_decode_beam_args`` have in common (same field names): the three plane
+    pointers with their strides, the folded context (not in the unfolded parity mode) and the environment's state.
+    ``ctx_table(tensor, name)`` gives the tensor a context-table slot is bound to — the one difference between the two
+    kernels. Returns those tensors: the caller holds them until its launch."""
+    kvl = cache.kvl  # [3, B, N, 128]: plane pointers + (instance, node) strides — any view with unit channel stride
+    if not kvl.is_cuda:
+        raise _lib.Rl4coLibraryError(f"cache.kvl lives on {kvl.device}; the rl4co_amd kernels only run on the MI355X (no CPU fallback)")
+    if not (kvl.dim() == 4 and kvl.stride(3) == 1):
+        raise ValueError("cache.kvl must be [3, B, N, 128] with unit stride along the channels")
+    a.cache_dtype = _lib.dtype_id(kvl.dtype)
+    a.glimpse_key, a.glimpse_val, a.logit_key = (cache.plane(i).data_ptr() for i in range(3))
+    a.kvl_row_stride, a.kvl_batch_stride = cache.row_stride, cache.batch_stride
+    tables = []
+    if not cache.unfold:
+        tables.append(ctx_table(cache.ctx_cur, "ctx_cur"))
+        a.ctx_cur = _ptr(tables[-1])
+    a.q_bias = _ptr(None if cache.q_bias is None else _dev(cache.q_bias, torch.float32, "q_bias"))
+    if not cache.unfold:  # what the folded context needs besides its tables, by the context's layout
+        if sp.ctx_first:
+            tables.append(ctx_table(cache.ctx_first, "ctx_first"))
+            a.ctx_first = _ptr(tables[-1])
+            a.q_step0 = _ptr(_dev(cache.q_step0, torch.float32, "q_step0"))
+        if sp.scalar is not None:
+            a.w_cap = _ptr(_dev(cache.w_cap, torch.float32, "w_cap"))
+    b_inst = bind_env_state(a, sp, state, b, n)
+    assert b_inst == cache.num_instances or not sp.keys("inst"), "instance data rows must match cache instances"
+    return tables
+
+
 def am_decode(
     cache: FoldedCache,
     state: dict,
@@ -330,33 +360,18 @@ def am_decode(
     a.variant = VARIANT_IDS[variant]
     a.mask_inner, a.mask_logits = int(mask_inner), int(mask_logits)
     a.tanh_clipping, a.temperature = float(tanh_clipping), float(temperature)
-    kvl = cache.kvl  # [3, B, N, 128]: plane pointers + (instance, node) strides — any view with unit channel stride
-    if not kvl.is_cuda:
-        raise _lib.Rl4coLibraryError(f"cache.kvl lives on {kvl.device}; the rl4co_amd kernels only run on the MI355X (no CPU fallback)")
-    if not (kvl.dim() == 4 and kvl.stride(3) == 1):
-        raise ValueError("cache.kvl must be [3, B, N, 128] with unit stride along the channels")
-    a.cache_dtype = _lib.dtype_id(kvl.dtype)
-    a.glimpse_key, a.glimpse_val, a.logit_key = (cache.plane(i).data_ptr() for i in range(3))
-    a.kvl_row_stride, a.kvl_batch_stride = cache.row_stride, cache.batch_stride
+    if cache.unfold and not sp.unfold:
+        raise ValueError("the unfolded parity mode serves tsp / cvrp")
+    # 16-bit context tables go through as they are, with their strides (_ctx_table)
+    _bind_cache_and_state(a, sp, cache, state, b, n, lambda t, name: _ctx_table(a, t, cache.kvl.dtype, name))
     if cache.unfold:  # reference-association parity mode: per-step GEMVs against the raw weights (cache.py)
         a.unfold, a.ctx_width = 1, cache.w_ctx_t.shape[0]
         a.node_embed = _ptr(_dev(cache.node_embed, torch.float32, "node_embed"))
         a.w_ctx_t = _ptr(_dev(cache.w_ctx_t, torch.float32, "w_ctx_t"))
         a.w_out_t = _ptr(_dev(cache.w_out_t, torch.float32, "w_out_t"))
         a.w_placeholder = _ptr(None if cache.w_placeholder is None else _dev(cache.w_placeholder, torch.float32, "w_placeholder"))
-    else:
-        a.ctx_cur = _ptr(_ctx_table(a, cache.ctx_cur, kvl.dtype, "ctx_cur"))
-    a.q_bias = _ptr(None if cache.q_bias is None else _dev(cache.q_bias, torch.float32, "q_bias"))
-    if not cache.unfold:  # what the folded context needs besides its tables, by the context's layout
-        if sp.ctx_first:
-            a.ctx_first = _ptr(_ctx_table(a, cache.ctx_first, kvl.dtype, "ctx_first"))
-            a.q_step0 = _ptr(_dev(cache.q_step0, torch.float32, "q_step0"))
-        if sp.scalar is not None:
-            a.w_cap = _ptr(_dev(cache.w_cap, torch.float32, "w_cap"))
-            if sp.scalar.clock:
-                a.w_time = _ptr(_dev(cache.w_time, torch.float32, "w_time"))
-    if cache.unfold and not sp.unfold:
-        raise ValueError("the unfolded parity mode serves tsp / cvrp")
+    elif sp.scalar is not None and sp.scalar.clock:
+        a.w_time = _ptr(_dev(cache.w_time, torch.float32, "w_time"))
     if sp.dynamic is not None:  # the dynamic embedding, folded to three vectors (cache.fold_dynamic)
         dyn = _dev(cache.dyn, torch.float32, "dyn")
         if tuple(dyn.shape) != (3, 128):
@@ -370,8 +385,6 @@ def am_decode(
             raise ValueError(f"{sp.name} runs one trajectory per instance (no multistart rows): {b} trajectories over "
                              f"{cache.num_instances} instances")
         a.mtsp_ctx = feat.data_ptr()
-    b_inst = bind_env_state(a, sp, state, b, n)
-    assert b_inst == cache.num_instances or not sp.keys("inst"), "instance data rows must match cache instances"
     if exp_noise is not None:
         _dev(exp_noise, torch.float32, "exp_noise")
         assert exp_noise.numel() >= max_steps * b * n, "exp_noise must hold [max_steps,B,N] draws"
@@ -460,29 +473,11 @@ def am_decode_beam(
     a.env, a.B_inst, a.N, a.beam_width, a.max_steps = sp.env_id, cache.num_instances, n, w, int(max_steps)
     a.mask_inner, a.mask_logits = int(mask_inner), int(mask_logits)
     a.tanh_clipping, a.temperature = float(tanh_clipping), float(temperature)
-    kvl = cache.kvl
-    if not kvl.is_cuda:
-        raise _lib.Rl4coLibraryError(f"cache.kvl lives on {kvl.device}; the rl4co_amd kernels only run on the MI355X (no CPU fallback)")
-    if not (kvl.dim() == 4 and kvl.stride(3) == 1):
-        raise ValueError("cache.kvl must be [3, B, N, 128] with unit stride along the channels")
-    a.cache_dtype = _lib.dtype_id(kvl.dtype)
-    a.glimpse_key, a.glimpse_val, a.logit_key = (cache.plane(i).data_ptr() for i in range(3))
-    a.kvl_row_stride, a.kvl_batch_stride = cache.row_stride, cache.batch_stride
 
     def table(t: Tensor, name: str) -> Tensor:  # dense fp32 (a 16-bit table is widened: exact)
         return _dev(t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous(), torch.float32, name)
 
-    keep = [table(cache.ctx_cur, "ctx_cur")]
-    a.ctx_cur = _ptr(keep[0])
-    a.q_bias = _ptr(None if cache.q_bias is None else _dev(cache.q_bias, torch.float32, "q_bias"))
-    if sp.ctx_first:
-        keep.append(table(cache.ctx_first, "ctx_first"))
-        a.ctx_first = _ptr(keep[-1])
-        a.q_step0 = _ptr(_dev(cache.q_step0, torch.float32, "q_step0"))
-    if sp.scalar is not None:
-        a.w_cap = _ptr(_dev(cache.w_cap, torch.float32, "w_cap"))
-    b_inst = bind_env_state(a, sp, state, b, n)
-    assert b_inst == cache.num_instances or not sp.keys("inst"), "instance data rows must match cache instances"
+    keep = _bind_cache_and_state(a, sp, cache, state, b, n, table)  # noqa: F841  (alive until the launch)
     t_len = actions.shape[1]
     if t_len < int(max_steps) + 1:
         raise ValueError(f"outputs hold {t_len} columns, {int(max_steps)} steps need {int(max_steps) + 1}")

@@ -691,6 +691,24 @@ class AttentionModelPolicy(nn.Module):
                                select_best=select_best, exp_noise=exp_noise, seed=seed, select_start_nodes_fn=select_start_nodes_fn,
                                top_k=top_k, top_p=top_p)
 
+    def _folded_cache(self, hidden: Tensor, cache_dtype: torch.dtype, fold: bool):
+        """The decoder's cache when the encoder path did not produce it (fp16, the reference's "16-mixed": an fp32 fold)."""
+        fold_dtype = (torch.bfloat16 if self._encoder_regime() == torch.bfloat16 and cache_dtype != torch.float16
+                      else torch.float32)
+        with torch.no_grad():
+            return self.decoder.precompute_cache(hidden.detach(), cache_dtype, fold_dtype, fold=fold)
+
+    def _resolve_env(self, env: str | RL4COEnvBase | None):
+        return get_env(self.env_name if env is None else env) if (isinstance(env, str) or env is None) else env
+
+    def _impose_start_nodes(self, td: TensorDict, env, state: dict, num_starts: int, start_fn, err: Tensor) -> Tensor:
+        """pre_decoder_hook (decoding.py:306-326, 491-516): the imposed first node of every start / beam, log-prob 0, from
+        ``start_fn(td, env, num_starts)`` ([num_starts * B] nodes, s-major) or the environment; steps the state with them."""
+        first = (env.select_start_nodes(td, num_starts=num_starts) if start_fn is None else
+                 start_fn(td, env, num_starts).to(device=td["action_mask"].device, dtype=torch.int64).contiguous())
+        self._env_step_state(state, first, err)
+        return first
+
     def _forward(self, td: TensorDict, env: str | RL4COEnvBase | None = None, phase: str = "train",
                  calc_reward: bool = True, return_actions: bool = True, return_entropy: bool = False,
                  return_hidden: bool = False, return_init_embeds: bool = False,
@@ -721,8 +739,7 @@ class AttentionModelPolicy(nn.Module):
                 t.record_stream(cur)
         else:
             cache, hidden, init_embeds = self._encode_for_rollout(td, grad_path, cache_dtype, return_hidden, return_init_embeds)
-        if isinstance(env, str) or env is None:
-            env = get_env(self.env_name if env is None else env)
+        env = self._resolve_env(env)
         # 2. decoding arguments, in the reference's order of precedence
         opt = self._parse_decoding(td, env, phase, actions, decoding_kwargs)
         mode, multistart, n_rep = opt.mode, opt.multistart, opt.n_rep
@@ -758,11 +775,7 @@ class AttentionModelPolicy(nn.Module):
                 cache_g = teacher.build_cache_autograd(self.env_name, h_fold, self.decoder, fused_planes=fused_planes)
                 cache = teacher.detached_cache(self.env_name, cache_g, cache_dtype)
         if cache is None:
-            with torch.no_grad():
-                regime = self._encoder_regime()  # fp16 (the reference's default "16-mixed"): the fold stays fp32
-                cache = self.decoder.precompute_cache(hidden.detach(), cache_dtype,
-                                                      torch.bfloat16 if (regime == torch.bfloat16 and cache_dtype != torch.float16)
-                                                      else torch.float32, fold=self.fold)
+            cache = self._folded_cache(hidden, cache_dtype, self.fold)
         # (bench.py's byte model: the context rows a decode step gathers are fp32 or, r06, the planes' 16-bit type)
         self.last_ctx_elem_bytes = cache.ctx_cur.element_size() if cache.ctx_cur is not None else 4
         state = self._initial_state(td, n_rep)
@@ -798,12 +811,7 @@ class AttentionModelPolicy(nn.Module):
                      if (grad_path and filtered) else None)
 
         if t0 == 1:
-            if select_start_nodes_fn is not None:  # decoding.py:308-311: (td, env, num_starts) -> [num_starts * B] nodes, s-major
-                first = select_start_nodes_fn(td, env, n_rep).to(device=device, dtype=torch.int64).contiguous()
-            else:
-                first = env.select_start_nodes(td, num_starts=n_rep)
-            out_actions[:, 0] = first
-            self._env_step_state(state, first, err)
+            out_actions[:, 0] = self._impose_start_nodes(td, env, state, n_rep, select_start_nodes_fn, err)
 
         if mode == "sampling" and exp_noise is None:
             self._philox_calls += 1
@@ -899,8 +907,7 @@ class AttentionModelPolicy(nn.Module):
             kw.pop(k, None)
         if kw:  # num_starts, multisample, store_all_logp, seed, ...: arguments of the other strategies
             raise NotImplementedError(f"beam search does not take {sorted(kw)}")
-        if isinstance(env, str) or env is None:
-            env = get_env(self.env_name if env is None else env)
+        env = self._resolve_env(env)
         device = td["action_mask"].device
         b_inst, n = td["action_mask"].shape[0], td["action_mask"].shape[-1]
         width = int(env.get_num_starts(td) if beam_width is None else beam_width)
@@ -913,20 +920,12 @@ class AttentionModelPolicy(nn.Module):
             cache_dtype = self._plane_dtype(False)
             cache, hidden, _ = self._encode_for_rollout(td, False, cache_dtype, False, False)
             if cache is None:
-                regime = self._encoder_regime()
-                cache = self.decoder.precompute_cache(hidden.detach(), cache_dtype,
-                                                      torch.bfloat16 if (regime == torch.bfloat16 and cache_dtype != torch.float16)
-                                                      else torch.float32, fold=True)
+                cache = self._folded_cache(hidden, cache_dtype, True)
             state = self._initial_state(td, width)
             tmax = min(self._max_horizon(self.env_name, n), max(int(max_steps), 2))
             status = torch.zeros(4, dtype=torch.int32, device=device)
             err = status[:1]
-            # pre_decoder_hook (decoding.py:491-516): the imposed start node of every beam, log-prob 0
-            if start_fn is not None:
-                first = start_fn(td, env, width).to(device=device, dtype=torch.int64).contiguous()
-            else:
-                first = env.select_start_nodes(td, num_starts=width)
-            self._env_step_state(state, first, err)
+            self._impose_start_nodes(td, env, state, width, start_fn, err)  # (column 0 is written by the kernel)
             rows = width * b_inst
             out_actions = torch.zeros((rows, tmax), dtype=torch.int64, device=device)
             logps = torch.zeros((rows, tmax), dtype=torch.float32, device=device)
