@@ -108,6 +108,10 @@ extern "C" {
                                   CU; bf16 query / glimpse (pinned to the rounding-model oracle, 5e-3); every
                                   environment; auto where measured faster: TSP / PDP / PCTSP from 8 starts per
                                   instance, CVRP from 16 */
+#define RL4CO_VARIANT_STREAM_REG 5 /* STREAM with a step's per-head scores held in registers instead of LDS, whose
+                                  bytes go to a larger row cache (11 resident rows per trajectory at N = 100 instead
+                                  of 6); 16-bit planes, TSP / CVRP, N <= 112, not the unfolded mode; bit for bit
+                                  STREAM's results */
 
 #define RL4CO_EMBED_DIM 128 /* the engine is specialised for the AM default d=128, H=8 */
 #define RL4CO_NUM_HEADS 8
@@ -469,7 +473,8 @@ int rl4co_am_decode_lds_bytes(int N, int env);
  * into (row j -> group j % G). G fixes the fp32 summation tree of the glimpse (am_decode.hip
  * header), so the specified-order oracle asks for it instead of guessing. -1 on bad args. */
 int rl4co_am_decode_row_groups(const rl4co_am_decode_args* args); /* 0: variant without such a contract (MS) */
-/* The variant (RL4CO_VARIANT_STREAM / _LDS) rl4co_am_decode will run for `args`. */
+/* The variant (RL4CO_VARIANT_STREAM / _LDS / ...) rl4co_am_decode will run for `args`; -1: an explicit variant that
+ * cannot serve them. */
 int rl4co_am_decode_variant(const rl4co_am_decode_args* args);
 
 /* --------------------------------------------------------------------------

@@ -16,7 +16,7 @@ ABI_VERSION = 16  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argu
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
-VARIANT_AUTO, VARIANT_STREAM, VARIANT_LDS, VARIANT_WIDE, VARIANT_MS = 0, 1, 2, 3, 4
+VARIANT_AUTO, VARIANT_STREAM, VARIANT_LDS, VARIANT_WIDE, VARIANT_MS, VARIANT_STREAM_REG = 0, 1, 2, 3, 4, 5
 
 EBIT_NAN_LOGIT = 1
 EBIT_INFEASIBLE = 2

@@ -98,17 +98,19 @@ template <class C>
 struct CtxTables {
   const char *cur, *first;
   int64_t rs;  // bytes between node rows
+  int late;    // bytes added at every load (`late_e0`: the lane's first dim when e0 is passed as 0 to keep cur / first wave-uniform)
   bool half;
-  __device__ inline CtxTables(const rl4co_am_decode_args& a, int cb, int N, int e0) {
+  __device__ inline CtxTables(const rl4co_am_decode_args& a, int cb, int N, int e0, int late_e0 = 0) {
     half = a.ctx_dtype != RL4CO_DT_F32;
     const int64_t esz = half ? 2 : 4;
+    late = late_e0 * (int)esz;
     rs = (a.ctx_row_stride ? a.ctx_row_stride : (int64_t)kD) * esz;
     const int64_t off = ((int64_t)cb * (a.ctx_batch_stride ? a.ctx_batch_stride : (int64_t)N * kD) + e0) * esz;
     cur = a.ctx_cur ? static_cast<const char*>(a.ctx_cur) + off : nullptr;
     first = a.ctx_first ? static_cast<const char*>(a.ctx_first) + off : nullptr;
   }
   __device__ inline void load(const char* table, int64_t row, float (&v)[C::EPL]) const {
-    const char* p = table + row * rs;
+    const char* p = table + row * rs + late;
     if constexpr (sizeof(typename C::elem) == 2) {
       if (half) {
         C::cvt(C::ld(reinterpret_cast<const typename C::elem*>(p)), v);
@@ -426,13 +428,33 @@ __host__ __device__ inline int row_cache_bytes(int N, int S, int esz) {
   return S > 0 ? S * 3 * kD * esz + lds_pad(N) + S : 0;
 }
 
-template <class C, int ENV, bool UNFOLD = false, bool FILT = false>
-__global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_args a, const int S) {
+// REG (RL4CO_VARIANT_STREAM_REG; 16-bit planes, TSP / CVRP, N <= kRegMaxN): a step's per-head scores never go to LDS. Pass 2
+// walks the list positions of pass 1 with the same lanes — row group rg takes c = c0 + u RPL + rg in both — and a lane
+// needs only its own head's value of an entry, so pass 1 keeps them in registers (both loops fully unrolled, the outer
+// iterations behind wave-uniform c0 < F guards; the two lanes of a head hold half of an iteration's kUnroll values each:
+// kRegIters x kUnroll / 2 registers), the head maximum is the butterfly's result in every lane, and pass 2 takes
+// p = exp(score - max) from the register, the other lane's by one DPP move: the same function of the same inputs as the
+// numerators STREAM stages, each evaluated once. Without the score block (Np x 32 bytes) the same 10 KiB hold 11 resident
+// rows per trajectory at N = 100 instead of 6, and the two barriers around the staging leave the step. Not built with
+// the top-k / top-p filter (FILT): that instantiation does not fit 128 VGPRs without scratch.
+constexpr int kRegIters = 7;                              // outer iterations of a pass held in registers
+constexpr int kRegMaxN = kRegIters * 4 * kUnroll;         // 112: 4 rows per load (16-bit planes) x kUnroll loads
+// LDS of the REG layout before the row cache: lg | fl | mk | vis
+__host__ __device__ inline int stream_reg_lds_bytes(int N) {
+  const int Np = lds_pad(N);
+  return Np * 4 + Np * 2 + Np + Np;
+}
+
+// (REG: the register allocator is held to the 128 VGPRs of four waves per SIMD — left alone it spends the next occupancy
+// step's 168 on the held scores, and 4096 trajectories no longer fit the chip in one round)
+template <class C, int ENV, bool UNFOLD = false, bool FILT = false, bool REG = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(REG ? 4 : 1))) am_decode_kernel(const rl4co_am_decode_args a, const int S) {
   constexpr int EPL = C::EPL;
   constexpr int LPR = kD / EPL;   // lanes per cache row
   constexpr int RPL = 64 / LPR;   // rows per wave-wide load (= row groups G)
   constexpr int LPH = kDH / EPL;  // lanes per head
   constexpr bool kRowCache = !UNFOLD && (ENV == RL4CO_ENV_TSP || ENV == RL4CO_ENV_CVRP);
+  static_assert(!REG || (kRowCache && RPL == 4 && LPH == 2 && !FILT), "REG: 16-bit planes, TSP / CVRP, folded, no top-k / top-p");
   constexpr bool kDyn = ENV == RL4CO_ENV_SDVRP;            // dynamic embedding: d_j * (x . u) joins every dot product
   constexpr bool kMtsp = ENV == RL4CO_ENV_MTSP;            // four running scalars in the context, min-max state
   constexpr int NG = ((kDyn || kMtsp) && RPL == 4) ? kUnroll : 1;  // accumulator sets of pass 2 (SDVRP / MTSP, 16-bit planes: one per load)
@@ -447,9 +469,10 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   const int N = a.N;
   const int Np = lds_pad(N);
   float* sc = reinterpret_cast<float*>(smem);  // [Np*kH] per-head scores -> softmax numerators, (c*kH + h)
-  float* lg = sc + Np * kH;                    // [Np] raw logits -> clipped logits -> log-probs (list order)
+  float* lg = sc + (REG ? 0 : Np * kH);  // [Np] raw logits -> clipped logits -> log-probs (list order)
   float* mh = lg + Np;                         // [8] per-head score maxima
-  uint16_t* fl = reinterpret_cast<uint16_t*>(mh + kH);  // [Np] nodes this step reads, ascending
+  uint16_t* fl = reinterpret_cast<uint16_t*>(mh + (REG ? 0 : kH));  // [Np] nodes this step reads, ascending
+  // (REG: no score block and no mh — stream_reg_lds_bytes; `sc` is not used)
   uint8_t* mk = reinterpret_cast<uint8_t*>(fl + Np);    // [Np] 1 = feasible
   uint8_t* vis = mk + Np;                               // [Np] CVRP visited flags
   elem* rc = reinterpret_cast<elem*>(vis + Np);         // [S][3][128] row cache (16-byte aligned: 40 Np + 32 bytes in)
@@ -463,11 +486,14 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   const int hd = li / LPH;      // head this lane contributes to
   const int e0 = li * EPL;      // first embedding dim held by this lane
 
-  const elem* Kg = static_cast<const elem*>(a.glimpse_key) + (int64_t)cb * a.kvl_batch_stride + e0;
-  const elem* Vg = static_cast<const elem*>(a.glimpse_val) + (int64_t)cb * a.kvl_batch_stride + e0;
-  const elem* Kl = static_cast<const elem*>(a.logit_key) + (int64_t)cb * a.kvl_batch_stride + e0;
+  // (REG: the plane bases stay wave-uniform, in scalar registers; the lane's e0 joins at each load)
+  constexpr bool kLateE0 = REG;
+  const int pe0 = kLateE0 ? 0 : e0, le0 = kLateE0 ? e0 : 0;
+  const elem* Kg = static_cast<const elem*>(a.glimpse_key) + (int64_t)cb * a.kvl_batch_stride + pe0;
+  const elem* Vg = static_cast<const elem*>(a.glimpse_val) + (int64_t)cb * a.kvl_batch_stride + pe0;
+  const elem* Kl = static_cast<const elem*>(a.logit_key) + (int64_t)cb * a.kvl_batch_stride + pe0;
   const int64_t rs = a.kvl_row_stride;
-  const CtxTables<C> ctx(a, cb, N, e0);  // (UNFOLD: not read)
+  const CtxTables<C> ctx(a, cb, N, pe0, le0);  // (UNFOLD: not read)
   const float* hrow = UNFOLD ? a.node_embed + (int64_t)cb * N * kD + e0 : nullptr;
 
   // ---- load the trajectory state ---------------------------------------------------
@@ -540,8 +566,11 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
   };
 
   float qb[EPL];
+  auto load_qb = [&]() {
 #pragma unroll
-  for (int e = 0; e < EPL; ++e) qb[e] = a.q_bias ? a.q_bias[(int64_t)cb * kD + e0 + e] : 0.0f;
+    for (int e = 0; e < EPL; ++e) qb[e] = a.q_bias ? a.q_bias[(int64_t)cb * kD + e0 + e] : 0.0f;
+  };
+  if constexpr (!REG) load_qb();  // (REG reads it again every step, a cache hit, instead of holding 8 registers through the passes)
 
   const float* dynv = kDyn ? a.dyn_vectors + e0 : nullptr;  // (u_k, u_v, u_l') [3,128]: this lane's EPL dims of each
   const float* mg = kMtsp ? a.mtsp_ctx + e0 : nullptr;      // MTSP: g [4,128], this lane's EPL dims of each row
@@ -566,11 +595,16 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
       }
       hend = rl4co::bfly_i_max(last_hbm) + 1;
       pbeg = -rl4co::bfly_i_max(-first_pend);
+      if constexpr (REG) {  // wave-uniform: scalar registers
+        hend = __builtin_amdgcn_readfirstlane(hend);
+        pbeg = __builtin_amdgcn_readfirstlane(pbeg);
+      }
     }
     rows_read += hend;
 
     // ---- query: folded context projection + graph context (decoder.py:128-140) ------
     float q[EPL];
+    if constexpr (REG) load_qb();
     if constexpr (UNFOLD) {
       // context vector into LDS (the score buffer is dead between steps), then q = W_ctx . ctx + graph context
       float* cv = sc;
@@ -657,35 +691,57 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
       if constexpr (kDyn) acc = fmaf(j > 0 ? dd[j] : 0.0f, kq, acc);
       const bool feas = valid && (!a.mask_inner || mk[valid ? j : 0] != 0);
       const float sv = feas ? acc : kNegInf;
-      if (valid && (li % LPH) == 0) sc[c * kH + hd] = sv;
+      if constexpr (!REG) {
+        if (valid && (li % LPH) == 0) sc[c * kH + hd] = sv;
+      }
       m = fmaxf(m, sv);
+      return sv;
     };
-    for (int c0 = 0; c0 < F; c0 += RPL * kUnroll) {
+    // REG: the scores of the entries this lane's row group owns, of the lane's own head. The two lanes of a head hold the
+    // same values, so each keeps half: the first lane those of loads 0 and 1, the second those of loads 2 and 3
+    constexpr int kHeld = kUnroll / 2;
+    [[maybe_unused]] float sreg[REG ? kRegIters : 1][kHeld];
+    [[maybe_unused]] const bool second = (li % LPH) != 0;
+    auto score_batch = [&](int c0, float (&keep)[kHeld]) {
       raw_t rw[kUnroll];
       int jj[kUnroll];
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
         jj[u] = (c < F) ? (int)fl[c] : -1;
-        rw[u] = (jj[u] < 0) ? C::zero() : (c < hend ? C::ld(Kg + (int64_t)jj[u] * rs) : C::ld(lds_row(jj[u], 0)));
+        rw[u] = (jj[u] < 0) ? C::zero() : (c < hend ? C::ld(Kg + (int64_t)jj[u] * rs + le0) : C::ld(lds_row(jj[u], 0)));
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
         if (caching && c >= pbeg && c < hend) fill_row(jj[u], 0, rw[u]);
-        score(rw[u], c, jj[u]);
+        const float sv = score(rw[u], c, jj[u]);
+        if constexpr (REG) keep[u % kHeld] = (u < kHeld || second) ? sv : keep[u % kHeld];
       }
+    };
+    if constexpr (REG) {
+#pragma unroll
+      for (int it = 0; it < kRegIters; ++it)
+        if (it * RPL * kUnroll < F) score_batch(it * RPL * kUnroll, sreg[it]);
+    } else {
+      for (int c0 = 0; c0 < F; c0 += RPL * kUnroll) score_batch(c0, sreg[0]);
     }
-    m = rl4co::bfly_max<LPR, 64>(m);
-    if (rg == 0 && (li % LPH) == 0) mh[hd] = m;
-    rl4co::lds_barrier_wave();
-    // softmax numerators once per (list entry, head) — lane-strided over the F*8 scores, so
-    // each exp is evaluated exactly once (index % 8 = head is fixed per lane: 64 % 8 == 0)
-    {
-      const float mm = mh[lane & (kH - 1)];
-      for (int idx = lane; idx < F * kH; idx += 64) sc[idx] = rl4co_expf(sc[idx] - mm);
+    m = rl4co::bfly_max<LPR, 64>(m);  // (every lane: the maximum of its own head)
+    if constexpr (!REG) {
+      if (rg == 0 && (li % LPH) == 0) mh[hd] = m;
+      rl4co::lds_barrier_wave();
+      // softmax numerators once per (list entry, head) — lane-strided over the F*8 scores, so
+      // each exp is evaluated exactly once (index % 8 = head is fixed per lane: 64 % 8 == 0)
+      {
+        const float mm = mh[lane & (kH - 1)];
+        for (int idx = lane; idx < F * kH; idx += 64) sc[idx] = rl4co_expf(sc[idx] - mm);
+      }
+      rl4co::lds_barrier_wave();
+    } else {
+      // nothing passes through LDS here; but pass 2 must read its list entries again as STREAM does — carried over from
+      // the unrolled pass 1 they would cost four more registers per held iteration
+      asm volatile("" ::: "memory");
     }
-    rl4co::lds_barrier_wave();
 
     // ---- pass 2: softmax-weighted value sum ------------------------------------------------
     float lacc[NG], pdacc[NG];
@@ -697,10 +753,12 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
 #pragma unroll
       for (int e = 0; e < EPL; ++e) oacc[g][e] = 0.0f;
     }
-    auto accumulate = [&](const raw_t& rw, int c, bool ok, int g) {  // !ok: no entry (adds exact zeros)
+    auto accumulate = [&](const raw_t& rw, int c, bool ok, int g, float pr) {  // !ok: no entry (adds exact zeros)
       float v[EPL];
       C::cvt(rw, v);
-      const float p = ok ? sc[c * kH + hd] : 0.0f;
+      float p;
+      if constexpr (REG) p = ok ? pr : 0.0f;  // pr: the entry's numerator, from the score held since pass 1
+      else p = ok ? sc[c * kH + hd] : 0.0f;
       lacc[g] = lacc[g] + p;
       if constexpr (kDyn) {
         const int j = ok ? (int)fl[c] : 0;
@@ -709,21 +767,38 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
 #pragma unroll
       for (int e = 0; e < EPL; ++e) oacc[g][e] = fmaf(p, v[e], oacc[g][e]);
     };
-    for (int c0 = 0; c0 < F; c0 += RPL * kUnroll) {
+    auto value_batch = [&](int c0, const float (&kept)[kHeld]) {
       raw_t rw[kUnroll];
       bool ok[kUnroll];
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
         ok[u] = c < F;
-        rw[u] = !ok[u] ? C::zero() : (c < hend ? C::ld(Vg + (int64_t)fl[c] * rs) : C::ld(lds_row(fl[c], 1)));
+        rw[u] = !ok[u] ? C::zero() : (c < hend ? C::ld(Vg + (int64_t)fl[c] * rs + le0) : C::ld(lds_row(fl[c], 1)));
+      }
+      [[maybe_unused]] float pr[kUnroll];
+      if constexpr (REG) {  // each numerator once per head: exp(score - max) by the lane that holds it, the other's by DPP
+#pragma unroll
+        for (int k = 0; k < kHeld; ++k) {
+          const float own = rl4co_expf(kept[k] - m);
+          const float other = rl4co::bfly_f<1>(own);
+          pr[k] = second ? other : own;
+          pr[kHeld + k] = second ? own : other;
+        }
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
         if (caching && c >= pbeg && c < hend) fill_row(fl[c], 1, rw[u]);
-        accumulate(rw[u], c, ok[u], NG > 1 ? u : 0);
+        accumulate(rw[u], c, ok[u], NG > 1 ? u : 0, REG ? pr[u] : 0.0f);
       }
+    };
+    if constexpr (REG) {
+#pragma unroll
+      for (int it = 0; it < kRegIters; ++it)
+        if (it * RPL * kUnroll < F) value_batch(it * RPL * kUnroll, sreg[it]);
+    } else {
+      for (int c0 = 0; c0 < F; c0 += RPL * kUnroll) value_batch(c0, sreg[0]);
     }
     // tree over the row groups: the butterfly over a load's rows, then (NG = 4) ((g0 + g1) + (g2 + g3)) over the loads
     auto tree = [&](auto&& term) -> float {
@@ -779,7 +854,7 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int c = c0 + u * RPL + rg;
-        rw[u] = (c >= F) ? C::zero() : (c < hend ? C::ld(Kl + (int64_t)fl[c] * rs) : C::ld(lds_row(fl[c], 2)));
+        rw[u] = (c >= F) ? C::zero() : (c < hend ? C::ld(Kl + (int64_t)fl[c] * rs + le0) : C::ld(lds_row(fl[c], 2)));
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
@@ -798,6 +873,13 @@ __global__ void __launch_bounds__(64) am_decode_kernel(const rl4co_am_decode_arg
     rl4co::lds_barrier_wave();
 
     const int bi = finalize_and_step<ENV, FILT>(a, st, lg, sc, fl, F, mk, vis, dem, cap, r, t, N, lane, oplocs, opmax, twdur, dd);
+    if constexpr (REG) {  // the state is the same in every lane: held in scalar registers across the passes
+      st.cur = __builtin_amdgcn_readfirstlane(st.cur);
+      st.first = __builtin_amdgcn_readfirstlane(st.first);
+      st.errbits = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.errbits);
+      st.used = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, st.used)));
+      st.ent_acc = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, st.ent_acc)));
+    }
     if (caching && rslot[bi] != kRowCacheNone && !candidate(bi)) {
       // the resident node left: its slot goes to the highest candidate not resident, which the next step that lists
       // it reads from HBM anyway
@@ -1368,7 +1450,11 @@ inline int resolve_variant(const rl4co_am_decode_args& a) {
   if (a.variant == RL4CO_VARIANT_MS) return ms_ok ? RL4CO_VARIANT_MS : -1;
   const bool fits = bf16 && lds_variant_bytes(a.N) + wide_dyn_bytes(a.N, a.env) <= 80 * 1024;
   const bool wide_ok = bf16 && wide_scratch_bytes(a.N) + wide_dyn_bytes(a.N, a.env) <= 64 * 1024;
+  // STREAM with the step's scores in registers: 16-bit planes, the row-cache environments, N within its register array
+  // (not with the top-k / top-p filter: its instantiation needs 2 to 5 registers past the 128 of four waves per SIMD)
+  const bool reg_ok = bf16 && a.N <= kRegMaxN && (a.env == RL4CO_ENV_TSP || a.env == RL4CO_ENV_CVRP) && !rl4co::topkp_on(a);
   if (a.variant == RL4CO_VARIANT_STREAM) return RL4CO_VARIANT_STREAM;
+  if (a.variant == RL4CO_VARIANT_STREAM_REG) return reg_ok ? RL4CO_VARIANT_STREAM_REG : -1;
   if (a.variant == RL4CO_VARIANT_LDS) return fits ? RL4CO_VARIANT_LDS : -1;
   if (a.variant == RL4CO_VARIANT_WIDE) return wide_ok ? RL4CO_VARIANT_WIDE : -1;
   if (a.max_steps < 4) return RL4CO_VARIANT_STREAM;
@@ -1388,7 +1474,7 @@ inline int resolve_variant(const rl4co_am_decode_args& a) {
   // one wave per trajectory needs >= ~16 waves per CU to hide its latency chain: with fewer
   // trajectories than that, four waves per trajectory keep the memory pipes busier
   if (wide_ok && a.B <= 2048) return RL4CO_VARIANT_WIDE;
-  return RL4CO_VARIANT_STREAM;
+  return reg_ok ? RL4CO_VARIANT_STREAM_REG : RL4CO_VARIANT_STREAM;
 }
 
 // Workgroups of `bytes` LDS one CU holds, at most kStreamWgPerCu: the streaming kernel's register bound (<= 128 VGPRs,
@@ -1406,9 +1492,9 @@ inline int stream_wg_per_cu(int bytes, int gran) {
 // their 1536-byte rows leave room for 3 slots at N = 100, 5.9 % of the bytes, and the leg measured slower with them
 // (DESIGN 4.1). RL4CO_DECODE_ROW_CACHE = n (read at every launch, so one process can compare) sets at most n slots, fp32
 // planes included; 0 turns the cache off.
-int row_cache_slots(const rl4co_am_decode_args& a, int esz, bool unfold) {
+// `base`: the kernel's LDS without the cache (rl4co_am_decode_lds_bytes for STREAM, stream_reg_lds_bytes for STREAM_REG).
+int row_cache_slots(const rl4co_am_decode_args& a, int esz, bool unfold, int base) {
   if (unfold || a.max_steps == 1 || (a.env != RL4CO_ENV_TSP && a.env != RL4CO_ENV_CVRP)) return 0;  // (SDVRP: a visited node comes back)
-  const int base = rl4co_am_decode_lds_bytes(a.N, a.env);
   int S = 0;
   while (S < min(a.N, 255)) {
     const int bytes = base + row_cache_bytes(a.N, S + 1, esz);
@@ -1422,21 +1508,26 @@ int row_cache_slots(const rl4co_am_decode_args& a, int esz, bool unfold) {
   return esz == 4 ? 0 : S;
 }
 
-template <class C, int ENV, bool UNFOLD, bool FILT>
+template <class C, int ENV, bool UNFOLD, bool FILT, bool REG = false>
 int launch_f(const rl4co_am_decode_args& a, hipStream_t stream) {
-  const int S = row_cache_slots(a, (int)sizeof(typename C::elem), UNFOLD);
-  const int lds = rl4co_am_decode_lds_bytes(a.N, ENV) + row_cache_bytes(a.N, S, (int)sizeof(typename C::elem));
+  const int base = REG ? stream_reg_lds_bytes(a.N) : rl4co_am_decode_lds_bytes(a.N, ENV);
+  const int S = row_cache_slots(a, (int)sizeof(typename C::elem), UNFOLD, base);
+  const int lds = base + row_cache_bytes(a.N, S, (int)sizeof(typename C::elem));
   if (lds > 64 * 1024) {
-    RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(am_decode_kernel<C, ENV, UNFOLD, FILT>),
+    RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(am_decode_kernel<C, ENV, UNFOLD, FILT, REG>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
-  hipLaunchKernelGGL((am_decode_kernel<C, ENV, UNFOLD, FILT>), dim3(a.B), dim3(64), lds, stream, a, S);
+  hipLaunchKernelGGL((am_decode_kernel<C, ENV, UNFOLD, FILT, REG>), dim3(a.B), dim3(64), lds, stream, a, S);
   RL4CO_HIP_TRY(hipGetLastError());
   return RL4CO_OK;
 }
 template <class C, int ENV, bool UNFOLD = false>
 int launch(const rl4co_am_decode_args& a, hipStream_t stream) {
   return rl4co::topkp_on(a) ? launch_f<C, ENV, UNFOLD, true>(a, stream) : launch_f<C, ENV, UNFOLD, false>(a, stream);
+}
+template <class C, int ENV>  // RL4CO_VARIANT_STREAM_REG
+int launch_reg(const rl4co_am_decode_args& a, hipStream_t stream) {
+  return launch_f<C, ENV, false, false, true>(a, stream);
 }
 
 }  // namespace
@@ -1515,7 +1606,7 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
     RL4CO_REQUIRE(a.w_cap && a.locs && a.max_length && a.used_capacity && a.step_i && a.visited);
   }
   RL4CO_REQUIRE(rl4co_am_decode_lds_bytes(a.N, a.env) <= 160 * 1024);
-  RL4CO_REQUIRE(a.variant >= RL4CO_VARIANT_AUTO && a.variant <= RL4CO_VARIANT_MS);
+  RL4CO_REQUIRE(a.variant >= RL4CO_VARIANT_AUTO && a.variant <= RL4CO_VARIANT_STREAM_REG);
   const int variant = resolve_variant(a);
   RL4CO_REQUIRE(variant >= 0);  // explicit variant requested that cannot serve these planes
   hipStream_t s = rl4co::as_stream(stream);
@@ -1526,6 +1617,11 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
   }
   if (variant == RL4CO_VARIANT_MS && a.cache_dtype == RL4CO_DT_F16) return rl4co::launch_decode_ms_f16(a, s);
   if (variant == RL4CO_VARIANT_MS) return rl4co::launch_decode_ms(a, s);
+  if (variant == RL4CO_VARIANT_STREAM_REG) {  // (resolve_variant: 16-bit planes, TSP or CVRP)
+    if (a.cache_dtype == RL4CO_DT_F16)
+      return a.env == RL4CO_ENV_TSP ? launch_reg<CacheF16, RL4CO_ENV_TSP>(a, s) : launch_reg<CacheF16, RL4CO_ENV_CVRP>(a, s);
+    return a.env == RL4CO_ENV_TSP ? launch_reg<CacheBF16, RL4CO_ENV_TSP>(a, s) : launch_reg<CacheBF16, RL4CO_ENV_CVRP>(a, s);
+  }
   if (variant == RL4CO_VARIANT_LDS || variant == RL4CO_VARIANT_WIDE) {
     const bool res = variant == RL4CO_VARIANT_LDS;
     switch (a.env) {
