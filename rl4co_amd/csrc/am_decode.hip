@@ -82,6 +82,7 @@
 
 #include "common.h"
 #include "decode_wave.h"
+#include "env_table.h"
 #include "rl4co_math.h"
 #include "topkp.h"
 
@@ -1415,6 +1416,11 @@ __global__ void __launch_bounds__(64 * kLdsWaves, 4) am_decode_wide_kernel(const
   }
 }
 
+using rl4co::EnvRecord;
+using PlanesF32 = rl4co::Planes<RL4CO_DT_F32, CacheF32>;
+using PlanesBF16 = rl4co::Planes<RL4CO_DT_BF16, CacheBF16>;
+using PlanesF16 = rl4co::Planes<RL4CO_DT_F16, CacheF16>;
+
 template <int ENV, bool RESIDENT, class C, bool FILT>
 int launch_wide_f(const rl4co_am_decode_args& a, hipStream_t stream) {
   const int lds = (RESIDENT ? lds_variant_bytes(a.N) : wide_scratch_bytes(a.N)) + wide_dyn_bytes(a.N, ENV);
@@ -1426,50 +1432,39 @@ int launch_wide_f(const rl4co_am_decode_args& a, hipStream_t stream) {
   RL4CO_HIP_TRY(hipGetLastError());
   return RL4CO_OK;
 }
-template <int ENV, bool RESIDENT, class C>
-int launch_wide_c(const rl4co_am_decode_args& a, hipStream_t stream) {
-  return rl4co::topkp_on(a) ? launch_wide_f<ENV, RESIDENT, C, true>(a, stream) : launch_wide_f<ENV, RESIDENT, C, false>(a, stream);
-}
-template <int ENV, bool RESIDENT>
-int launch_wide(const rl4co_am_decode_args& a, hipStream_t stream) {
-  return a.cache_dtype == RL4CO_DT_F16 ? launch_wide_c<ENV, RESIDENT, CacheF16>(a, stream)
-                                       : launch_wide_c<ENV, RESIDENT, CacheBF16>(a, stream);
+template <int ENV, class C>  // RL4CO_VARIANT_LDS (resident planes) / RL4CO_VARIANT_WIDE
+int launch_wide(const rl4co_am_decode_args& a, bool resident, hipStream_t stream) {
+  const bool filt = rl4co::topkp_on(a);
+  if (resident) return filt ? launch_wide_f<ENV, true, C, true>(a, stream) : launch_wide_f<ENV, true, C, false>(a, stream);
+  return filt ? launch_wide_f<ENV, false, C, true>(a, stream) : launch_wide_f<ENV, false, C, false>(a, stream);
 }
 
-// Which kernel serves these arguments (rules from measurements on MI355X, see the kernel headers).
+// Which kernel serves these arguments (rules from measurements on MI355X, see the kernel headers; per environment:
+// env_table.h).
 inline int resolve_variant(const rl4co_am_decode_args& a) {
+  const EnvRecord* env = rl4co::env_record(a.env);
+  if (env == nullptr) return -1;
   // the unfolded parity mode exists in the streaming kernel only
   if (a.unfold) return (a.variant == RL4CO_VARIANT_AUTO || a.variant == RL4CO_VARIANT_STREAM) ? RL4CO_VARIANT_STREAM : -1;
   const bool f16 = a.cache_dtype == RL4CO_DT_F16;  // fp16 planes: every variant the bf16 planes have
   const bool bf16 = a.cache_dtype == RL4CO_DT_BF16 || f16;  // (16-bit planes)
-  // multistart on the matrix cores (am_decode_ms.hip): 16-bit planes, N <= 128, plain outputs; every environment
+  // multistart on the matrix cores (am_decode_ms.hip): 16-bit planes, N <= 128, plain outputs
   const bool ms_ok = bf16 && a.N <= 128 && a.B_inst > 0 && a.all_logps == nullptr && a.entropy == nullptr &&
-                     !rl4co::topkp_on(a) &&           // the top-k / top-p filter is not in am_decode_ms.hip
-                     a.env != RL4CO_ENV_SDVRP &&      // nor is the dynamic embedding
-                     a.env != RL4CO_ENV_MTSP;         // nor the four-scalar context and the min-max state
+                     !rl4co::topkp_on(a) &&  // the top-k / top-p filter is not in am_decode_ms.hip
+                     env->ms;
   if (a.variant == RL4CO_VARIANT_MS) return ms_ok ? RL4CO_VARIANT_MS : -1;
   const bool fits = bf16 && lds_variant_bytes(a.N) + wide_dyn_bytes(a.N, a.env) <= 80 * 1024;
   const bool wide_ok = bf16 && wide_scratch_bytes(a.N) + wide_dyn_bytes(a.N, a.env) <= 64 * 1024;
   // STREAM with the step's scores in registers: 16-bit planes, the row-cache environments, N within its register array
   // (not with the top-k / top-p filter: its instantiation needs 2 to 5 registers past the 128 of four waves per SIMD)
-  const bool reg_ok = bf16 && a.N <= kRegMaxN && (a.env == RL4CO_ENV_TSP || a.env == RL4CO_ENV_CVRP) && !rl4co::topkp_on(a);
+  const bool reg_ok = bf16 && a.N <= kRegMaxN && env->stream_reg && !rl4co::topkp_on(a);
   if (a.variant == RL4CO_VARIANT_STREAM) return RL4CO_VARIANT_STREAM;
   if (a.variant == RL4CO_VARIANT_STREAM_REG) return reg_ok ? RL4CO_VARIANT_STREAM_REG : -1;
   if (a.variant == RL4CO_VARIANT_LDS) return fits ? RL4CO_VARIANT_LDS : -1;
   if (a.variant == RL4CO_VARIANT_WIDE) return wide_ok ? RL4CO_VARIANT_WIDE : -1;
   if (a.max_steps < 4) return RL4CO_VARIANT_STREAM;
-  // auto where it was measured faster than one wave per trajectory (N = 100, 4096 instances, sampling, r02; M trajectory-
-  // steps/s MS vs STREAM): TSP 8 starts 667 vs 276; pickup-delivery 8 starts 633 vs 379; prize-collecting TSP 8 starts
-  // 442 vs 178; CVRP 8 starts 254 vs 277 but 16 starts 463 vs 276 (a full 16-column tile). Orienteering (7-step
-  // ragged tours under random weights: 84 vs 162) and CVRP with time windows (111 vs 278: the per-step mask over all
-  // nodes with a square root each, replicated in every lane of the column) stay on STREAM unless MS is asked for
-  // r03, with two instances per column tile at <= 8 starts (a launch then costs ~3.3 ms for 4096 instances whatever
-  // the start count; tools/ms_bench.py, sampling, 4096 x S): TSP 3 starts 3.26 vs 5.11 ms (2: 3.24 vs 3.59), prize-
-  // collecting TSP 3 starts 3.38 vs 5.09, pickup-delivery 3 starts 3.43 vs 3.64 (2: 3.42 vs 2.58 — STREAM), CVRP 8 starts
-  // 13.6 vs 14.3 (4: 13.3 vs 7.8 — STREAM: every column of a tile runs to the tile's longest tour)
-  const int ms_from = (a.env == RL4CO_ENV_TSP || a.env == RL4CO_ENV_PDP || a.env == RL4CO_ENV_PCTSP) ? 3
-                      : (a.env == RL4CO_ENV_CVRP ? 8 : 0);
-  if (ms_ok && ms_from > 0 && a.B >= ms_from * a.B_inst) return RL4CO_VARIANT_MS;
+  // auto: MS from the start count at which it was measured faster than one wave per trajectory (EnvRecord::ms_from)
+  if (ms_ok && env->ms_from > 0 && a.B >= env->ms_from * a.B_inst) return RL4CO_VARIANT_MS;
   if (fits && a.B <= 1024) return RL4CO_VARIANT_LDS;
   // one wave per trajectory needs >= ~16 waves per CU to hide its latency chain: with fewer
   // trajectories than that, four waves per trajectory keep the memory pipes busier
@@ -1494,7 +1489,7 @@ inline int stream_wg_per_cu(int bytes, int gran) {
 // planes included; 0 turns the cache off.
 // `base`: the kernel's LDS without the cache (rl4co_am_decode_lds_bytes for STREAM, stream_reg_lds_bytes for STREAM_REG).
 int row_cache_slots(const rl4co_am_decode_args& a, int esz, bool unfold, int base) {
-  if (unfold || a.max_steps == 1 || (a.env != RL4CO_ENV_TSP && a.env != RL4CO_ENV_CVRP)) return 0;  // (SDVRP: a visited node comes back)
+  if (unfold || a.max_steps == 1 || !rl4co::env_served(a.env, &EnvRecord::row_cache)) return 0;  // (SDVRP: a visited node comes back)
   int S = 0;
   while (S < min(a.N, 255)) {
     const int bytes = base + row_cache_bytes(a.N, S + 1, esz);
@@ -1543,7 +1538,7 @@ extern "C" int rl4co_am_decode_row_groups(const rl4co_am_decode_args* args) {
   if (v < 0) return -1;
   if (v == RL4CO_VARIANT_MS) return 0;  // bf16 MFMA variant: tolerance-tested, no specified-order oracle
   if (v == RL4CO_VARIANT_LDS || v == RL4CO_VARIANT_WIDE) return kLdsGroups;
-  if ((args->env == RL4CO_ENV_SDVRP || args->env == RL4CO_ENV_MTSP) && args->cache_dtype != RL4CO_DT_F32) return kLdsGroups;  // one accumulator per load
+  if (rl4co::env_served(args->env, &EnvRecord::one_acc16) && args->cache_dtype != RL4CO_DT_F32) return kLdsGroups;  // one accumulator per load
   return args->cache_dtype != RL4CO_DT_F32 ? 64 / (kD / CacheBF16::EPL) : 64 / (kD / CacheF32::EPL);
 }
 
@@ -1554,9 +1549,7 @@ extern "C" int rl4co_am_decode_variant(const rl4co_am_decode_args* args) {
 extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
   RL4CO_REQUIRE(args != nullptr);
   const rl4co_am_decode_args& a = *args;
-  RL4CO_REQUIRE(a.env == RL4CO_ENV_TSP || a.env == RL4CO_ENV_CVRP || a.env == RL4CO_ENV_OP ||
-                a.env == RL4CO_ENV_PCTSP || a.env == RL4CO_ENV_PDP || a.env == RL4CO_ENV_CVRPTW || a.env == RL4CO_ENV_SDVRP ||
-                a.env == RL4CO_ENV_MTSP);
+  RL4CO_REQUIRE(rl4co::env_served(a.env, &EnvRecord::decode));
   RL4CO_REQUIRE(a.B > 0 && a.B_inst > 0 && a.B % a.B_inst == 0);
   RL4CO_REQUIRE(a.N >= 2 && a.N <= 4096);
   RL4CO_REQUIRE(a.max_steps >= 1);
@@ -1571,7 +1564,7 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
   RL4CO_REQUIRE(a.ctx_batch_stride == 0 || (a.ctx_batch_stride >= (int64_t)a.N * kD && a.ctx_batch_stride % 8 == 0));
   RL4CO_REQUIRE(a.ctx_dtype == RL4CO_DT_F32 || ((reinterpret_cast<uintptr_t>(a.ctx_cur) | reinterpret_cast<uintptr_t>(a.ctx_first)) & 15) == 0);
   if (a.unfold) {
-    RL4CO_REQUIRE(a.env == RL4CO_ENV_TSP || a.env == RL4CO_ENV_CVRP);
+    RL4CO_REQUIRE(rl4co::env_served(a.env, &EnvRecord::unfold));
     RL4CO_REQUIRE(a.node_embed && a.w_ctx_t && a.w_out_t);
     RL4CO_REQUIRE(a.ctx_width == (a.env == RL4CO_ENV_TSP ? 2 * kD : kD + 1));
     RL4CO_REQUIRE(a.env != RL4CO_ENV_TSP || a.w_placeholder);
@@ -1586,6 +1579,7 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
   RL4CO_REQUIRE(a.top_p == a.top_p && a.top_p <= 1.0f);  // decoding.py:147 "top-p should be in (0, 1]."
   RL4CO_REQUIRE(a.kept_bits == nullptr || (a.kept_words >= (a.N + 31) / 32 && a.kept_words % 4 == 0 &&
                                            (reinterpret_cast<uintptr_t>(a.kept_bits) & 3) == 0));
+  // the argument slots an environment needs (which state tensor rides in which slot: envspec.py)
   if (a.env == RL4CO_ENV_TSP) {
     RL4CO_REQUIRE(((a.ctx_first && a.q_step0) || a.unfold) && a.first_node && a.step_i);
   } else if (a.env == RL4CO_ENV_CVRP) {
@@ -1610,61 +1604,23 @@ extern "C" int rl4co_am_decode(const rl4co_am_decode_args* args, void* stream) {
   const int variant = resolve_variant(a);
   RL4CO_REQUIRE(variant >= 0);  // explicit variant requested that cannot serve these planes
   hipStream_t s = rl4co::as_stream(stream);
-  if (a.unfold) {
-    if (a.cache_dtype == RL4CO_DT_F32)
-      return a.env == RL4CO_ENV_TSP ? launch<CacheF32, RL4CO_ENV_TSP, true>(a, s) : launch<CacheF32, RL4CO_ENV_CVRP, true>(a, s);
-    return a.env == RL4CO_ENV_TSP ? launch<CacheBF16, RL4CO_ENV_TSP, true>(a, s) : launch<CacheBF16, RL4CO_ENV_CVRP, true>(a, s);
-  }
-  if (variant == RL4CO_VARIANT_MS && a.cache_dtype == RL4CO_DT_F16) return rl4co::launch_decode_ms_f16(a, s);
-  if (variant == RL4CO_VARIANT_MS) return rl4co::launch_decode_ms(a, s);
-  if (variant == RL4CO_VARIANT_STREAM_REG) {  // (resolve_variant: 16-bit planes, TSP or CVRP)
-    if (a.cache_dtype == RL4CO_DT_F16)
-      return a.env == RL4CO_ENV_TSP ? launch_reg<CacheF16, RL4CO_ENV_TSP>(a, s) : launch_reg<CacheF16, RL4CO_ENV_CVRP>(a, s);
-    return a.env == RL4CO_ENV_TSP ? launch_reg<CacheBF16, RL4CO_ENV_TSP>(a, s) : launch_reg<CacheBF16, RL4CO_ENV_CVRP>(a, s);
-  }
-  if (variant == RL4CO_VARIANT_LDS || variant == RL4CO_VARIANT_WIDE) {
-    const bool res = variant == RL4CO_VARIANT_LDS;
-    switch (a.env) {
-      case RL4CO_ENV_TSP: return res ? launch_wide<RL4CO_ENV_TSP, true>(a, s) : launch_wide<RL4CO_ENV_TSP, false>(a, s);
-      case RL4CO_ENV_CVRP: return res ? launch_wide<RL4CO_ENV_CVRP, true>(a, s) : launch_wide<RL4CO_ENV_CVRP, false>(a, s);
-      case RL4CO_ENV_OP: return res ? launch_wide<RL4CO_ENV_OP, true>(a, s) : launch_wide<RL4CO_ENV_OP, false>(a, s);
-      case RL4CO_ENV_PCTSP: return res ? launch_wide<RL4CO_ENV_PCTSP, true>(a, s) : launch_wide<RL4CO_ENV_PCTSP, false>(a, s);
-      case RL4CO_ENV_PDP: return res ? launch_wide<RL4CO_ENV_PDP, true>(a, s) : launch_wide<RL4CO_ENV_PDP, false>(a, s);
-      case RL4CO_ENV_SDVRP: return res ? launch_wide<RL4CO_ENV_SDVRP, true>(a, s) : launch_wide<RL4CO_ENV_SDVRP, false>(a, s);
-      case RL4CO_ENV_MTSP: return res ? launch_wide<RL4CO_ENV_MTSP, true>(a, s) : launch_wide<RL4CO_ENV_MTSP, false>(a, s);
-      default: return res ? launch_wide<RL4CO_ENV_CVRPTW, true>(a, s) : launch_wide<RL4CO_ENV_CVRPTW, false>(a, s);
-    }
-  }
-  if (a.cache_dtype == RL4CO_DT_F16) {
-    switch (a.env) {
-      case RL4CO_ENV_TSP: return launch<CacheF16, RL4CO_ENV_TSP>(a, s);
-      case RL4CO_ENV_CVRP: return launch<CacheF16, RL4CO_ENV_CVRP>(a, s);
-      case RL4CO_ENV_OP: return launch<CacheF16, RL4CO_ENV_OP>(a, s);
-      case RL4CO_ENV_PCTSP: return launch<CacheF16, RL4CO_ENV_PCTSP>(a, s);
-      case RL4CO_ENV_PDP: return launch<CacheF16, RL4CO_ENV_PDP>(a, s);
-      case RL4CO_ENV_SDVRP: return launch<CacheF16, RL4CO_ENV_SDVRP>(a, s);
-      case RL4CO_ENV_MTSP: return launch<CacheF16, RL4CO_ENV_MTSP>(a, s);
-      default: return launch<CacheF16, RL4CO_ENV_CVRPTW>(a, s);
-    }
-  }
-  if (a.env == RL4CO_ENV_MTSP)
-    return a.cache_dtype == RL4CO_DT_F32 ? launch<CacheF32, RL4CO_ENV_MTSP>(a, s) : launch<CacheBF16, RL4CO_ENV_MTSP>(a, s);
-  if (a.env == RL4CO_ENV_SDVRP)
-    return a.cache_dtype == RL4CO_DT_F32 ? launch<CacheF32, RL4CO_ENV_SDVRP>(a, s) : launch<CacheBF16, RL4CO_ENV_SDVRP>(a, s);
-  if (a.env == RL4CO_ENV_CVRPTW)
-    return a.cache_dtype == RL4CO_DT_F32 ? launch<CacheF32, RL4CO_ENV_CVRPTW>(a, s)
-                                         : launch<CacheBF16, RL4CO_ENV_CVRPTW>(a, s);
-  if (a.env == RL4CO_ENV_PDP)
-    return a.cache_dtype == RL4CO_DT_F32 ? launch<CacheF32, RL4CO_ENV_PDP>(a, s) : launch<CacheBF16, RL4CO_ENV_PDP>(a, s);
-  if (a.env == RL4CO_ENV_PCTSP)
-    return a.cache_dtype == RL4CO_DT_F32 ? launch<CacheF32, RL4CO_ENV_PCTSP>(a, s)
-                                         : launch<CacheBF16, RL4CO_ENV_PCTSP>(a, s);
-  if (a.env == RL4CO_ENV_OP)
-    return a.cache_dtype == RL4CO_DT_F32 ? launch<CacheF32, RL4CO_ENV_OP>(a, s) : launch<CacheBF16, RL4CO_ENV_OP>(a, s);
-  if (a.cache_dtype == RL4CO_DT_F32) {
-    return a.env == RL4CO_ENV_TSP ? launch<CacheF32, RL4CO_ENV_TSP>(a, s)
-                                  : launch<CacheF32, RL4CO_ENV_CVRP>(a, s);
-  }
-  return a.env == RL4CO_ENV_TSP ? launch<CacheBF16, RL4CO_ENV_TSP>(a, s)
-                                : launch<CacheBF16, RL4CO_ENV_CVRP>(a, s);
+  if (variant == RL4CO_VARIANT_MS) return a.cache_dtype == RL4CO_DT_F16 ? rl4co::launch_decode_ms_f16(a, s) : rl4co::launch_decode_ms(a, s);
+  // the kernels of this file: plane type, then environment (the builds that exist: the column of env_table.h)
+  if (a.unfold)
+    return rl4co::dispatch_planes<PlanesF32, PlanesBF16>(a.cache_dtype, [&](auto p) {
+      return rl4co::dispatch_env<&EnvRecord::unfold>(a.env, [&](auto e) { return launch<typename decltype(p)::type, decltype(e)::value, true>(a, s); });
+    });
+  if (variant == RL4CO_VARIANT_STREAM_REG)
+    return rl4co::dispatch_planes<PlanesBF16, PlanesF16>(a.cache_dtype, [&](auto p) {
+      return rl4co::dispatch_env<&EnvRecord::stream_reg>(a.env, [&](auto e) { return launch_reg<typename decltype(p)::type, decltype(e)::value>(a, s); });
+    });
+  if (variant == RL4CO_VARIANT_LDS || variant == RL4CO_VARIANT_WIDE)
+    return rl4co::dispatch_planes<PlanesBF16, PlanesF16>(a.cache_dtype, [&](auto p) {
+      return rl4co::dispatch_env<&EnvRecord::decode>(a.env, [&](auto e) {
+        return launch_wide<decltype(e)::value, typename decltype(p)::type>(a, variant == RL4CO_VARIANT_LDS, s);
+      });
+    });
+  return rl4co::dispatch_planes<PlanesF32, PlanesBF16, PlanesF16>(a.cache_dtype, [&](auto p) {
+    return rl4co::dispatch_env<&EnvRecord::decode>(a.env, [&](auto e) { return launch<typename decltype(p)::type, decltype(e)::value>(a, s); });
+  });
 }

@@ -59,6 +59,7 @@
 
 #include "common.h"
 #include "decode_wave.h"
+#include "env_table.h"
 #include "rl4co_math.h"
 
 namespace {
@@ -526,11 +527,6 @@ int launch(const rl4co_am_decode_beam_args& a, hipStream_t stream) {
   return RL4CO_OK;
 }
 
-template <class C>
-int launch_env(const rl4co_am_decode_beam_args& a, hipStream_t stream) {
-  return a.env == RL4CO_ENV_TSP ? launch<C, RL4CO_ENV_TSP>(a, stream) : launch<C, RL4CO_ENV_CVRP>(a, stream);
-}
-
 }  // namespace
 
 extern "C" int rl4co_am_decode_beam_max_width(int N) {
@@ -543,7 +539,7 @@ extern "C" int rl4co_am_decode_beam_max_width(int N) {
 extern "C" int rl4co_am_decode_beam(const rl4co_am_decode_beam_args* args, void* stream) {
   RL4CO_REQUIRE(args != nullptr);
   const rl4co_am_decode_beam_args& a = *args;
-  RL4CO_REQUIRE(a.env == RL4CO_ENV_TSP || a.env == RL4CO_ENV_CVRP);
+  RL4CO_REQUIRE(rl4co::env_served(a.env, &rl4co::EnvRecord::beam));
   RL4CO_REQUIRE(a.B_inst > 0);
   RL4CO_REQUIRE(a.N >= 2 && a.N <= 1024);
   RL4CO_REQUIRE(a.beam_width >= 2);  // decoding.py:494 "beam width must be larger than 1"
@@ -566,7 +562,9 @@ extern "C" int rl4co_am_decode_beam(const rl4co_am_decode_beam_args* args, void*
     RL4CO_REQUIRE(a.w_cap && a.demand && a.used_capacity && a.vehicle_capacity && a.visited);
   }
   hipStream_t s = rl4co::as_stream(stream);
-  if (a.cache_dtype == RL4CO_DT_F32) return launch_env<CacheF32>(a, s);
-  if (a.cache_dtype == RL4CO_DT_F16) return launch_env<CacheF16>(a, s);
-  return launch_env<CacheBF16>(a, s);
+  using rl4co::Planes;
+  return rl4co::dispatch_planes<Planes<RL4CO_DT_F32, CacheF32>, Planes<RL4CO_DT_BF16, CacheBF16>, Planes<RL4CO_DT_F16, CacheF16>>(
+      a.cache_dtype, [&](auto p) {
+        return rl4co::dispatch_env<&rl4co::EnvRecord::beam>(a.env, [&](auto e) { return launch<typename decltype(p)::type, decltype(e)::value>(a, s); });
+      });
 }

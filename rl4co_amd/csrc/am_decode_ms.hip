@@ -37,6 +37,7 @@
 
 #include "common.h"
 #include "elem16.h"
+#include "env_table.h"
 #include "rl4co_math.h"
 
 namespace {
@@ -999,15 +1000,7 @@ int RL4CO_CXX(launch_decode_ms)(const rl4co_am_decode_args& a, hipStream_t strea
 #ifdef RL4CO_MS_PROBE_ONLY  // timing probes (tools/ms_variants.sh): one instantiation instead of 144 — a 10 s build
   return launch_mode<RL4CO_ENV_TSP, 7, RL4CO_DECODE_SAMPLE>(a, stream);
 #else
-  switch (a.env) {
-    case RL4CO_ENV_TSP: return dispatch_tiles<RL4CO_ENV_TSP>(a, stream);
-    case RL4CO_ENV_CVRP: return dispatch_tiles<RL4CO_ENV_CVRP>(a, stream);
-    case RL4CO_ENV_OP: return dispatch_tiles<RL4CO_ENV_OP>(a, stream);
-    case RL4CO_ENV_PCTSP: return dispatch_tiles<RL4CO_ENV_PCTSP>(a, stream);
-    case RL4CO_ENV_PDP: return dispatch_tiles<RL4CO_ENV_PDP>(a, stream);
-    case RL4CO_ENV_CVRPTW: return dispatch_tiles<RL4CO_ENV_CVRPTW>(a, stream);
-    default: return RL4CO_ERR_ARG;
-  }
+  return dispatch_env<&EnvRecord::ms>(a.env, [&](auto e) { return dispatch_tiles<decltype(e)::value>(a, stream); });
 #endif
 }
 }  // namespace rl4co

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "env_table.h"
 
 namespace {
 
@@ -557,8 +558,7 @@ int dispatch_rows(const rl4co_am_teacher_args& a, hipStream_t s) {
 extern "C" int rl4co_am_teacher_max_nodes(void) { return 128; }
 
 static int validate_teacher(const rl4co_am_teacher_args& a) {
-  RL4CO_REQUIRE(a.env == RL4CO_ENV_TSP || a.env == RL4CO_ENV_CVRP || a.env == RL4CO_ENV_OP ||
-                a.env == RL4CO_ENV_PCTSP || a.env == RL4CO_ENV_PDP || a.env == RL4CO_ENV_CVRPTW);
+  RL4CO_REQUIRE(rl4co::env_served(a.env, &rl4co::EnvRecord::teacher));
   RL4CO_REQUIRE(a.B > 0 && a.B_inst > 0 && a.B % a.B_inst == 0);
   RL4CO_REQUIRE(a.N >= 2 && a.N <= 128 && a.T >= 1 && a.t0 >= 0 && a.t0 <= 1);
   RL4CO_REQUIRE(a.cache_dtype == RL4CO_DT_F32 || a.cache_dtype == RL4CO_DT_BF16 || a.cache_dtype == RL4CO_DT_F16);
@@ -619,12 +619,5 @@ extern "C" int rl4co_am_teacher_backward(const rl4co_am_teacher_args* args, void
   hipStream_t s = rl4co::as_stream(stream);
   if (variant == RL4CO_TEACHER_MMA)
     return a.cache_dtype == RL4CO_DT_F16 ? rl4co::launch_teacher_mma_f16(a, s) : rl4co::launch_teacher_mma(a, s);
-  switch (a.env) {
-    case RL4CO_ENV_TSP: return dispatch_rows<RL4CO_ENV_TSP>(a, s);
-    case RL4CO_ENV_CVRP: return dispatch_rows<RL4CO_ENV_CVRP>(a, s);
-    case RL4CO_ENV_OP: return dispatch_rows<RL4CO_ENV_OP>(a, s);
-    case RL4CO_ENV_PCTSP: return dispatch_rows<RL4CO_ENV_PCTSP>(a, s);
-    case RL4CO_ENV_PDP: return dispatch_rows<RL4CO_ENV_PDP>(a, s);
-    default: return dispatch_rows<RL4CO_ENV_CVRPTW>(a, s);
-  }
+  return rl4co::dispatch_env<&rl4co::EnvRecord::teacher>(a.env, [&](auto e) { return dispatch_rows<decltype(e)::value>(a, s); });
 }

@@ -33,6 +33,7 @@
 
 #include "common.h"
 #include "elem16.h"
+#include "env_table.h"
 
 namespace {
 
@@ -1079,11 +1080,7 @@ static int dispatch_tiles(const rl4co_am_teacher_args& a, hipStream_t stream) {
 }
 
 int RL4CO_CXX(launch_teacher_mma)(const rl4co_am_teacher_args& a, hipStream_t stream) {
-  if (a.env == RL4CO_ENV_OP) return dispatch_tiles<RL4CO_ENV_OP>(a, stream);
-  if (a.env == RL4CO_ENV_PCTSP) return dispatch_tiles<RL4CO_ENV_PCTSP>(a, stream);
-  if (a.env == RL4CO_ENV_PDP) return dispatch_tiles<RL4CO_ENV_PDP>(a, stream);
-  if (a.env == RL4CO_ENV_CVRPTW) return dispatch_tiles<RL4CO_ENV_CVRPTW>(a, stream);
-  return a.env == RL4CO_ENV_TSP ? dispatch_tiles<RL4CO_ENV_TSP>(a, stream) : dispatch_tiles<RL4CO_ENV_CVRP>(a, stream);
+  return dispatch_env<&EnvRecord::teacher>(a.env, [&](auto e) { return dispatch_tiles<decltype(e)::value>(a, stream); });
 }
 
 }  // namespace rl4co
