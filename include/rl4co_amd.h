@@ -43,8 +43,10 @@ extern "C" {
  *  15: rl4co_am_decode_args carries the multi-agent TSP's folded context table and agent counts (mtsp_ctx, num_agents,
  *      behind err); rl4co_mtsp_step.
  *  16: rl4co_am_decode_beam / rl4co_am_decode_beam_max_width (beam search, rl4co_am_decode_beam_args);
- *      RL4CO_EBIT_BEAM_INFEASIBLE. */
-#define RL4CO_ABI_VERSION 16
+ *      RL4CO_EBIT_BEAM_INFEASIBLE.
+ *  17: rl4co_tsp_two_opt / rl4co_tsp_two_opt_lds_nodes (TSP local search, rl4co_tsp_two_opt_args);
+ *      RL4CO_EBIT_TOUR_INDEX. */
+#define RL4CO_ABI_VERSION 17
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -71,6 +73,7 @@ extern "C" {
 #define RL4CO_EBIT_TW_EMPTY 32768      /* cvrptw/env.py:159-161 "there are unfeasible time windows"    */
 #define RL4CO_EBIT_TW_DEADLINE 65536   /* cvrptw/env.py:176-179 "vehicle cannot start service before deadline" */
 #define RL4CO_EBIT_BEAM_INFEASIBLE 131072 /* utils/decoding.py:485 "infeasible action selected": beam search kept a -inf candidate (fewer than beam_width finite ones) */
+#define RL4CO_EBIT_TOUR_INDEX 262144 /* rl4co_tsp_two_opt: a tour holds a node index outside [0, N) (the reference would index its distance matrix out of bounds); that tour is returned unchanged */
 
 /* ---- enums --------------------------------------------------------------- */
 #define RL4CO_ENV_TSP 0
@@ -544,6 +547,38 @@ int rl4co_am_decode_beam(const rl4co_am_decode_beam_args* args, void* stream);
 /* Largest beam_width rl4co_am_decode_beam serves for N nodes (the kernel's LDS budget, am_decode_beam.hip header); 0 if N
  * itself is out of range. */
 int rl4co_am_decode_beam_max_width(int N);
+
+/* --------------------------------------------------------------------------
+ * TSP local search: best-improvement 2-opt (envs/routing/tsp/local_search.py:16-81) as ONE launch, one workgroup per
+ * tour (tsp_two_opt.hip). Per iteration every pair of positions 1 <= i < j <= T-1 is scored,
+ *   change = ((d[prev][tour[j]] + d[tour[i]][next]) - d[prev][tour[i]]) - d[tour[j]][next],
+ *   prev = tour[i-1], next = tour[(j+1) % T], pairs with prev == tour[j] or next == tour[i] skipped,
+ * in fp32 with one rounding per operation; the smallest change wins, EQUAL CHANGES GO TO THE LOWEST (i, j) (the
+ * reference's sequential scan keeps the first); if it is below -1e-6 (compared in double) tour[i..j] is reversed and the
+ * search goes on, otherwise it ends. `iterations` counts the final, non-improving scan too; max_iterations = 0 returns
+ * the input. The result equals the reference's bit for bit.
+ * d is `distances` with 1e9 added on its diagonal, or from `locs`: d[a][b] = sqrtf(fmaf(dy, dy, dx * dx)) (ATen's
+ * norm(p=2) over two elements), d[a][a] = 1e9. Exactly one of the two is given. Up to rl4co_tsp_two_opt_lds_nodes() nodes
+ * the matrix is kept in LDS; above, up to 1024, distances are computed from coordinates in LDS or read from global memory.
+ * A tour with an index outside [0, N) sets RL4CO_EBIT_TOUR_INDEX and is copied through unchanged (0 iterations).
+ * out_actions == actions (in place) is allowed.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_tsp_two_opt_args {
+  int32_t B;                /* tours (= workgroups), >= 1; instance b serves tour b        */
+  int32_t N;                /* nodes, 2 .. 1024                                            */
+  int32_t T;                /* tour length, 1 .. 1024                                      */
+  int32_t max_iterations;   /* >= 0                                                        */
+  const float* locs;        /* [B,N,2] or NULL                                             */
+  const float* distances;   /* [B,N,N] or NULL (may be asymmetric)                         */
+  const int64_t* actions;   /* [B,T]                                                       */
+  int64_t* out_actions;     /* [B,T]                                                       */
+  int32_t* iterations;      /* [B] or NULL: scans run per tour                             */
+  int32_t* err;             /* sticky error bits                                           */
+} rl4co_tsp_two_opt_args;
+
+int rl4co_tsp_two_opt(const rl4co_tsp_two_opt_args* args, void* stream);
+/* Largest N whose distance matrix rl4co_tsp_two_opt keeps in LDS (the kernel's LDS budget, tsp_two_opt.hip header). */
+int rl4co_tsp_two_opt_lds_nodes(void);
 
 /* --------------------------------------------------------------------------
  * a11-a13  fused encoder + decoder-cache fold on the matrix cores (inference rollouts).

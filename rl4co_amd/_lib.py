@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 16  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 17  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -32,6 +32,7 @@ EBIT_DEPOT_MIDDLE = 1024
 EBIT_NO_PICKUP = 2048
 EBIT_TW_NEGATIVE, EBIT_TW_RETURN, EBIT_TW_DURATION, EBIT_TW_EMPTY, EBIT_TW_DEADLINE = 4096, 8192, 16384, 32768, 65536
 EBIT_BEAM_INFEASIBLE = 131072
+EBIT_TOUR_INDEX = 262144
 
 # Reference assertion messages (file:line in the reference checkout) per sticky bit.
 ERROR_MESSAGES = {
@@ -53,6 +54,7 @@ ERROR_MESSAGES = {
     EBIT_TW_EMPTY: "there are unfeasible time windows",  # cvrptw/env.py:159-161
     EBIT_TW_DEADLINE: "vehicle cannot start service before deadline",  # cvrptw/env.py:176-179
     EBIT_BEAM_INFEASIBLE: "infeasible action selected",  # utils/decoding.py:485 (beam search kept a -inf candidate)
+    EBIT_TOUR_INDEX: "tour index out of range",  # rl4co_tsp_two_opt: an index outside [0, N) (no reference message)
 }
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -103,6 +105,15 @@ class AmDecodeBeamArgs(C.Structure):
         ("out_stride", _i32), ("reserved0", _i32),
         ("actions", _vp), ("logps", _vp), ("step_nodes", _vp), ("step_logps", _vp), ("parents", _vp), ("cum_logp", _vp),
         ("steps_summary", _vp), ("err", _vp),
+    ]
+
+
+class TspTwoOptArgs(C.Structure):
+    """Mirror of ``struct rl4co_tsp_two_opt_args`` (field order and types must match the header)."""
+
+    _fields_ = [
+        ("B", _i32), ("N", _i32), ("T", _i32), ("max_iterations", _i32),
+        ("locs", _vp), ("distances", _vp), ("actions", _vp), ("out_actions", _vp), ("iterations", _vp), ("err", _vp),
     ]
 
 
@@ -204,6 +215,8 @@ SYMBOLS = {
     "rl4co_am_decode_variant": (C.c_int, [C.POINTER(AmDecodeArgs)]),
     "rl4co_am_decode_beam": (C.c_int, [C.POINTER(AmDecodeBeamArgs), _vp]),
     "rl4co_am_decode_beam_max_width": (C.c_int, [C.c_int]),
+    "rl4co_tsp_two_opt": (C.c_int, [C.POINTER(TspTwoOptArgs), _vp]),
+    "rl4co_tsp_two_opt_lds_nodes": (C.c_int, []),
     "rl4co_select_start_nodes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "rl4co_augment_dihedral8_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_augment_symmetric_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp]),

@@ -13,7 +13,9 @@ Differences a caller can observe, both deliberate:
   * validity asserts are evaluated on the device and raised once, by ``get_reward``, with the
     reference's messages, instead of synchronising the host every step.
 ``dataset`` / ``load_data`` (base.py:234-286) serve npz instance files straight to the device (rl4co_amd/data.py).
-Out of scope (not on the rollout path): rendering, local search, torchrl specs.
+``local_search`` (base.py:228-232) is TSP's best-improvement 2-opt (``rl4co_tsp_two_opt``); the other environments raise
+``NotImplementedError`` as the reference's base does.
+Out of scope (not on the rollout path): rendering, torchrl specs.
 """
 from __future__ import annotations
 
@@ -362,6 +364,10 @@ class RL4COEnvBase:
     def check_solution_validity(self, td, actions) -> None:
         raise NotImplementedError
 
+    # -- RL4COEnvBase.local_search (base.py:228-232) ----------------------------------------------
+    def local_search(self, td: TensorDict, actions: Tensor, **kwargs) -> Tensor:
+        raise NotImplementedError(f"Local is not implemented yet for {self.name} environment")
+
 
 class TSPEnv(RL4COEnvBase):
     name = "tsp"
@@ -409,6 +415,23 @@ class TSPEnv(RL4COEnvBase):
         K.tsp_check_solution(actions.contiguous(), td["locs"].shape[-2], err)
         if own:
             K.raise_if_error(err)
+
+    @staticmethod
+    def local_search(td: TensorDict, actions: Tensor, max_iterations: int = 1000, num_threads: int | None = None) -> Tensor:
+        """tsp/env.py:183-188, tsp/local_search.py:16-43: best-improvement 2-opt on every tour, run until no move is
+        better than -1e-6 or ``max_iterations`` scans, by rl4co_tsp_two_opt (one workgroup per tour, the reference's
+        result bit for bit; equal improvements go to the lowest position pair). ``td["distances"]`` [B, N, N] is used
+        when present, else ``td["locs"]``; up to 1024 nodes. ``num_threads`` (the reference's numba pool) is ignored."""
+        distances = td.get("distances", None) if hasattr(td, "get") else None
+        source = td["locs"] if distances is None else distances
+        if not (actions.is_cuda and source.is_cuda):
+            raise NotImplementedError("TSP local search runs inside the MI355X 2-opt kernel (rl4co_tsp_two_opt) only: "
+                                      f"actions on {actions.device}, instance data on {source.device}")
+        source = source.detach().to(device=actions.device, dtype=torch.float32)
+        acts = actions.detach().to(torch.int64)
+        if distances is None:
+            return K.tsp_two_opt(acts, locs=source, max_iterations=max_iterations)
+        return K.tsp_two_opt(acts, distances=source, max_iterations=max_iterations)
 
 
 class CVRPEnv(RL4COEnvBase):

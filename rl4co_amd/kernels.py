@@ -499,6 +499,59 @@ def am_decode_beam(
     _lib.check(st, "rl4co_am_decode_beam")
 
 
+def two_opt_lds_nodes() -> int:
+    """Largest node count whose distance matrix the 2-opt kernel keeps in LDS (its LDS budget; a host query)."""
+    return int(_lib.lib().rl4co_tsp_two_opt_lds_nodes())
+
+
+def tsp_two_opt(actions: Tensor, *, locs: Tensor | None = None, distances: Tensor | None = None,
+                max_iterations: int = 1000, err: Tensor | None = None, return_iterations: bool = False,
+                out: Tensor | None = None):
+    """Best-improvement 2-opt on every tour of ``actions`` [B, T] (tsp/local_search.py:16-81) in one launch
+    (rl4co_tsp_two_opt), bit for bit the reference's result; equal improvements go to the lowest ``(i, j)``.
+
+    Exactly one of ``locs`` [B, N, 2] and ``distances`` [B, N, N] (fp32; the matrix may be asymmetric), N and T up to
+    1024. Returns the new int64 tours, and the int32 scan counts [B] with ``return_iterations``. ``out``: where the tours
+    go (``out is actions``: in place). With ``err`` the sticky bits are OR-ed into the caller's word and nothing is
+    synchronised; without it the word is read back and an out-of-range index raises."""
+    if (locs is None) == (distances is None):
+        raise ValueError("tsp_two_opt takes exactly one of locs and distances")
+    if actions.dim() != 2:
+        raise ValueError(f"actions must be [B, T], got {tuple(actions.shape)}")
+    if actions.dtype != torch.int64:
+        raise TypeError(f"actions must be torch.int64, got {actions.dtype}")
+    b, t = actions.shape
+    src = locs if distances is None else distances
+    if src.dtype != torch.float32:
+        raise TypeError(f"{'locs' if distances is None else 'distances'} must be torch.float32, got {src.dtype}")
+    n = src.shape[1] if src.dim() == 3 else -1
+    if src.dim() != 3 or src.shape[0] != b or (src.shape[2] != 2 if distances is None else src.shape[2] != n):
+        raise ValueError(f"{'locs must be [B, N, 2]' if distances is None else 'distances must be [B, N, N]'} with B = {b}, "
+                         f"got {tuple(src.shape)}")
+    if not 2 <= n <= 1024 or not 1 <= t <= 1024:
+        raise NotImplementedError(f"tsp_two_opt serves 2..1024 nodes and tours of 1..1024 positions, got N = {n}, T = {t}")
+    if int(max_iterations) < 0:
+        raise ValueError("max_iterations must be >= 0")
+    actions = _dev(actions.contiguous(), torch.int64, "actions")
+    src = _dev(src.contiguous(), torch.float32, "locs" if distances is None else "distances")
+    if out is None:
+        out = torch.empty_like(actions)
+    elif _dev(out, torch.int64, "out").shape != actions.shape:
+        raise ValueError(f"out must be {tuple(actions.shape)}, got {tuple(out.shape)}")
+    own = err is None
+    err = new_error_word(actions.device) if own else _dev(err, torch.int32, "err")
+    iters = torch.empty(b, dtype=torch.int32, device=actions.device) if return_iterations else None
+    a = _lib.TspTwoOptArgs()
+    a.B, a.N, a.T, a.max_iterations = b, n, t, int(max_iterations)
+    a.locs, a.distances = (_ptr(src), None) if distances is None else (None, _ptr(src))
+    a.actions, a.out_actions, a.iterations, a.err = _ptr(actions), _ptr(out), _ptr(iters), _ptr(err)
+    st = _lib.lib().rl4co_tsp_two_opt(C.byref(a), _stream())
+    _lib.check(st, "rl4co_tsp_two_opt")
+    if own:
+        raise_if_error(err)
+    return (out, iters) if return_iterations else out
+
+
 def decoding_filter(top_k, top_p, n: int) -> tuple[int, float]:
     """The top-k / top-p arguments of utils/decoding.py:109-188 as the kernel takes them: ``top_k <= 0`` is off and is
     clamped to ``n`` (k >= n removes nothing: 0); ``top_p <= 0`` or ``>= 1`` is off (0.0); ``top_p > 1`` raises the
