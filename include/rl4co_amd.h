@@ -45,8 +45,9 @@ extern "C" {
  *  16: rl4co_am_decode_beam / rl4co_am_decode_beam_max_width (beam search, rl4co_am_decode_beam_args);
  *      RL4CO_EBIT_BEAM_INFEASIBLE.
  *  17: rl4co_tsp_two_opt / rl4co_tsp_two_opt_lds_nodes (TSP local search, rl4co_tsp_two_opt_args);
- *      RL4CO_EBIT_TOUR_INDEX. */
-#define RL4CO_ABI_VERSION 17
+ *      RL4CO_EBIT_TOUR_INDEX.
+ *  18: rl4co_aco_tsp / rl4co_aco_tsp_lds_nodes (Ant System search on a heatmap, rl4co_aco_tsp_args, RL4CO_ACO_*). */
+#define RL4CO_ABI_VERSION 18
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -579,6 +580,74 @@ typedef struct rl4co_tsp_two_opt_args {
 int rl4co_tsp_two_opt(const rl4co_tsp_two_opt_args* args, void* stream);
 /* Largest N whose distance matrix rl4co_tsp_two_opt keeps in LDS (the kernel's LDS budget, tsp_two_opt.hip header). */
 int rl4co_tsp_two_opt_lds_nodes(void);
+
+/* --------------------------------------------------------------------------
+ * Ant System search on a heatmap for TSP (models/zoo/deepaco/antsystem.py, DeepACO's test-time loop) as ONE launch, one
+ * workgroup per instance (aco_tsp.hip). Rows are ant-major: row j * B + b is ant j of instance b, rows = n_ants * B.
+ * An iteration is
+ *   SAMPLE  L = alpha * log(pheromone) + beta * log_heuristic (two multiplies and an add, each rounded once); every ant
+ *           starts at start_nodes[it][row] (column 0 of `actions`, log-prob 0) and takes N - 1 steps: log-softmax of row
+ *           `cur` of L over the unvisited nodes (divided by `temperature` first), then the argmax over them of
+ *           lp[n] - ln_noise[n], the lowest node on equal keys. ln_noise is the caller's (parity mode: the natural log of
+ *           Exp(1) draws) or drawn in the kernel from Philox (step counter philox_offset + it * N + t, trajectory = row).
+ *           With forced_actions the given tours are followed and only their log-probs are computed. The reward, minus the
+ *           closed tour length from `locs`, is bit-equal to rl4co_tour_length_f32's.
+ *   UPDATE  the reference's _update_results, _reward_map and _update_pheromone bit for bit: M, m = max, min reward of the
+ *           instance's ants; the lowest ant with reward M is the iteration's best and replaces final_reward /
+ *           final_actions when has_best == 0 (first iteration) or final_reward <= M; v_j = ((r_j - m) / (M - m))^2 * Q
+ *           (NaN when M == m, as the reference); delta[a_t][a_t+1] += v_j for ants in ascending order over the N - 1
+ *           directed edges t = 0 .. N - 2 (no closing edge, nothing symmetric); delta[0][0] = 0;
+ *           pheromone = pheromone * decay + delta.
+ * phases = SAMPLE | UPDATE runs `iterations` whole iterations (locs required). One phase alone runs once (iterations == 1):
+ * SAMPLE writes actions / reward (reward only with locs), UPDATE reads them.
+ * Up to rl4co_aco_tsp_lds_nodes() nodes L and the pheromone live in LDS; above, up to 1024, `pheromone` is updated in place
+ * and L / delta use `logits_scratch`.
+ * Sticky bits: RL4CO_EBIT_NAN_LOGIT (a feasible logit is NaN), RL4CO_EBIT_NEG_INF_LOGP (chosen log-prob not above -1000),
+ * RL4CO_EBIT_INFEASIBLE (every feasible logit -inf: the lowest feasible node is taken; or a forced node already visited),
+ * RL4CO_EBIT_TOUR_INDEX (a start node, forced action or UPDATE-only input action outside [0, N): that instance is left
+ * untouched).
+ * -------------------------------------------------------------------------- */
+#define RL4CO_ACO_SAMPLE 1
+#define RL4CO_ACO_UPDATE 2
+
+typedef struct rl4co_aco_tsp_args {
+  int32_t B;                /* instances (= workgroups), >= 1                               */
+  int32_t N;                /* nodes, 2 .. 1024                                             */
+  int32_t n_ants;           /* >= 1; n_ants * B <= 2^31 - 1                                 */
+  int32_t iterations;       /* >= 1; 1 unless both phases are set                           */
+  int32_t phases;           /* RL4CO_ACO_SAMPLE | RL4CO_ACO_UPDATE                          */
+  int32_t has_best;         /* 0: final_reward / final_actions hold nothing yet             */
+  float alpha;
+  float beta;
+  float decay;
+  float Q;
+  float temperature;        /* > 0                                                          */
+  int32_t reserved0;        /* 0                                                            */
+  uint64_t philox_seed;     /* in-kernel noise when ln_noise == NULL                        */
+  uint64_t philox_offset;
+  const uint64_t* philox_seed_dev; /* optional device word XOR-ed into philox_seed          */
+  const float* log_heuristic;   /* [B,N,N] (SAMPLE)                                         */
+  float* pheromone;             /* [B,N,N] in / out                                         */
+  const float* locs;            /* [B,N,2]; NULL allowed for one phase alone (no reward)    */
+  const int64_t* start_nodes;   /* [iterations,rows] (SAMPLE)                               */
+  const float* ln_noise;        /* [iterations,N-1,rows,N] or NULL                          */
+  const int64_t* forced_actions;/* [rows,N] or NULL (SAMPLE, iterations == 1)               */
+  float* logits_scratch;        /* [B,N,N]; required above rl4co_aco_tsp_lds_nodes()        */
+  int64_t* actions;             /* [rows,N] last iteration's tours (UPDATE alone: input)    */
+  float* reward;                /* [rows] last iteration's rewards (UPDATE alone: input)    */
+  float* logps;                 /* [rows,N] or NULL                                         */
+  float* all_logps;             /* [rows,N,N] or NULL                                       */
+  int64_t* iter_actions;        /* [iterations,rows,N] or NULL                              */
+  float* iter_reward;           /* [iterations,rows] or NULL                                */
+  float* final_reward;          /* [B] in / out (UPDATE)                                    */
+  int64_t* final_actions;       /* [B,N] in / out (UPDATE)                                  */
+  float* final_reward_cache;    /* [iterations,B] or NULL                                   */
+  int32_t* err;                 /* sticky error bits                                        */
+} rl4co_aco_tsp_args;
+
+int rl4co_aco_tsp(const rl4co_aco_tsp_args* args, void* stream);
+/* Largest N at which rl4co_aco_tsp keeps the logits and the pheromone in LDS (the kernel's LDS budget, aco_tsp.hip header). */
+int rl4co_aco_tsp_lds_nodes(void);
 
 /* --------------------------------------------------------------------------
  * a11-a13  fused encoder + decoder-cache fold on the matrix cores (inference rollouts).

@@ -6,3 +6,13 @@ hand-written HIP kernels for gfx950 reached through a C-ABI (``include/rl4co_amd
 See DESIGN.md for the path, the boundary and what is out of scope.
 """
 __version__ = "0.1.0"
+
+__all__ = ["AntSystem"]
+
+
+def __getattr__(name):
+    if name == "AntSystem":  # rl4co_amd.aco: the reference's AntSystem on the rl4co_aco_tsp kernel (imported on first use)
+        from .aco import AntSystem
+
+        return AntSystem
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

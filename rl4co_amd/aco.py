@@ -1,0 +1,169 @@
+"""Ant System search on a heatmap: the reference's ``AntSystem`` (models/zoo/deepaco/antsystem.py), DeepACO's test-time
+loop, behind its own class surface with the loop inside ONE kernel launch (``rl4co_aco_tsp``, csrc/aco_tsp.hip).
+
+``run`` without local search is one launch for all iterations and one read-back of the error word. With
+``use_local_search`` every iteration is a SAMPLE launch, ``env.local_search`` (the 2-opt kernel, from ``td["locs"]``, on the
+device), ``env.get_reward`` and an UPDATE launch. The update (best tour, reward map, pheromone) is the reference's bit for
+bit; the sampled tours follow the kernel's own noise (Philox), so they are the reference's in distribution, not draw for
+draw. Served: TSP, ``multistart`` decoding with ``num_starts == n_ants``, ``select_start_nodes_fn``, ``temperature``.
+Refused (``NotImplementedError``): other environments, ``use_nls``, ``top_k`` / ``top_p`` / ``multisample`` and any other
+decoding keyword, CPU tensors."""
+from __future__ import annotations
+
+import torch
+from torch import Tensor
+
+from . import _lib
+from . import kernels as K
+
+_SERVED_KWARGS = ("multistart", "num_starts", "select_best", "select_start_nodes_fn", "temperature")
+
+
+class AntSystem:
+    """antsystem.py:15-76, attribute for attribute. ``Q`` defaults to ``1 / n_ants / decay``."""
+
+    def __init__(self, log_heuristic: Tensor, n_ants: int = 20, alpha: float = 1.0, beta: float = 1.0, decay: float = 0.95,
+                 Q: float | None = None, pheromone: Tensor | int | None = None, use_local_search: bool = False,
+                 use_nls: bool = False, n_perturbations: int = 1, local_search_params: dict = {},
+                 perturbation_params: dict = {}):
+        self.batch_size = log_heuristic.shape[0]
+        self.n_ants = n_ants
+        self.alpha = alpha
+        self.beta = beta
+        self.decay = decay
+        self.Q = 1 / self.n_ants / self.decay if Q is None else Q
+        self.log_heuristic = log_heuristic
+        if pheromone is None or isinstance(pheromone, int):
+            self.pheromone = torch.ones_like(log_heuristic)
+            self.pheromone.fill_(pheromone if isinstance(pheromone, int) else 1)
+        else:
+            assert pheromone.shape == log_heuristic.shape
+            self.pheromone = pheromone
+        self.final_actions = self.final_reward = None
+        self.final_reward_cache: dict = {}
+        self.use_local_search = use_local_search
+        assert not (use_nls and not use_local_search), "use_nls requires use_local_search"
+        if use_nls:
+            raise NotImplementedError("use_nls (neural-guided perturbation) is not served by the Ant System kernel")
+        self.use_nls = use_nls
+        self.n_perturbations = n_perturbations
+        self.local_search_params = local_search_params.copy()
+        self.perturbation_params = perturbation_params.copy()
+        self.last_iterations: dict | None = None  # tests only: per-iteration actions / rewards of the last run
+
+    # ---- what the kernel takes ---------------------------------------------------------------------------------------
+    def _check(self, td, env, decoding_kwargs: dict) -> float:
+        if getattr(env, "name", None) != "tsp":
+            raise NotImplementedError(f"AntSystem serves the tsp environment only (rl4co_aco_tsp), got "
+                                      f"{getattr(env, 'name', env)!r}")
+        for key in decoding_kwargs:
+            if key not in _SERVED_KWARGS:
+                raise NotImplementedError(f"decoding_kwargs[{key!r}] is not served by the Ant System kernel")
+        if not decoding_kwargs.get("multistart", False):
+            raise NotImplementedError("decoding_kwargs['multistart'] must be True: every ant starts from a given node")
+        if decoding_kwargs.get("num_starts", self.n_ants) != self.n_ants:
+            raise NotImplementedError(f"decoding_kwargs['num_starts'] must equal n_ants = {self.n_ants}")
+        if decoding_kwargs.get("select_best", False):
+            raise NotImplementedError("decoding_kwargs['select_best'] must be False: the update needs every ant's tour")
+        for name, t in (("log_heuristic", self.log_heuristic), ("pheromone", self.pheromone), ("td['locs']", td["locs"])):
+            if not t.is_cuda:
+                raise NotImplementedError(f"AntSystem runs inside the MI355X kernel (rl4co_aco_tsp) only: {name} on {t.device}")
+        return float(decoding_kwargs.get("temperature", 1.0))
+
+    def _tensors(self, td):
+        dev = self.log_heuristic.device
+        heu = self.log_heuristic.detach().to(torch.float32).contiguous()
+        if self.pheromone.dtype != torch.float32 or not self.pheromone.is_contiguous():
+            self.pheromone = self.pheromone.detach().to(torch.float32).contiguous()
+        return heu, td["locs"].detach().to(device=dev, dtype=torch.float32).contiguous()
+
+    def _start_nodes(self, td, env, decoding_kwargs: dict) -> Tensor:
+        """Sampling.pre_decoder_hook (decoding.py:304-311): called once per iteration."""
+        fn = decoding_kwargs.get("select_start_nodes_fn", None)
+        nodes = fn(td, env, self.n_ants) if fn is not None else env.select_start_nodes(td, num_starts=self.n_ants)
+        return nodes.to(device=self.log_heuristic.device, dtype=torch.int64).reshape(-1)
+
+    def _next_seed(self) -> tuple[int, int]:
+        """The Philox key of one launch: drawn from torch's (CPU) generator, so ``torch.manual_seed`` reproduces a run."""
+        return int(torch.randint(0, 2**62, (1,)).item()), 0
+
+    def _common(self, temperature: float) -> dict:
+        return dict(n_ants=self.n_ants, alpha=float(self.alpha), beta=float(self.beta), decay=float(self.decay),
+                    Q=float(self.Q), temperature=temperature)
+
+    def _record(self):
+        has = self.final_reward is not None
+        return dict(has_best=has, final_reward=self.final_reward if has else None,
+                    final_actions=torch.stack(self.final_actions, 0).contiguous() if has else None)
+
+    def _take_record(self, out: dict) -> None:
+        self.final_reward = out["final_reward"]
+        self.final_actions = list(out["final_actions"].unbind(0))
+
+    # ---- AntSystem.run (antsystem.py:87-118) -----------------------------------------------------------------------------
+    def run(self, td_initial, env, n_iterations: int, decoding_kwargs: dict, disable_tqdm: bool = True):
+        temperature = self._check(td_initial, env, decoding_kwargs)
+        if self.use_local_search:
+            acts, rews, sampled = [], [], []
+            for i in range(n_iterations):
+                a, r = self._one_step(td_initial, env, decoding_kwargs)
+                acts.append(a)
+                rews.append(r)
+                sampled.append(self._sampled_reward)
+                self.final_reward_cache[i] = self.final_reward.clone()
+            self.last_iterations = {"actions": torch.stack(acts, 0), "reward": torch.stack(rews, 0),
+                                    "sampled_reward": torch.stack(sampled, 0)}
+            return self._convert_final_action_to_matrix(), self.final_reward_cache
+        heu, locs = self._tensors(td_initial)
+        starts = torch.stack([self._start_nodes(td_initial, env, decoding_kwargs) for _ in range(n_iterations)], 0)
+        seed, offset = self._next_seed()
+        err = K.new_error_word(heu.device)
+        out = K.aco_tsp(self.pheromone, iterations=n_iterations, log_heuristic=heu, locs=locs, start_nodes=starts.contiguous(),
+                        philox_seed=seed, philox_offset=offset, record_iterations=True, err=err, **self._record(),
+                        **self._common(temperature))
+        _lib.raise_for_error_bits(int(err.item()))  # the one read-back of the run
+        self._take_record(out)
+        for i in range(n_iterations):
+            self.final_reward_cache[i] = out["final_reward_cache"][i].clone()
+        self.last_iterations = {"actions": out["iter_actions"], "reward": out["iter_reward"]}
+        return self._convert_final_action_to_matrix(), self.final_reward_cache
+
+    # ---- AntSystem._one_step (antsystem.py:120-147) ----------------------------------------------------------------------
+    def _one_step(self, td, env, decoding_kwargs: dict):
+        """One iteration: sample, optional local search, update. Returns (actions [rows, N], reward [rows]), ant-major."""
+        temperature = self._check(td, env, decoding_kwargs)
+        heu, locs = self._tensors(td)
+        starts = self._start_nodes(td, env, decoding_kwargs)[None].contiguous()
+        seed, offset = self._next_seed()
+        err = K.new_error_word(heu.device)
+        common = self._common(temperature)
+        if not self.use_local_search:
+            out = K.aco_tsp(self.pheromone, log_heuristic=heu, locs=locs, start_nodes=starts, philox_seed=seed,
+                            philox_offset=offset, err=err, **self._record(), **common)
+            actions, reward = out["actions"], out["reward"]
+        else:
+            sampled = K.aco_tsp(self.pheromone, phases=_lib.ACO_SAMPLE, log_heuristic=heu, locs=locs, start_nodes=starts,
+                                philox_seed=seed, philox_offset=offset, err=err, **common)
+            self._sampled_reward = sampled["reward"]  # (tests: the local search never makes a tour longer)
+            actions, reward = self.local_search(td, env, sampled["actions"], decoding_kwargs)
+            out = K.aco_tsp(self.pheromone, phases=_lib.ACO_UPDATE, actions=actions.contiguous(),
+                            reward=reward.to(torch.float32).contiguous(), err=err, **self._record(), **common)
+        _lib.raise_for_error_bits(int(err.item()))
+        self._take_record(out)
+        return actions, reward
+
+    # ---- AntSystem.local_search (antsystem.py:173-230), without the host round trip --------------------------------------
+    def local_search(self, td, env, actions: Tensor, decoding_kwargs: dict):
+        if getattr(env, "name", None) != "tsp":
+            raise NotImplementedError(f"Local search not implemented for {getattr(env, 'name', env)}")
+        locs = td["locs"]
+        rows = actions.shape[0]
+        # one instance row per ant row (ant-major, the reference's batchify): the 2-opt kernel pairs tour r with instance r
+        tiled = {"locs": locs.repeat(rows // locs.shape[0], 1, 1)} if locs.shape[0] != rows else {"locs": locs}
+        best_actions = env.local_search(td=tiled, actions=actions, **self.local_search_params)
+        best_rewards = env.get_reward(tiled, best_actions)
+        return best_actions, best_rewards
+
+    def _convert_final_action_to_matrix(self) -> Tensor:
+        assert self.final_actions is not None
+        return torch.stack(self.final_actions, 0)

@@ -552,6 +552,103 @@ def tsp_two_opt(actions: Tensor, *, locs: Tensor | None = None, distances: Tenso
     return (out, iters) if return_iterations else out
 
 
+def aco_lds_nodes() -> int:
+    """Largest node count at which the Ant System kernel keeps logits and pheromone in LDS (a host query)."""
+    return int(_lib.lib().rl4co_aco_tsp_lds_nodes())
+
+
+def aco_tsp(pheromone: Tensor, *, n_ants: int, phases: int = _lib.ACO_SAMPLE | _lib.ACO_UPDATE, iterations: int = 1,
+            log_heuristic: Tensor | None = None, locs: Tensor | None = None, start_nodes: Tensor | None = None,
+            alpha: float = 1.0, beta: float = 1.0, decay: float = 0.95, Q: float = 1.0, temperature: float = 1.0,
+            ln_noise: Tensor | None = None, philox_seed: int = 0, philox_offset: int = 0,
+            philox_seed_dev: Tensor | None = None, forced_actions: Tensor | None = None, actions: Tensor | None = None,
+            reward: Tensor | None = None, final_reward: Tensor | None = None, final_actions: Tensor | None = None,
+            has_best: bool = False, all_logps: bool = False, record_iterations: bool = False,
+            err: Tensor | None = None) -> dict:
+    """Ant System iterations on ``pheromone`` [B, N, N] (fp32, updated IN PLACE) in one launch (rl4co_aco_tsp; the header
+    states the arithmetic). Rows are ant-major: row ``j * B + b`` is ant ``j`` of instance ``b``.
+
+    ``phases``: SAMPLE | UPDATE runs ``iterations`` whole iterations; SAMPLE alone samples (or, with ``forced_actions``
+    [rows, N], evaluates) once; UPDATE alone takes ``actions`` [rows, N] and ``reward`` [rows] and updates once.
+    ``start_nodes`` int64 [iterations, rows]; ``ln_noise`` fp32 [iterations, N - 1, rows, N] (parity mode) or None for
+    the in-kernel Philox. ``final_reward`` [B] / ``final_actions`` [B, N] are updated in place when given
+    (``has_best``: they hold a record already), else created. Returns a dict of the tensors the launch wrote:
+    actions, reward, logps, final_reward, final_actions, final_reward_cache [iterations, B] and, on request, all_logps
+    [rows, N, N], iter_actions [iterations, rows, N], iter_reward [iterations, rows]. With ``err`` the sticky bits are
+    OR-ed into the caller's word and nothing is synchronised; without it the word is read back and a set bit raises."""
+    pheromone = _dev(pheromone, torch.float32, "pheromone")
+    if pheromone.dim() != 3 or pheromone.shape[1] != pheromone.shape[2]:
+        raise ValueError(f"pheromone must be [B, N, N], got {tuple(pheromone.shape)}")
+    b, n, _ = pheromone.shape
+    if not 2 <= n <= 1024:
+        raise NotImplementedError(f"aco_tsp serves 2..1024 nodes, got N = {n}")
+    n_ants, iterations = int(n_ants), int(iterations)
+    rows = n_ants * b
+    dev = pheromone.device
+    sample, update = bool(phases & _lib.ACO_SAMPLE), bool(phases & _lib.ACO_UPDATE)
+
+    def shaped(t, dtype, shape, name):
+        if t is None:
+            return None
+        t = _dev(t, dtype, name)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    log_heuristic = shaped(log_heuristic, torch.float32, (b, n, n), "log_heuristic")
+    locs = shaped(locs, torch.float32, (b, n, 2), "locs")
+    start_nodes = shaped(start_nodes, torch.int64, (iterations, rows), "start_nodes")
+    ln_noise = shaped(ln_noise, torch.float32, (iterations, n - 1, rows, n), "ln_noise")
+    forced_actions = shaped(forced_actions, torch.int64, (rows, n), "forced_actions")
+    if sample:
+        if actions is not None or reward is not None:
+            raise ValueError("actions / reward are outputs of the SAMPLE phase")
+        actions = torch.empty((rows, n), dtype=torch.int64, device=dev)
+        reward = torch.zeros(rows, dtype=torch.float32, device=dev)
+    elif actions is None or reward is None:
+        raise ValueError("the UPDATE phase alone takes actions [rows, N] and reward [rows]")
+    actions = shaped(actions, torch.int64, (rows, n), "actions")
+    reward = shaped(reward, torch.float32, (rows,), "reward")
+    out = {"actions": actions, "reward": reward}
+    if sample:
+        out["logps"] = torch.empty((rows, n), dtype=torch.float32, device=dev)
+        if all_logps:
+            out["all_logps"] = torch.empty((rows, n, n), dtype=torch.float32, device=dev)
+        if record_iterations:
+            out["iter_actions"] = torch.empty((iterations, rows, n), dtype=torch.int64, device=dev)
+            out["iter_reward"] = torch.zeros((iterations, rows), dtype=torch.float32, device=dev)
+    if update:
+        if (final_reward is None) != (final_actions is None):
+            raise ValueError("final_reward and final_actions come together")
+        if final_reward is None:
+            if has_best:
+                raise ValueError("has_best needs final_reward and final_actions")
+            final_reward = torch.zeros(b, dtype=torch.float32, device=dev)
+            final_actions = torch.zeros((b, n), dtype=torch.int64, device=dev)
+        out["final_reward"] = shaped(final_reward, torch.float32, (b,), "final_reward")
+        out["final_actions"] = shaped(final_actions, torch.int64, (b, n), "final_actions")
+        out["final_reward_cache"] = torch.zeros((iterations, b), dtype=torch.float32, device=dev)
+    scratch = torch.empty((b, n, n), dtype=torch.float32, device=dev) if n > aco_lds_nodes() else None
+    own = err is None
+    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
+    a = _lib.AcoTspArgs()
+    a.B, a.N, a.n_ants, a.iterations, a.phases, a.has_best = b, n, n_ants, iterations, int(phases), int(bool(has_best))
+    a.alpha, a.beta, a.decay, a.Q, a.temperature, a.reserved0 = alpha, beta, decay, Q, temperature, 0
+    a.philox_seed, a.philox_offset = int(philox_seed) & (2**64 - 1), int(philox_offset) & (2**64 - 1)
+    a.philox_seed_dev = _ptr(philox_seed_dev)
+    a.log_heuristic, a.pheromone, a.locs, a.start_nodes = _ptr(log_heuristic), _ptr(pheromone), _ptr(locs), _ptr(start_nodes)
+    a.ln_noise, a.forced_actions, a.logits_scratch = _ptr(ln_noise), _ptr(forced_actions), _ptr(scratch)
+    a.actions, a.reward, a.logps, a.all_logps = _ptr(actions), _ptr(reward), _ptr(out.get("logps")), _ptr(out.get("all_logps"))
+    a.iter_actions, a.iter_reward = _ptr(out.get("iter_actions")), _ptr(out.get("iter_reward"))
+    a.final_reward, a.final_actions = _ptr(out.get("final_reward")), _ptr(out.get("final_actions"))
+    a.final_reward_cache, a.err = _ptr(out.get("final_reward_cache")), _ptr(err)
+    st = _lib.lib().rl4co_aco_tsp(C.byref(a), _stream())
+    _lib.check(st, "rl4co_aco_tsp")
+    if own:
+        raise_if_error(err)
+    return out
+
+
 def decoding_filter(top_k, top_p, n: int) -> tuple[int, float]:
     """The top-k / top-p arguments of utils/decoding.py:109-188 as the kernel takes them: ``top_k <= 0`` is off and is
     clamped to ``n`` (k >= n removes nothing: 0); ``top_p <= 0`` or ``>= 1`` is off (0.0); ``top_p > 1`` raises the

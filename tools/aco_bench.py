@@ -1,0 +1,140 @@
+"""End-to-end time of the Ant System search (rl4co_amd.aco.AntSystem on csrc/aco_tsp.hip) at DeepACO's defaults: 4096 x
+TSP-100, 48 ants, 10 iterations, heuristic -log(distance). Three legs, alternating round by round after one warm-up round,
+each timed with HIP events around the whole ``run`` (host work included) and synchronised:
+  fused          one rl4co_aco_tsp launch for all iterations
+  local_search   per iteration: SAMPLE launch, the 2-opt kernel, the reward kernel, UPDATE launch
+  torch_per_step the same configuration composed per decoding step from torch ops on the GPU — this script's own plain
+                 restatement of the loop (one multinomial draw per step, a Python loop over the ants in the deposit), for
+                 scale only: it draws other tours than the kernel.
+Next to the times: the mean best tour length after the last iteration, in float64.
+
+    python tools/aco_bench.py [--reps 5] [--batch 4096] [--num-loc 100] [--out profiles/aco_bench.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from rl4co_amd import AntSystem  # noqa: E402
+from rl4co_amd.envs import get_env  # noqa: E402
+from rl4co_amd.tensordict import TensorDict  # noqa: E402
+
+
+def length64(locs, tours):
+    p = locs.double().gather(1, tours[..., None].expand(-1, -1, 2))
+    return (p - p.roll(-1, dims=1)).norm(dim=-1).sum(1)
+
+
+def torch_ant_system(heu, locs, n_ants, iterations, alpha=1.0, beta=1.0, decay=0.95):
+    """The Ant System loop from torch ops, one decoding step at a time (ant-major rows)."""
+    b, n, _ = heu.shape
+    rows = n_ants * b
+    q = 1 / n_ants / decay
+    dev = heu.device
+    ar, inst = torch.arange(rows, device=dev), torch.arange(rows, device=dev) % b
+    bidx = torch.arange(b, device=dev)
+    phe = torch.ones_like(heu)
+    best_reward = best_actions = None
+    for _ in range(iterations):
+        logits = alpha * torch.log(phe) + beta * heu
+        cur = (ar // b) % n
+        mask = torch.ones(rows, n, dtype=torch.bool, device=dev)
+        mask[ar, cur] = False
+        steps = [cur]
+        for _t in range(1, n):
+            lp = torch.log_softmax(logits[inst, cur].masked_fill(~mask, float("-inf")), -1)
+            cur = torch.multinomial(lp.exp(), 1).squeeze(1)
+            mask[ar, cur] = False
+            steps.append(cur)
+        actions = torch.stack(steps, 1)
+        pts = locs[inst[:, None], actions]
+        reward = -(pts.roll(-1, 1) - pts).norm(p=2, dim=-1).sum(1)
+        rew, act = reward.view(n_ants, b).t(), actions.view(n_ants, b, n)
+        top = rew.argmax(-1)
+        top_reward, top_actions = rew[bidx, top], act[top, bidx]
+        if best_reward is None:
+            best_reward, best_actions = top_reward.clone(), top_actions.clone()
+        else:
+            take = best_reward <= top_reward
+            best_reward = torch.where(take, top_reward, best_reward)
+            best_actions = torch.where(take[:, None], top_actions, best_actions)
+        hi, lo = rew.max(-1, keepdim=True).values, rew.min(-1, keepdim=True).values
+        v = ((rew - lo) / (hi - lo)) ** 2 * q
+        delta = torch.zeros_like(phe)
+        for j in range(n_ants):
+            delta[bidx[:, None], act[j, :, :-1], act[j, :, 1:]] += v[:, j : j + 1]
+        delta[:, 0, 0] = 0
+        phe = phe * decay + delta
+    return best_actions
+
+
+class Leg:
+    def __init__(self, kind, fn):
+        self.kind, self.fn, self.times, self.tours = kind, fn, [], None
+
+    def launch(self, keep: bool):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        self.tours = self.fn()
+        e1.record()
+        torch.cuda.synchronize()
+        if keep:
+            self.times.append(e0.elapsed_time(e1))
+
+    def result(self, locs):
+        t = sorted(self.times)
+        return dict(leg=self.kind, reps=len(t), median_ms=t[len(t) // 2], min_ms=t[0], max_ms=t[-1],
+                    mean_best_length_f64=float(length64(locs, self.tours).mean()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--num-loc", type=int, default=100)
+    ap.add_argument("--ants", type=int, default=48)
+    ap.add_argument("--iterations", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("aco_bench needs the MI355X: a time taken anywhere else says nothing")
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(1234)
+    locs = torch.rand(a.batch, a.num_loc, 2, generator=g).to(dev)
+    dist = (locs[:, :, None] - locs[:, None, :]).norm(p=2, dim=-1)
+    heu = -torch.log(dist + 1e9 * torch.eye(a.num_loc, device=dev))
+    env = get_env("tsp", generator_params=dict(num_loc=a.num_loc, device=dev), device=dev)
+    td = env.reset(TensorDict({"locs": locs}, batch_size=[a.batch]))
+    kwargs = dict(multistart=True, num_starts=a.ants, select_best=False)
+
+    def kernel_run(**kw):
+        def run():
+            torch.manual_seed(0)
+            return AntSystem(heu, n_ants=a.ants, **kw).run(td, env, a.iterations, kwargs)[0]
+
+        return run
+
+    legs = [Leg("fused", kernel_run()), Leg("local_search", kernel_run(use_local_search=True)),
+            Leg("torch_per_step", lambda: torch_ant_system(heu, locs, a.ants, a.iterations))]
+    for it in range(a.reps + 1):  # one warm-up round; the legs alternate inside every round
+        for leg in legs:
+            leg.launch(keep=it >= 1)
+    rows = [leg.result(locs) for leg in legs]
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), when=time.strftime("%Y-%m-%d"),
+                           case=f"tsp{a.num_loc}x{a.batch}, {a.ants} ants, {a.iterations} iterations",
+                           what="AntSystem.run end to end (host work included), HIP events around the call, synchronised",
+                           rows=rows), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
