@@ -46,8 +46,9 @@ extern "C" {
  *      RL4CO_EBIT_BEAM_INFEASIBLE.
  *  17: rl4co_tsp_two_opt / rl4co_tsp_two_opt_lds_nodes (TSP local search, rl4co_tsp_two_opt_args);
  *      RL4CO_EBIT_TOUR_INDEX.
- *  18: rl4co_aco_tsp / rl4co_aco_tsp_lds_nodes (Ant System search on a heatmap, rl4co_aco_tsp_args, RL4CO_ACO_*). */
-#define RL4CO_ABI_VERSION 18
+ *  18: rl4co_aco_tsp / rl4co_aco_tsp_lds_nodes (Ant System search on a heatmap, rl4co_aco_tsp_args, RL4CO_ACO_*).
+ *  19: rl4co_aco_cvrp / rl4co_aco_cvrp_lds_nodes (the same search for CVRP, rl4co_aco_cvrp_args). */
+#define RL4CO_ABI_VERSION 19
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -648,6 +649,78 @@ typedef struct rl4co_aco_tsp_args {
 int rl4co_aco_tsp(const rl4co_aco_tsp_args* args, void* stream);
 /* Largest N at which rl4co_aco_tsp keeps the logits and the pheromone in LDS (the kernel's LDS budget, aco_tsp.hip header). */
 int rl4co_aco_tsp_lds_nodes(void);
+
+/* --------------------------------------------------------------------------
+ * Ant System search on a heatmap for CVRP (the same reference class with CVRPEnv) as ONE launch, one workgroup per
+ * instance (aco_cvrp.hip). N is the heatmap side with the depot as node 0, C = N - 1 the customers, rows = n_ants * B
+ * ant-major as in rl4co_aco_tsp, and W = max(C + 1, 2 C - 1) the longest action row the reference can produce.
+ *   SAMPLE  L as in rl4co_aco_tsp. An ant carries CVRPEnv's state (cvrp/env.py:66-136) in fp32: used = (used +
+ *           demand[a - 1]) * (a != 0); customer c is infeasible when visited or demand[c - 1] + used >
+ *           vehicle_capacity + 1e-5f; the depot is infeasible when the ant stands on it and some customer is feasible;
+ *           the row is done when every customer has been visited and action 0 has been taken at least once. With
+ *           start_nodes == NULL (multisample) every ant starts at the depot and samples its first action from row 0 of L;
+ *           with start_nodes (multistart) column 0 of `actions` is the given customer with log-prob 0, stepped through the
+ *           state. A step is rl4co_aco_tsp's over the feasible nodes; ln_noise is [iterations, W, rows, N] (step t reads
+ *           [it][t][row]; t = 0 is unused in multistart mode), the Philox step counter is philox_offset + it * W + t.
+ *           An ant stops at done: lengths[row] counts its actions, the rest of the row is 0 (log-probs 0). A row not done
+ *           after W actions (a demand above the capacity) raises RL4CO_EBIT_INFEASIBLE and ends there.
+ *           REWARD WIDTH: the reward is minus the closed length of [depot, actions[0 .. W-1]] at the fixed width W,
+ *           bit-equal to rl4co_tour_length_f32 with prepend_depot on the W-wide zero-padded row. The reference trims a
+ *           batch to its longest row before it sums, which changes only the association of the sum (trailing depot
+ *           segments are exactly 0) and depends on the other instances; this kernel does not follow that.
+ *   UPDATE  rl4co_aco_tsp's over the whole padded row of width T (SAMPLE: T = W): edges (a_t, a_t+1), t = 0 .. T - 2, for
+ *           ants in ascending order, (0, 0) edges skipped (the reference zeroes delta[0][0] afterwards);
+ *           final_iteration[b] = iteration_base + it where iteration `it` replaced the record of instance b.
+ * phases, the one-phase-alone rule, the LDS tier (rl4co_aco_cvrp_lds_nodes(), logits_scratch above it) and the sticky bits
+ * are rl4co_aco_tsp's; RL4CO_EBIT_INFEASIBLE also covers a forced node that is infeasible and the row that is not done
+ * after W actions; RL4CO_EBIT_TOUR_INDEX covers a start node outside [1, N) and a forced / UPDATE-only action outside
+ * [0, N): that instance is left untouched.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_aco_cvrp_args {
+  int32_t B;                /* instances (= workgroups), >= 1                               */
+  int32_t N;                /* nodes with the depot, 2 .. 1024                              */
+  int32_t n_ants;           /* >= 1; n_ants * B <= 2^31 - 1                                 */
+  int32_t iterations;       /* >= 1; 1 unless both phases are set                           */
+  int32_t phases;           /* RL4CO_ACO_SAMPLE | RL4CO_ACO_UPDATE                          */
+  int32_t has_best;         /* 0: final_reward / final_actions hold nothing yet             */
+  int32_t T;                /* width of actions / final_actions: W with SAMPLE, else >= 2   */
+  int32_t iteration_base;   /* added to the iteration index written to final_iteration      */
+  float alpha;
+  float beta;
+  float decay;
+  float Q;
+  float temperature;        /* > 0                                                          */
+  int32_t reserved0;        /* 0                                                            */
+  uint64_t philox_seed;     /* in-kernel noise when ln_noise == NULL                        */
+  uint64_t philox_offset;
+  const uint64_t* philox_seed_dev; /* optional device word XOR-ed into philox_seed          */
+  const float* log_heuristic;   /* [B,N,N] (SAMPLE)                                         */
+  float* pheromone;             /* [B,N,N] in / out                                         */
+  const float* locs;            /* [B,N,2], depot first; NULL allowed for one phase alone   */
+  const float* demand;          /* [B,N-1] (SAMPLE)                                         */
+  const float* vehicle_capacity;/* [B] (SAMPLE)                                             */
+  const int64_t* start_nodes;   /* [iterations,rows] customers (multistart) or NULL         */
+  const float* ln_noise;        /* [iterations,W,rows,N] or NULL                            */
+  const int64_t* forced_actions;/* [rows,W] or NULL (SAMPLE, iterations == 1)               */
+  float* logits_scratch;        /* [B,N,N]; required above rl4co_aco_cvrp_lds_nodes()       */
+  int64_t* actions;             /* [rows,T] last iteration's rows (UPDATE alone: input)     */
+  int32_t* lengths;             /* [rows] actions up to and including done (SAMPLE)         */
+  float* reward;                /* [rows] last iteration's rewards (UPDATE alone: input)    */
+  float* logps;                 /* [rows,W] or NULL                                         */
+  float* all_logps;             /* [rows,W,N] or NULL                                       */
+  int64_t* iter_actions;        /* [iterations,rows,W] or NULL                              */
+  int32_t* iter_lengths;        /* [iterations,rows] or NULL                                */
+  float* iter_reward;           /* [iterations,rows] or NULL                                */
+  float* final_reward;          /* [B] in / out (UPDATE)                                    */
+  int64_t* final_actions;       /* [B,T] in / out (UPDATE)                                  */
+  int32_t* final_iteration;     /* [B] or NULL: written where the record is replaced        */
+  float* final_reward_cache;    /* [iterations,B] or NULL                                   */
+  int32_t* err;                 /* sticky error bits                                        */
+} rl4co_aco_cvrp_args;
+
+int rl4co_aco_cvrp(const rl4co_aco_cvrp_args* args, void* stream);
+/* Largest N at which rl4co_aco_cvrp keeps the logits and the pheromone in LDS (the kernel's LDS budget, aco_cvrp.hip header). */
+int rl4co_aco_cvrp_lds_nodes(void);
 
 /* --------------------------------------------------------------------------
  * a11-a13  fused encoder + decoder-cache fold on the matrix cores (inference rollouts).

@@ -1,5 +1,6 @@
 """Ant System search on a heatmap: the reference's ``AntSystem`` (models/zoo/deepaco/antsystem.py), DeepACO's test-time
-loop, behind its own class surface with the loop inside ONE kernel launch (``rl4co_aco_tsp``, csrc/aco_tsp.hip).
+loop, behind its own class surface with the loop inside ONE kernel launch (``rl4co_aco_tsp``, csrc/aco_tsp.hip; for CVRP
+``rl4co_aco_cvrp``, csrc/aco_cvrp.hip).
 
 ``run`` without local search is one launch for all iterations and one read-back of the error word. With
 ``use_local_search`` every iteration is a SAMPLE launch, ``env.local_search`` (the 2-opt kernel, from ``td["locs"]``, on the
@@ -7,7 +8,14 @@ device), ``env.get_reward`` and an UPDATE launch. The update (best tour, reward 
 bit; the sampled tours follow the kernel's own noise (Philox), so they are the reference's in distribution, not draw for
 draw. Served: TSP, ``multistart`` decoding with ``num_starts == n_ants``, ``select_start_nodes_fn``, ``temperature``.
 Refused (``NotImplementedError``): other environments, ``use_nls``, ``top_k`` / ``top_p`` / ``multisample`` and any other
-decoding keyword, CPU tensors."""
+decoding keyword, CPU tensors.
+
+CVRP (``env.name == "cvrp"``, the heatmap's node 0 is the depot): ``multisample`` with ``num_samples == n_ants`` (DeepACO's
+default: every ant starts at the depot) or ``multistart`` with ``num_starts == n_ants``; no local search (the reference's
+is the external HGS library). The kernel's rows are ``W = max(C + 1, 2 C - 1)`` wide and zero-filled after each row's
+length, and every reward is the one of that W-wide row (csrc/aco_cvrp.hip states why). ``final_actions`` is the reference's
+ragged list: entry ``b`` has the width the reference's batch had in the iteration that last replaced it, the longest row of
+that iteration, which takes one small read-back (with the error word) after the launch."""
 from __future__ import annotations
 
 import torch
@@ -17,6 +25,7 @@ from . import _lib
 from . import kernels as K
 
 _SERVED_KWARGS = ("multistart", "num_starts", "select_best", "select_start_nodes_fn", "temperature")
+_SERVED_KWARGS_CVRP = _SERVED_KWARGS + ("multisample", "num_samples")
 
 
 class AntSystem:
@@ -53,9 +62,11 @@ class AntSystem:
 
     # ---- what the kernel takes ---------------------------------------------------------------------------------------
     def _check(self, td, env, decoding_kwargs: dict) -> float:
+        if getattr(env, "name", None) == "cvrp":
+            return self._check_cvrp(td, decoding_kwargs)
         if getattr(env, "name", None) != "tsp":
-            raise NotImplementedError(f"AntSystem serves the tsp environment only (rl4co_aco_tsp), got "
-                                      f"{getattr(env, 'name', env)!r}")
+            raise NotImplementedError(f"AntSystem serves the tsp and cvrp environments only (rl4co_aco_tsp, rl4co_aco_cvrp), "
+                                      f"got {getattr(env, 'name', env)!r}")
         for key in decoding_kwargs:
             if key not in _SERVED_KWARGS:
                 raise NotImplementedError(f"decoding_kwargs[{key!r}] is not served by the Ant System kernel")
@@ -68,6 +79,27 @@ class AntSystem:
         for name, t in (("log_heuristic", self.log_heuristic), ("pheromone", self.pheromone), ("td['locs']", td["locs"])):
             if not t.is_cuda:
                 raise NotImplementedError(f"AntSystem runs inside the MI355X kernel (rl4co_aco_tsp) only: {name} on {t.device}")
+        return float(decoding_kwargs.get("temperature", 1.0))
+
+    def _check_cvrp(self, td, decoding_kwargs: dict) -> float:
+        if self.use_local_search:
+            raise NotImplementedError("use_local_search is not served for cvrp: the reference's CVRP local search is the "
+                                      "external HGS library")
+        for key in decoding_kwargs:
+            if key not in _SERVED_KWARGS_CVRP:
+                raise NotImplementedError(f"decoding_kwargs[{key!r}] is not served by the Ant System kernel")
+        multistart = bool(decoding_kwargs.get("multistart", False))
+        if multistart == bool(decoding_kwargs.get("multisample", False)):
+            raise NotImplementedError("exactly one of decoding_kwargs['multistart'] and decoding_kwargs['multisample'] must "
+                                      "be True for cvrp")
+        key = "num_starts" if multistart else "num_samples"
+        if decoding_kwargs.get(key, self.n_ants) != self.n_ants:
+            raise NotImplementedError(f"decoding_kwargs[{key!r}] must equal n_ants = {self.n_ants}")
+        if decoding_kwargs.get("select_best", False):
+            raise NotImplementedError("decoding_kwargs['select_best'] must be False: the update needs every ant's tour")
+        for name, t in (("log_heuristic", self.log_heuristic), ("pheromone", self.pheromone), ("td['locs']", td["locs"])):
+            if not t.is_cuda:  # (before td['demand'] is touched)
+                raise NotImplementedError(f"AntSystem runs inside the MI355X kernel (rl4co_aco_cvrp) only: {name} on {t.device}")
         return float(decoding_kwargs.get("temperature", 1.0))
 
     def _tensors(self, td):
@@ -103,6 +135,12 @@ class AntSystem:
     # ---- AntSystem.run (antsystem.py:87-118) -----------------------------------------------------------------------------
     def run(self, td_initial, env, n_iterations: int, decoding_kwargs: dict, disable_tqdm: bool = True):
         temperature = self._check(td_initial, env, decoding_kwargs)
+        if env.name == "cvrp":
+            out = self._sampling_cvrp(td_initial, env, decoding_kwargs, temperature, n_iterations)
+            for i in range(n_iterations):
+                self.final_reward_cache[i] = out["final_reward_cache"][i].clone()
+            self.last_iterations = {"actions": out["iter_actions"], "reward": out["iter_reward"], "lengths": out["iter_lengths"]}
+            return self._convert_final_action_to_matrix(), self.final_reward_cache
         if self.use_local_search:
             acts, rews, sampled = [], [], []
             for i in range(n_iterations):
@@ -132,6 +170,9 @@ class AntSystem:
     def _one_step(self, td, env, decoding_kwargs: dict):
         """One iteration: sample, optional local search, update. Returns (actions [rows, N], reward [rows]), ant-major."""
         temperature = self._check(td, env, decoding_kwargs)
+        if env.name == "cvrp":  # actions [rows, W], zero-filled after each row's length
+            out = self._sampling_cvrp(td, env, decoding_kwargs, temperature, 1)
+            return out["actions"], out["reward"]
         heu, locs = self._tensors(td)
         starts = self._start_nodes(td, env, decoding_kwargs)[None].contiguous()
         seed, offset = self._next_seed()
@@ -152,6 +193,39 @@ class AntSystem:
         self._take_record(out)
         return actions, reward
 
+    # ---- CVRP: sampling and update of ``n_iterations`` iterations in one launch (rl4co_aco_cvrp) -----------------------------
+    def _sampling_cvrp(self, td, env, decoding_kwargs: dict, temperature: float, n_iterations: int) -> dict:
+        heu, locs = self._tensors(td)
+        dev, b = heu.device, self.batch_size
+        demand = td["demand"].detach().to(device=dev, dtype=torch.float32).contiguous()
+        capacity = td["vehicle_capacity"].detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        starts = None
+        if decoding_kwargs.get("multistart", False):  # Sampling.pre_decoder_hook: called once per iteration
+            starts = torch.stack([self._start_nodes(td, env, decoding_kwargs) for _ in range(n_iterations)], 0).contiguous()
+        seed, offset = self._next_seed()
+        err = K.new_error_word(dev)
+        width = K.aco_cvrp_width(heu.shape[1])
+        has = self.final_reward is not None
+        record = dict(has_best=has, final_reward=self.final_reward if has else None, final_actions=None)
+        if has:  # the ragged list, zero-padded to the kernel's width
+            record["final_actions"] = torch.stack(
+                [torch.nn.functional.pad(t, (0, width - t.shape[0])) for t in self.final_actions], 0).contiguous()
+        out = K.aco_cvrp(self.pheromone, iterations=n_iterations, log_heuristic=heu, locs=locs, demand=demand,
+                         vehicle_capacity=capacity, start_nodes=starts, philox_seed=seed, philox_offset=offset,
+                         record_iterations=True, err=err, **record, **self._common(temperature))
+        # the one read-back of the run: the error word, which iteration last replaced each record, every iteration's width
+        widths = out["iter_lengths"].amax(1).to(torch.int32)
+        host = torch.cat((err, out["final_iteration"], widths)).tolist()
+        _lib.raise_for_error_bits(host[0])
+        replaced, widths = host[1 : 1 + b], host[1 + b :]
+        self.final_reward = out["final_reward"]
+        if not has:
+            self.final_actions = [None] * b
+        for i, it in enumerate(replaced):  # antsystem.py:238-245: the entry has the width of its iteration's batch
+            if it >= 0:
+                self.final_actions[i] = out["final_actions"][i, : widths[it]].clone()
+        return out
+
     # ---- AntSystem.local_search (antsystem.py:173-230), without the host round trip --------------------------------------
     def local_search(self, td, env, actions: Tensor, decoding_kwargs: dict):
         if getattr(env, "name", None) != "tsp":
@@ -166,4 +240,7 @@ class AntSystem:
 
     def _convert_final_action_to_matrix(self) -> Tensor:
         assert self.final_actions is not None
-        return torch.stack(self.final_actions, 0)
+        count = max(len(t) for t in self.final_actions)  # antsystem.py:284-294: zero-padded to the longest entry
+        if all(len(t) == count for t in self.final_actions):
+            return torch.stack(self.final_actions, 0)
+        return torch.stack([torch.nn.functional.pad(t, (0, count - len(t))) for t in self.final_actions], 0)

@@ -649,6 +649,135 @@ def aco_tsp(pheromone: Tensor, *, n_ants: int, phases: int = _lib.ACO_SAMPLE | _
     return out
 
 
+def aco_cvrp_lds_nodes() -> int:
+    """Largest node count (depot included) at which the CVRP Ant System kernel keeps logits and pheromone in LDS."""
+    return int(_lib.lib().rl4co_aco_cvrp_lds_nodes())
+
+
+def aco_cvrp_width(n: int) -> int:
+    """W = max(C + 1, 2 C - 1), C = n - 1: the longest action row the reference's CVRP sampling loop can produce."""
+    return max(n, 2 * n - 3)
+
+
+def aco_cvrp(pheromone: Tensor, *, n_ants: int, phases: int = _lib.ACO_SAMPLE | _lib.ACO_UPDATE, iterations: int = 1,
+             log_heuristic: Tensor | None = None, locs: Tensor | None = None, demand: Tensor | None = None,
+             vehicle_capacity: Tensor | None = None, start_nodes: Tensor | None = None,
+             alpha: float = 1.0, beta: float = 1.0, decay: float = 0.95, Q: float = 1.0, temperature: float = 1.0,
+             ln_noise: Tensor | None = None, philox_seed: int = 0, philox_offset: int = 0,
+             philox_seed_dev: Tensor | None = None, forced_actions: Tensor | None = None, actions: Tensor | None = None,
+             reward: Tensor | None = None, final_reward: Tensor | None = None, final_actions: Tensor | None = None,
+             final_iteration: Tensor | None = None, has_best: bool = False, iteration_base: int = 0,
+             all_logps: bool = False, record_iterations: bool = False, err: Tensor | None = None) -> dict:
+    """Ant System iterations for CVRP on ``pheromone`` [B, n, n] (fp32, the depot is node 0, updated IN PLACE) in one
+    launch (rl4co_aco_cvrp; the header states the arithmetic). Rows are ant-major as in :func:`aco_tsp`; sampled rows are
+    ``W = aco_cvrp_width(n)`` wide, zero-filled after ``lengths[row]``.
+
+    ``locs`` [B, n, 2] with the depot at 0, ``demand`` [B, n - 1], ``vehicle_capacity`` [B] or [B, 1]. ``start_nodes``
+    int64 [iterations, rows] of customers (multistart) or None (multisample: every ant starts at the depot).
+    ``ln_noise`` fp32 [iterations, W, rows, n] (parity mode) or None for the in-kernel Philox. SAMPLE alone samples (or,
+    with ``forced_actions`` [rows, W], evaluates) once; UPDATE alone takes ``actions`` [rows, T] of any width T >= 2 and
+    ``reward`` [rows]. The reward is the one of the W-wide padded row (``CVRPEnv.get_reward`` on it, bit for bit).
+    ``final_reward`` [B] / ``final_actions`` [B, T] / ``final_iteration`` [B] (int32, ``iteration_base + it`` of the last
+    replacement, -1 where none happened) are updated in place when given, else created. Returns a dict of the tensors the
+    launch wrote: actions, lengths, reward, logps, final_reward, final_actions, final_iteration, final_reward_cache
+    [iterations, B] and, on request, all_logps [rows, W, n], iter_actions [iterations, rows, W], iter_lengths and
+    iter_reward [iterations, rows]. ``err`` as in :func:`aco_tsp`."""
+    for name, t in (("pheromone", pheromone), ("log_heuristic", log_heuristic), ("locs", locs), ("demand", demand)):
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError(f"aco_cvrp runs inside the MI355X kernel (rl4co_aco_cvrp) only: {name} on {t.device}")
+    pheromone = _dev(pheromone, torch.float32, "pheromone")
+    if pheromone.dim() != 3 or pheromone.shape[1] != pheromone.shape[2]:
+        raise ValueError(f"pheromone must be [B, n, n], got {tuple(pheromone.shape)}")
+    b, n, _ = pheromone.shape
+    if not 2 <= n <= 1024:
+        raise NotImplementedError(f"aco_cvrp serves 2..1024 nodes (depot included), got n = {n}")
+    n_ants, iterations = int(n_ants), int(iterations)
+    rows, w = n_ants * b, aco_cvrp_width(n)
+    dev = pheromone.device
+    sample, update = bool(phases & _lib.ACO_SAMPLE), bool(phases & _lib.ACO_UPDATE)
+
+    def shaped(t, dtype, shape, name):
+        if t is None:
+            return None
+        t = _dev(t, dtype, name)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    log_heuristic = shaped(log_heuristic, torch.float32, (b, n, n), "log_heuristic")
+    locs = shaped(locs, torch.float32, (b, n, 2), "locs")
+    demand = shaped(demand, torch.float32, (b, n - 1), "demand")
+    if vehicle_capacity is not None:
+        vehicle_capacity = shaped(vehicle_capacity.reshape(-1), torch.float32, (b,), "vehicle_capacity")
+    start_nodes = shaped(start_nodes, torch.int64, (iterations, rows), "start_nodes")
+    ln_noise = shaped(ln_noise, torch.float32, (iterations, w, rows, n), "ln_noise")
+    forced_actions = shaped(forced_actions, torch.int64, (rows, w), "forced_actions")
+    if sample:
+        if actions is not None or reward is not None:
+            raise ValueError("actions / reward are outputs of the SAMPLE phase")
+        if demand is None or vehicle_capacity is None:
+            raise ValueError("the SAMPLE phase takes demand [B, n - 1] and vehicle_capacity [B]")
+        actions = torch.zeros((rows, w), dtype=torch.int64, device=dev)
+        reward = torch.zeros(rows, dtype=torch.float32, device=dev)
+        t = w
+    elif actions is None or reward is None:
+        raise ValueError("the UPDATE phase alone takes actions [rows, T] and reward [rows]")
+    else:
+        t = actions.shape[-1]
+        if t < 2:
+            raise ValueError(f"actions must be [rows, T] with T >= 2, got {tuple(actions.shape)}")
+    actions = shaped(actions, torch.int64, (rows, t), "actions")
+    reward = shaped(reward, torch.float32, (rows,), "reward")
+    out = {"actions": actions, "reward": reward}
+    if sample:
+        out["lengths"] = torch.zeros(rows, dtype=torch.int32, device=dev)
+        out["logps"] = torch.zeros((rows, w), dtype=torch.float32, device=dev)
+        if all_logps:
+            out["all_logps"] = torch.zeros((rows, w, n), dtype=torch.float32, device=dev)
+        if record_iterations:
+            out["iter_actions"] = torch.zeros((iterations, rows, w), dtype=torch.int64, device=dev)
+            out["iter_lengths"] = torch.zeros((iterations, rows), dtype=torch.int32, device=dev)
+            out["iter_reward"] = torch.zeros((iterations, rows), dtype=torch.float32, device=dev)
+    if update:
+        if (final_reward is None) != (final_actions is None):
+            raise ValueError("final_reward and final_actions come together")
+        if final_reward is None:
+            if has_best:
+                raise ValueError("has_best needs final_reward and final_actions")
+            final_reward = torch.zeros(b, dtype=torch.float32, device=dev)
+            final_actions = torch.zeros((b, t), dtype=torch.int64, device=dev)
+        if final_iteration is None:
+            final_iteration = torch.full((b,), -1, dtype=torch.int32, device=dev)
+        out["final_reward"] = shaped(final_reward, torch.float32, (b,), "final_reward")
+        out["final_actions"] = shaped(final_actions, torch.int64, (b, t), "final_actions")
+        out["final_iteration"] = shaped(final_iteration, torch.int32, (b,), "final_iteration")
+        out["final_reward_cache"] = torch.zeros((iterations, b), dtype=torch.float32, device=dev)
+    scratch = torch.empty((b, n, n), dtype=torch.float32, device=dev) if n > aco_cvrp_lds_nodes() else None
+    own = err is None
+    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
+    a = _lib.AcoCvrpArgs()
+    a.B, a.N, a.n_ants, a.iterations, a.phases, a.has_best = b, n, n_ants, iterations, int(phases), int(bool(has_best))
+    a.T, a.iteration_base = t, int(iteration_base)
+    a.alpha, a.beta, a.decay, a.Q, a.temperature, a.reserved0 = alpha, beta, decay, Q, temperature, 0
+    a.philox_seed, a.philox_offset = int(philox_seed) & (2**64 - 1), int(philox_offset) & (2**64 - 1)
+    a.philox_seed_dev = _ptr(philox_seed_dev)
+    a.log_heuristic, a.pheromone, a.locs = _ptr(log_heuristic), _ptr(pheromone), _ptr(locs)
+    a.demand, a.vehicle_capacity, a.start_nodes = _ptr(demand), _ptr(vehicle_capacity), _ptr(start_nodes)
+    a.ln_noise, a.forced_actions, a.logits_scratch = _ptr(ln_noise), _ptr(forced_actions), _ptr(scratch)
+    a.actions, a.lengths, a.reward = _ptr(actions), _ptr(out.get("lengths")), _ptr(reward)
+    a.logps, a.all_logps = _ptr(out.get("logps")), _ptr(out.get("all_logps"))
+    a.iter_actions, a.iter_lengths = _ptr(out.get("iter_actions")), _ptr(out.get("iter_lengths"))
+    a.iter_reward = _ptr(out.get("iter_reward"))
+    a.final_reward, a.final_actions = _ptr(out.get("final_reward")), _ptr(out.get("final_actions"))
+    a.final_iteration, a.final_reward_cache = _ptr(out.get("final_iteration")), _ptr(out.get("final_reward_cache"))
+    a.err = _ptr(err)
+    st = _lib.lib().rl4co_aco_cvrp(C.byref(a), _stream())
+    _lib.check(st, "rl4co_aco_cvrp")
+    if own:
+        raise_if_error(err)
+    return out
+
+
 def decoding_filter(top_k, top_p, n: int) -> tuple[int, float]:
     """The top-k / top-p arguments of utils/decoding.py:109-188 as the kernel takes them: ``top_k <= 0`` is off and is
     clamped to ``n`` (k >= n removes nothing: 0); ``top_p <= 0`` or ``>= 1`` is off (0.0); ``top_p > 1`` raises the

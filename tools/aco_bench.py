@@ -9,6 +9,10 @@ each timed with HIP events around the whole ``run`` (host work included) and syn
 Next to the times: the mean best tour length after the last iteration, in float64.
 
     python tools/aco_bench.py [--reps 5] [--batch 4096] [--num-loc 100] [--out profiles/aco_bench.json]
+
+``--env cvrp`` times the CVRP search (csrc/aco_cvrp.hip) instead: 4096 x CVRP-100 from the environment's generator, 48 ants,
+10 iterations, ``multisample`` decoding (every ant starts at the depot), heuristic -log(distance). One leg, ``fused``: there
+is no earlier CVRP path to compare with. Writes profiles/aco_cvrp_bench.json unless ``--out`` says otherwise.
 """
 import argparse
 import json
@@ -72,9 +76,14 @@ def torch_ant_system(heu, locs, n_ants, iterations, alpha=1.0, beta=1.0, decay=0
     return best_actions
 
 
+def cvrp_length64(locs, tours):
+    """Closed length of [depot, tours] in float64 (trailing depot visits add nothing)."""
+    return length64(locs, torch.cat((torch.zeros_like(tours[:, :1]), tours), 1))
+
+
 class Leg:
-    def __init__(self, kind, fn):
-        self.kind, self.fn, self.times, self.tours = kind, fn, [], None
+    def __init__(self, kind, fn, length=length64):
+        self.kind, self.fn, self.times, self.tours, self.length = kind, fn, [], None, length
 
     def launch(self, keep: bool):
         torch.cuda.synchronize()
@@ -89,7 +98,7 @@ class Leg:
     def result(self, locs):
         t = sorted(self.times)
         return dict(leg=self.kind, reps=len(t), median_ms=t[len(t) // 2], min_ms=t[0], max_ms=t[-1],
-                    mean_best_length_f64=float(length64(locs, self.tours).mean()))
+                    mean_best_length_f64=float(self.length(locs, self.tours).mean()))
 
 
 def main():
@@ -100,10 +109,13 @@ def main():
     ap.add_argument("--ants", type=int, default=48)
     ap.add_argument("--iterations", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--env", choices=("tsp", "cvrp"), default="tsp")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("aco_bench needs the MI355X: a time taken anywhere else says nothing")
     dev = torch.device("cuda", 0)
+    if a.env == "cvrp":
+        return main_cvrp(a, dev)
     g = torch.Generator().manual_seed(1234)
     locs = torch.rand(a.batch, a.num_loc, 2, generator=g).to(dev)
     dist = (locs[:, :, None] - locs[:, None, :]).norm(p=2, dim=-1)
@@ -134,6 +146,34 @@ def main():
                            case=f"tsp{a.num_loc}x{a.batch}, {a.ants} ants, {a.iterations} iterations",
                            what="AntSystem.run end to end (host work included), HIP events around the call, synchronised",
                            rows=rows), f, indent=1)
+
+
+def main_cvrp(a, dev):
+    torch.manual_seed(1234)
+    env = get_env("cvrp", generator_params=dict(num_loc=a.num_loc, device=dev), device=dev)
+    td = env.reset(batch_size=[a.batch])
+    locs = td["locs"]  # [B, num_loc + 1, 2], the depot first
+    dist = (locs[:, :, None] - locs[:, None, :]).norm(p=2, dim=-1)
+    heu = -torch.log(dist + 1e9 * torch.eye(a.num_loc + 1, device=dev))
+    kwargs = dict(multisample=True, num_samples=a.ants, select_best=False)
+
+    def run():
+        torch.manual_seed(0)
+        return AntSystem(heu, n_ants=a.ants).run(td, env, a.iterations, kwargs)[0]
+
+    leg = Leg("fused", run, cvrp_length64)
+    for it in range(a.reps + 1):  # one warm-up round
+        leg.launch(keep=it >= 1)
+    env.check_solution_validity(td, leg.tours)
+    row = leg.result(locs)
+    print(json.dumps(row), flush=True)
+    out = a.out or "profiles/aco_cvrp_bench.json"
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(dict(device=torch.cuda.get_device_name(0), when=time.strftime("%Y-%m-%d"),
+                       case=f"cvrp{a.num_loc}x{a.batch}, {a.ants} ants, {a.iterations} iterations, multisample",
+                       what="AntSystem.run end to end (host work included), HIP events around the call, synchronised",
+                       rows=[row]), f, indent=1)
 
 
 if __name__ == "__main__":
