@@ -47,8 +47,9 @@ extern "C" {
  *  17: rl4co_tsp_two_opt / rl4co_tsp_two_opt_lds_nodes (TSP local search, rl4co_tsp_two_opt_args);
  *      RL4CO_EBIT_TOUR_INDEX.
  *  18: rl4co_aco_tsp / rl4co_aco_tsp_lds_nodes (Ant System search on a heatmap, rl4co_aco_tsp_args, RL4CO_ACO_*).
- *  19: rl4co_aco_cvrp / rl4co_aco_cvrp_lds_nodes (the same search for CVRP, rl4co_aco_cvrp_args). */
-#define RL4CO_ABI_VERSION 19
+ *  19: rl4co_aco_cvrp / rl4co_aco_cvrp_lds_nodes (the same search for CVRP, rl4co_aco_cvrp_args).
+ *  20: rl4co_tsp_nls / rl4co_tsp_nls_lds_nodes (neural-guided local search for TSP, rl4co_tsp_nls_args). */
+#define RL4CO_ABI_VERSION 20
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -721,6 +722,51 @@ typedef struct rl4co_aco_cvrp_args {
 int rl4co_aco_cvrp(const rl4co_aco_cvrp_args* args, void* stream);
 /* Largest N at which rl4co_aco_cvrp keeps the logits and the pheromone in LDS (the kernel's LDS budget, aco_cvrp.hip header). */
 int rl4co_aco_cvrp_lds_nodes(void);
+
+/* --------------------------------------------------------------------------
+ * Neural-guided local search for TSP (DeepACO's NLS: AntSystem.local_search with use_nls, antsystem.py:173-230) as ONE
+ * launch, one workgroup per tour row (tsp_nls.hip). Row r uses instance r % n_instances (the ant-major rows of
+ * rl4co_aco_tsp); neither `locs` nor `perturb_distances` is tiled per ant. Per row, with two_opt the search of
+ * rl4co_tsp_two_opt (the same text, every rule above: association, lowest (i, j) on ties, -1e-6 in double):
+ *   cur  = two_opt(real, cur, ls_max_iterations)
+ *   best = cur (written to out_actions[row]); best_r = reward(cur)
+ *   n_perturbations times:
+ *     cur = two_opt(perturb, cur, perturb_max_iterations)
+ *     cur = two_opt(real,    cur, ls_max_iterations)
+ *     r   = reward(cur);  if r > best_r (fp32, NaN never wins): out_actions[row] = cur, best_r = r
+ *     (cur carries on whether or not it won)
+ *   out_reward[row] = best_r
+ * `real` is d[a][b] = sqrtf(fmaf(dy, dy, dx * dx)) from `locs` with d[a][a] = 1e9; `perturb` is perturb_distances (given
+ * WITHOUT the diagonal, may be asymmetric) with 1e9 added on its diagonal. reward is minus the closed tour length from
+ * `locs`, bit-equal to rl4co_tour_length_f32's. `scans` holds the scans of each of the 1 + 2 * n_perturbations searches,
+ * counted as rl4co_tsp_two_opt's `iterations`; `accepted` the rounds that replaced the best tour.
+ * Up to rl4co_tsp_nls_lds_nodes() nodes one matrix slot in LDS is restaged at each phase switch; above, up to 1024, the real
+ * phases compute distances from coordinates in LDS and the perturbation phases read global memory.
+ * A tour with an index outside [0, N) sets RL4CO_EBIT_TOUR_INDEX and is copied through unchanged with reward NaN, zero
+ * scans and zero accepted. out_actions == actions (in place) is allowed.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_tsp_nls_args {
+  int32_t R;                      /* tour rows (= workgroups), >= 1, R % n_instances == 0    */
+  int32_t n_instances;            /* I >= 1; row r uses instance r % I                       */
+  int32_t N;                      /* nodes, 2 .. 1024                                        */
+  int32_t T;                      /* tour length, 1 .. 1024                                  */
+  int32_t ls_max_iterations;      /* >= 0: scans of a search over the real distances         */
+  int32_t perturb_max_iterations; /* >= 0: scans of a search over perturb_distances          */
+  int32_t n_perturbations;        /* >= 0 rounds                                             */
+  int32_t reserved0;              /* 0                                                       */
+  const float* locs;              /* [I,N,2]                                                 */
+  const float* perturb_distances; /* [I,N,N], without the 1e9 diagonal                       */
+  const int64_t* actions;         /* [R,T]                                                   */
+  int64_t* out_actions;           /* [R,T] the best tour of each row                         */
+  float* out_reward;              /* [R] its reward                                          */
+  int32_t* scans;                 /* [R, 1 + 2 * n_perturbations] or NULL                    */
+  int32_t* accepted;              /* [R] or NULL                                             */
+  int32_t* err;                   /* sticky error bits                                       */
+} rl4co_tsp_nls_args;
+
+int rl4co_tsp_nls(const rl4co_tsp_nls_args* args, void* stream);
+/* Largest N whose distance matrix rl4co_tsp_nls keeps in LDS (the kernel's LDS budget, tsp_nls.hip header). */
+int rl4co_tsp_nls_lds_nodes(void);
 
 /* --------------------------------------------------------------------------
  * a11-a13  fused encoder + decoder-cache fold on the matrix cores (inference rollouts).

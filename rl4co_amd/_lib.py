@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 19  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 20  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -115,6 +115,17 @@ class TspTwoOptArgs(C.Structure):
     _fields_ = [
         ("B", _i32), ("N", _i32), ("T", _i32), ("max_iterations", _i32),
         ("locs", _vp), ("distances", _vp), ("actions", _vp), ("out_actions", _vp), ("iterations", _vp), ("err", _vp),
+    ]
+
+
+class TspNlsArgs(C.Structure):
+    """Mirror of ``struct rl4co_tsp_nls_args`` (field order and types must match the header)."""
+
+    _fields_ = [
+        ("R", _i32), ("n_instances", _i32), ("N", _i32), ("T", _i32),
+        ("ls_max_iterations", _i32), ("perturb_max_iterations", _i32), ("n_perturbations", _i32), ("reserved0", _i32),
+        ("locs", _vp), ("perturb_distances", _vp), ("actions", _vp), ("out_actions", _vp), ("out_reward", _vp),
+        ("scans", _vp), ("accepted", _vp), ("err", _vp),
     ]
 
 
@@ -252,6 +263,8 @@ SYMBOLS = {
     "rl4co_aco_tsp_lds_nodes": (C.c_int, []),
     "rl4co_aco_cvrp": (C.c_int, [C.POINTER(AcoCvrpArgs), _vp]),
     "rl4co_aco_cvrp_lds_nodes": (C.c_int, []),
+    "rl4co_tsp_nls": (C.c_int, [C.POINTER(TspNlsArgs), _vp]),
+    "rl4co_tsp_nls_lds_nodes": (C.c_int, []),
     "rl4co_select_start_nodes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "rl4co_augment_dihedral8_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_augment_symmetric_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp]),

@@ -4,19 +4,25 @@ loop, behind its own class surface with the loop inside ONE kernel launch (``rl4
 
 ``run`` without local search is one launch for all iterations and one read-back of the error word. With
 ``use_local_search`` every iteration is a SAMPLE launch, ``env.local_search`` (the 2-opt kernel, from ``td["locs"]``, on the
-device), ``env.get_reward`` and an UPDATE launch. The update (best tour, reward map, pheromone) is the reference's bit for
-bit; the sampled tours follow the kernel's own noise (Philox), so they are the reference's in distribution, not draw for
-draw. Served: TSP, ``multistart`` decoding with ``num_starts == n_ants``, ``select_start_nodes_fn``, ``temperature``.
-Refused (``NotImplementedError``): other environments, ``use_nls``, ``top_k`` / ``top_p`` / ``multisample`` and any other
-decoding keyword, CPU tensors.
+device), ``env.get_reward`` and an UPDATE launch. With ``use_nls`` as well (DeepACO's neural-guided local search) the local
+search of an iteration is ONE launch instead (``rl4co_tsp_nls``, csrc/tsp_nls.hip): the 2-opt, then ``n_perturbations``
+rounds of a 2-opt over ``heuristic_dist`` (the heatmap's distances) and a 2-opt over the real distances, the better tour
+kept per ant, rewards included. The update (best tour, reward map, pheromone) is the reference's bit for bit; the sampled
+tours follow the kernel's own noise (Philox), so they are the reference's in distribution, not draw for draw. Served: TSP,
+``use_local_search``, ``use_nls``, ``multistart`` decoding with ``num_starts == n_ants``, ``select_start_nodes_fn``,
+``temperature``. Refused (``NotImplementedError``): other environments, ``top_k`` / ``top_p`` / ``multisample`` and any
+other decoding keyword, CPU tensors (with ``use_nls`` by the constructor already: ``heuristic_dist`` is built on the
+heatmap's device).
 
 CVRP (``env.name == "cvrp"``, the heatmap's node 0 is the depot): ``multisample`` with ``num_samples == n_ants`` (DeepACO's
 default: every ant starts at the depot) or ``multistart`` with ``num_starts == n_ants``; no local search (the reference's
-is the external HGS library). The kernel's rows are ``W = max(C + 1, 2 C - 1)`` wide and zero-filled after each row's
-length, and every reward is the one of that W-wide row (csrc/aco_cvrp.hip states why). ``final_actions`` is the reference's
+is the external HGS library, so ``use_local_search`` and with it ``use_nls`` stay refused). The kernel's rows are
+``W = max(C + 1, 2 C - 1)`` wide and zero-filled after each row's length, and every reward is the one of that W-wide row (csrc/aco_cvrp.hip states why). ``final_actions`` is the reference's
 ragged list: entry ``b`` has the width the reference's batch had in the iteration that last replaced it, the longest row of
 that iteration, which takes one small read-back (with the error word) after the launch."""
 from __future__ import annotations
+
+from functools import cached_property
 
 import torch
 from torch import Tensor
@@ -52,13 +58,25 @@ class AntSystem:
         self.final_reward_cache: dict = {}
         self.use_local_search = use_local_search
         assert not (use_nls and not use_local_search), "use_nls requires use_local_search"
-        if use_nls:
-            raise NotImplementedError("use_nls (neural-guided perturbation) is not served by the Ant System kernel")
+        if use_nls and not log_heuristic.is_cuda:  # heuristic_dist and the search live on the heatmap's device
+            raise NotImplementedError(f"use_nls (neural-guided local search) runs inside the MI355X kernel (rl4co_tsp_nls) "
+                                      f"only: log_heuristic on {log_heuristic.device}")
         self.use_nls = use_nls
         self.n_perturbations = n_perturbations
         self.local_search_params = local_search_params.copy()
         self.perturbation_params = perturbation_params.copy()
         self.last_iterations: dict | None = None  # tests only: per-iteration actions / rewards of the last run
+        self._err: Tensor | None = None  # the error word of the iteration in flight (None: local_search reads back its own)
+
+    @cached_property
+    def heuristic_dist(self) -> Tensor:
+        """antsystem.py:78-85 on the device of ``log_heuristic``: the heatmap as a distance matrix [B, N, N] fp32, 0 on the
+        diagonal (the local search adds its 1e9 there)."""
+        heuristic = self.log_heuristic.detach().to(torch.float32).exp() + 1e-10
+        heuristic_dist = 1 / (heuristic / heuristic.max(-1, keepdim=True)[0] + 1e-5)
+        n = heuristic_dist.shape[1]
+        heuristic_dist[:, torch.arange(n), torch.arange(n)] = 0
+        return heuristic_dist.contiguous()
 
     # ---- what the kernel takes ---------------------------------------------------------------------------------------
     def _check(self, td, env, decoding_kwargs: dict) -> float:
@@ -186,7 +204,11 @@ class AntSystem:
             sampled = K.aco_tsp(self.pheromone, phases=_lib.ACO_SAMPLE, log_heuristic=heu, locs=locs, start_nodes=starts,
                                 philox_seed=seed, philox_offset=offset, err=err, **common)
             self._sampled_reward = sampled["reward"]  # (tests: the local search never makes a tour longer)
-            actions, reward = self.local_search(td, env, sampled["actions"], decoding_kwargs)
+            self._err = err  # the NLS launch ORs into this iteration's word: read back once, below
+            try:
+                actions, reward = self.local_search(td, env, sampled["actions"], decoding_kwargs)
+            finally:
+                self._err = None
             out = K.aco_tsp(self.pheromone, phases=_lib.ACO_UPDATE, actions=actions.contiguous(),
                             reward=reward.to(torch.float32).contiguous(), err=err, **self._record(), **common)
         _lib.raise_for_error_bits(int(err.item()))
@@ -230,6 +252,8 @@ class AntSystem:
     def local_search(self, td, env, actions: Tensor, decoding_kwargs: dict):
         if getattr(env, "name", None) != "tsp":
             raise NotImplementedError(f"Local search not implemented for {getattr(env, 'name', env)}")
+        if self.use_nls:
+            return self._nls(td, actions)
         locs = td["locs"]
         rows = actions.shape[0]
         # one instance row per ant row (ant-major, the reference's batchify): the 2-opt kernel pairs tour r with instance r
@@ -237,6 +261,27 @@ class AntSystem:
         best_actions = env.local_search(td=tiled, actions=actions, **self.local_search_params)
         best_rewards = env.get_reward(tiled, best_actions)
         return best_actions, best_rewards
+
+    @staticmethod
+    def _max_iterations(params: dict, name: str) -> int:
+        """``env.local_search(td, actions, max_iterations=1000, num_threads=0)``: any other key is a TypeError there."""
+        for key in params:
+            if key not in ("max_iterations", "num_threads"):  # num_threads: accepted and ignored (one workgroup per tour)
+                raise TypeError(f"local_search() got an unexpected keyword argument {key!r} (from {name})")
+        return int(params.get("max_iterations", 1000))
+
+    def _nls(self, td, actions: Tensor):
+        """The whole of antsystem.py:204-225 in one launch; the caller's error word, no read-back of its own."""
+        ls_cap = self._max_iterations(self.local_search_params, "local_search_params")
+        perturb_cap = self._max_iterations(self.perturbation_params, "perturbation_params")
+        dev = self.log_heuristic.device
+        if not actions.is_cuda or not dev.type == "cuda":
+            raise NotImplementedError(f"neural-guided local search runs inside the MI355X kernel (rl4co_tsp_nls) only: "
+                                      f"actions on {actions.device}, log_heuristic on {dev}")
+        locs = td["locs"].detach().to(device=dev, dtype=torch.float32).contiguous()
+        return K.tsp_nls(actions.contiguous(), locs=locs, perturb_distances=self.heuristic_dist,
+                         n_perturbations=int(self.n_perturbations), ls_max_iterations=ls_cap,
+                         perturb_max_iterations=perturb_cap, err=self._err)
 
     def _convert_final_action_to_matrix(self) -> Tensor:
         assert self.final_actions is not None

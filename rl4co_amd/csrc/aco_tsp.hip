@@ -12,9 +12,9 @@
 //              ln_noise: the caller's fp32 [iterations, N - 1, rows, N] (parity mode), else
 //              rl4co_logf(rl4co_exp1_noise(seed, philox_offset + it * N + t, row, n)). forced_actions: the given tours are
 //              followed and only their log-probs computed.
-//   R  reward  minus the closed tour length: tour_length.hip's arithmetic RESTATED here in the same order (ATen's
-//              vector_norm over two elements, then SumKernel's 8-lane / 4-ILP / 4-level cascade; lanes 0..7 of the ant's
-//              wave play the SIMD lanes) from the wave's tour in LDS; the expression text is kept equal to that file's
+//   R  reward  minus the closed tour length: tour_length.hip's arithmetic RESTATED in lds_tour_reward.h in the same order
+//              (ATen's vector_norm over two elements, then SumKernel's 8-lane / 4-ILP / 4-level cascade; lanes 0..7 of the
+//              ant's wave play the SIMD lanes) from the wave's tour in LDS; the expression text is kept equal to that file's
 //              TourView::seg and lane_row_sum — change both together. Bit-equal to TSPEnv.get_reward (tested).
 //   U  update  per instance over its ants, bit for bit the reference's _update_results / _reward_map / _update_pheromone:
 //              M, m = max, min reward; best ant = lowest j with r_j == M; the first iteration or final_reward <= M replaces
@@ -42,9 +42,13 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "lds_tour_reward.h"
 #include "rl4co_math.h"
 
 namespace {
+
+using rl4co::AntTour;  // lds_tour_reward.h: the reward of a tour held in LDS (shared with tsp_nls.hip)
+using rl4co::ant_reward;
 
 constexpr int kWaves = 4;
 constexpr int kThreads = 64 * kWaves;
@@ -58,85 +62,6 @@ constexpr float kNegInf = -__builtin_huge_valf();
 
 __host__ __device__ inline int64_t aco_lds_bytes(bool lds, int N) {
   return kScratchBytes + kTourBytes + (lds ? (int64_t)8 * N * N : 0);
-}
-
-// ---- reward: tour_length.hip's TourView::seg / lane_row_sum over the wave's LDS tour (same text, same order) -----------
-struct AntTour {
-  const uint16_t* tour;  // [n] in LDS
-  const float2* xy;      // [N] of the instance
-  int n;
-  __device__ inline float seg(int t) const {
-    const float2 p0 = xy[tour[t]];
-    const float2 p1 = xy[tour[t + 1 == n ? 0 : t + 1]];  // torch.roll(-1)
-    const float dx = p1.x - p0.x;
-    const float dy = p1.y - p0.y;
-    return sqrtf(fmaf(dy, dy, dx * dx));
-  }
-};
-
-__device__ float lane_row_sum(const AntTour& tv, int lane8, int nvec) {
-  constexpr int kIlp = 4;
-  constexpr int kLevels = 4;
-  const int size = nvec / kIlp;  // size_ilp
-  int ceil_log2 = 0;
-  while ((1LL << ceil_log2) < size) ++ceil_log2;
-  int level_power = ceil_log2 / kLevels;
-  if (level_power < 4) level_power = 4;
-  const int level_step = 1 << level_power;
-  const int level_mask = level_step - 1;
-  float acc[kLevels][kIlp];
-  for (int l = 0; l < kLevels; ++l)
-    for (int k = 0; k < kIlp; ++k) acc[l][k] = 0.0f;
-  int i = 0;
-  for (; i + level_step <= size;) {
-    for (int j = 0; j < level_step; ++j, ++i) {
-      for (int k = 0; k < kIlp; ++k) acc[0][k] = acc[0][k] + tv.seg(8 * (i * kIlp + k) + lane8);
-    }
-    for (int j = 1; j < kLevels; ++j) {
-      for (int k = 0; k < kIlp; ++k) {
-        acc[j][k] = acc[j][k] + acc[j - 1][k];
-        acc[j - 1][k] = 0.0f;
-      }
-      const int mask = level_mask << (j * level_power);
-      if ((i & mask) != 0) break;
-    }
-  }
-  for (; i < size; ++i) {
-    for (int k = 0; k < kIlp; ++k) acc[0][k] = acc[0][k] + tv.seg(8 * (i * kIlp + k) + lane8);
-  }
-  for (int j = 1; j < kLevels; ++j)
-    for (int k = 0; k < kIlp; ++k) acc[0][k] = acc[0][k] + acc[j][k];
-  for (int v = size * kIlp; v < nvec; ++v) acc[0][0] = acc[0][0] + tv.seg(8 * v + lane8);
-  for (int k = 1; k < kIlp; ++k) acc[0][0] = acc[0][0] + acc[0][k];
-  return acc[0][0];
-}
-
-// minus the closed tour length, valid in lane 0; the whole wave calls it (tour_length_kernel's body for one trajectory)
-__device__ float ant_reward(const AntTour& tv, int lane) {
-  const int n = tv.n;
-  const int nvec = n / 8;
-  if (n < 8) {  // ATen's scalar_inner_sum
-    float p[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (lane == 0) {
-      const int g = n / 4;
-      for (int i = 0; i < g; ++i)
-        for (int k = 0; k < 4; ++k) p[k] = p[k] + tv.seg(4 * i + k);
-      for (int k = 4 * g; k < n; ++k) p[0] = p[0] + tv.seg(k);
-      for (int k = 1; k < 4; ++k) p[0] = p[0] + p[k];
-    }
-    return -p[0];
-  }
-  float part = 0.0f;
-  if (lane < 8) part = lane_row_sum(tv, lane, nvec);
-  float fin = 0.0f;
-  if (lane == 0) {
-    for (int k = nvec * 8; k < n; ++k) fin = fin + tv.seg(k);
-  }
-  for (int l = 0; l < 8; ++l) {
-    const float pl = __shfl(part, l, 64);
-    fin = fin + pl;
-  }
-  return -fin;
 }
 
 template <bool LDS>

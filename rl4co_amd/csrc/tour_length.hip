@@ -9,8 +9,8 @@
 // Eight GPU lanes play the eight SIMD lanes of one CPU vector register, so one
 // wavefront reduces eight trajectories; the final lane-order scalar fold is done
 // with shuffles in the same l = 0..7 order as the CPU's store-and-add loop.
-// aco_tsp.hip RESTATES TourView::seg, lane_row_sum and the kernel's epilogue over a tour held in LDS (its reward must be
-// bit-equal to this file's): change both together.
+// lds_tour_reward.h (aco_tsp.hip, tsp_nls.hip) RESTATES TourView::seg, lane_row_sum and the kernel's epilogue over a tour
+// held in LDS (its reward must be bit-equal to this file's): change both together.
 #include <hip/hip_runtime.h>
 
 #include "common.h"

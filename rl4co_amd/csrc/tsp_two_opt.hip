@@ -17,7 +17,8 @@
 //            tour[i + k] and tour[j - k]; workgroup barrier; next iteration. `iterations` counts the last, non-improving
 //            scan too. No barrier sits inside divergent control flow; the only loop is bounded by max_iterations.
 //
-// Distances (one kernel template over the three sources, one text of the search loop):
+// Distances (one kernel template over the three sources, one text of the search loop: tsp_two_opt_search.h, which
+// tsp_nls.hip calls too):
 //   kMatrix   N <= rl4co_tsp_two_opt_lds_nodes(): the N x N fp32 matrix of the instance in LDS, 1e9 added on its diagonal —
 //             built by the workgroup from `locs`, or staged once from `distances` with coalesced loads.
 //   kCoords   above that, from `locs`: the coordinates in LDS (8 N bytes), every d[a][b] computed where it is used.
@@ -41,70 +42,11 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "tsp_two_opt_search.h"
 
 namespace {
 
-constexpr int kWaves = 4;
-constexpr int kThreads = 64 * kWaves;
-constexpr int kMaxTour = 1024;
-constexpr int kCuLds = 160 * 1024;
-constexpr int kRedBytes = 64;
-constexpr int kTourBytes = 2 * kMaxTour;
-constexpr int kStaticLds = 64;  // static LDS allowed beside the dynamic bytes (checked at launch)
-constexpr uint64_t kNoPair = ~0ull;
-
-enum Source { kMatrix = 0, kCoords = 1, kGlobal = 2 };
-
-__host__ __device__ inline int64_t two_opt_lds_bytes(int src, int N) {
-  return kRedBytes + kTourBytes + (src == kMatrix ? (int64_t)4 * N * N : src == kCoords ? (int64_t)8 * N : 0);
-}
-
-// order-preserving image of a float, ascending (NaN above everything)
-__device__ inline uint32_t ord_key(float v) {
-  if (v != v) return 0xffffffffu;
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ inline float ord_value(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// minimum of the 64-bit keys over the wave, in every lane
-template <int S = 1>
-__device__ inline uint64_t bfly_min_u64(uint64_t key) {
-  if constexpr (S < 64) {
-    const uint32_t oh = (uint32_t)rl4co::bfly_i<S>((int)(uint32_t)(key >> 32));
-    const uint32_t ol = (uint32_t)rl4co::bfly_i<S>((int)(uint32_t)key);
-    const uint64_t o = ((uint64_t)oh << 32) | ol;
-    return bfly_min_u64<S * 2>(o < key ? o : key);
-  } else {
-    return key;
-  }
-}
-
-__device__ inline float coord_distance(float2 pa, float2 pb) {
-  const float dx = pa.x - pb.x;
-  const float dy = pa.y - pb.y;
-  return sqrtf(fmaf(dy, dy, dx * dx));
-}
-
-// d[a][b] of the instance with 1e9 added on the diagonal, from the template's source
-template <int SRC>
-struct Distances {
-  const float* mat;     // kMatrix: LDS [N,N]; kGlobal: the instance's global [N,N]
-  const float2* xy;     // kCoords: LDS [N]
-  int N;
-  __device__ inline float operator()(int a, int b) const {
-    if constexpr (SRC == kMatrix) {
-      return mat[a * N + b];
-    } else if constexpr (SRC == kCoords) {
-      return a == b ? 1e9f : coord_distance(xy[a], xy[b]);
-    } else {
-      return mat[a * N + b] + (a == b ? 1e9f : 0.0f);
-    }
-  }
-};
+using namespace rl4co::two_opt;  // tsp_two_opt_search.h: the constants, Distances<SRC>, staging and the search loop
 
 template <int SRC>
 __global__ void __launch_bounds__(kThreads) tsp_two_opt_kernel(const rl4co_tsp_two_opt_args a) {
@@ -147,19 +89,10 @@ __global__ void __launch_bounds__(kThreads) tsp_two_opt_kernel(const rl4co_tsp_t
   dist.mat = nullptr;
   dist.xy = nullptr;
   if constexpr (SRC == kMatrix) {
-    const int nn = N * N;
     if (a.locs) {
-      const float2* xy = reinterpret_cast<const float2*>(a.locs) + (int64_t)blockIdx.x * N;
-      for (int e = tid; e < nn; e += kThreads) {
-        const int p = e / N, q = e - p * N;
-        payload[e] = p == q ? 1e9f : coord_distance(xy[p], xy[q]);
-      }
+      stage_matrix_from_locs(payload, reinterpret_cast<const float2*>(a.locs) + (int64_t)blockIdx.x * N, N, tid);
     } else {
-      const float* g = a.distances + (int64_t)blockIdx.x * nn;
-      for (int e = tid; e < nn; e += kThreads) {
-        const int p = e / N, q = e - p * N;
-        payload[e] = g[e] + (p == q ? 1e9f : 0.0f);
-      }
+      stage_matrix_from_distances(payload, a.distances + (int64_t)blockIdx.x * N * N, N, tid);
     }
     dist.mat = payload;
   } else if constexpr (SRC == kCoords) {
@@ -173,45 +106,7 @@ __global__ void __launch_bounds__(kThreads) tsp_two_opt_kernel(const rl4co_tsp_t
   __syncthreads();
 
   // ---- the search -------------------------------------------------------------------------------------------------
-  const int last = T - 1;  // pairs 1 <= i < j <= last; row i of the pair list holds j = i + 1 .. last
-  int it = 0;
-  while (it < a.max_iterations) {
-    uint64_t best = kNoPair;
-    // pair `tid` of the list, then every 256th: (i, j) advanced over the row ends
-    int i = 1, j = 2 + tid;
-    for (;;) {
-      while (i < last && j > last) {
-        j -= last - i - 1;  // (j - last - 1) past the row's end = the offset behind i + 2, the next row's first j
-        ++i;
-      }
-      if (i >= last) break;
-      const int ni = tour[i], nj = tour[j], np = tour[i - 1], nn = tour[j == last ? 0 : j + 1];
-      if (np != nj && nn != ni) {
-        const float change = ((dist(np, nj) + dist(ni, nn)) - dist(np, ni)) - dist(nj, nn);
-        if (change < 0.0f) {
-          const uint64_t key = ((uint64_t)ord_key(change) << 32) | (uint32_t)((i << 16) | j);
-          best = key < best ? key : best;
-        }
-      }
-      j += kThreads;
-    }
-    best = bfly_min_u64(best);
-    if ((tid & 63) == 0) red[tid >> 6] = best;
-    __syncthreads();
-    uint64_t win = red[0];
-    for (int w = 1; w < kWaves; ++w) win = red[w] < win ? red[w] : win;
-    ++it;
-    // every thread holds the same `win` (the same four LDS words, the same fold): a uniform decision
-    if (win == kNoPair || !((double)ord_value((uint32_t)(win >> 32)) < -1e-6)) break;
-    const int wi = (int)((uint32_t)win >> 16), wj = (int)((uint32_t)win & 0xffffu);
-    const int half = (wj - wi + 1) >> 1;
-    for (int k = tid; k < half; k += kThreads) {
-      const uint16_t lo = tour[wi + k], hi = tour[wj - k];
-      tour[wi + k] = hi;
-      tour[wj - k] = lo;
-    }
-    __syncthreads();  // the reversal is in place before the next scan; red[] is rewritten only behind this barrier
-  }
+  const int it = search(dist, tour, red, T, a.max_iterations, tid);  // tsp_two_opt_search.h
 
   for (int t = tid; t < T; t += kThreads) out[t] = (int64_t)tour[t];
   if (tid == 0 && a.iterations) a.iterations[blockIdx.x] = it;

@@ -552,6 +552,69 @@ def tsp_two_opt(actions: Tensor, *, locs: Tensor | None = None, distances: Tenso
     return (out, iters) if return_iterations else out
 
 
+def nls_lds_nodes() -> int:
+    """Largest node count whose distance matrix the NLS kernel keeps in LDS (its LDS budget; a host query)."""
+    return int(_lib.lib().rl4co_tsp_nls_lds_nodes())
+
+
+def tsp_nls(actions: Tensor, *, locs: Tensor, perturb_distances: Tensor, n_perturbations: int,
+            ls_max_iterations: int = 1000, perturb_max_iterations: int = 1000, err: Tensor | None = None,
+            return_counts: bool = False):
+    """Neural-guided local search (DeepACO's NLS, antsystem.py:173-230) on every tour row of ``actions`` [R, T] in one
+    launch (rl4co_tsp_nls): a 2-opt over the real distances, then ``n_perturbations`` rounds of a 2-opt over
+    ``perturb_distances`` followed by a 2-opt over the real distances, the best tour by reward kept per row.
+
+    ``locs`` [I, N, 2] and ``perturb_distances`` [I, N, N] (fp32, without the 1e9 diagonal, may be asymmetric) with
+    ``R % I == 0``: row ``r`` uses instance ``r % I`` (ant-major rows), nothing is tiled per ant. Returns
+    ``(actions, reward)``: the best int64 tours [R, T] and their fp32 rewards [R] (``TSPEnv.get_reward`` bit for bit);
+    with ``return_counts`` also ``scans`` int32 [R, 1 + 2 * n_perturbations] (scans per 2-opt) and ``accepted`` int32 [R]
+    (rounds that replaced the best tour). With ``err`` the sticky bits are OR-ed into the caller's word and nothing is
+    synchronised; without it the word is read back and an out-of-range index raises."""
+    if actions.dim() != 2:
+        raise ValueError(f"actions must be [R, T], got {tuple(actions.shape)}")
+    if actions.dtype != torch.int64:
+        raise TypeError(f"actions must be torch.int64, got {actions.dtype}")
+    rows, t = actions.shape
+    for name, src in (("locs", locs), ("perturb_distances", perturb_distances)):
+        if src.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, got {src.dtype}")
+    if locs.dim() != 3 or locs.shape[2] != 2:
+        raise ValueError(f"locs must be [I, N, 2], got {tuple(locs.shape)}")
+    inst, n, _ = locs.shape
+    if tuple(perturb_distances.shape) != (inst, n, n):
+        raise ValueError(f"perturb_distances must be [I, N, N] = {(inst, n, n)}, got {tuple(perturb_distances.shape)}")
+    if inst < 1 or rows % inst != 0:
+        raise ValueError(f"the {rows} tour rows must be a multiple of the {inst} instances (R % I == 0)")
+    if not 2 <= n <= 1024 or not 1 <= t <= 1024:
+        raise NotImplementedError(f"tsp_nls serves 2..1024 nodes and tours of 1..1024 positions, got N = {n}, T = {t}")
+    counts = dict(n_perturbations=n_perturbations, ls_max_iterations=ls_max_iterations,
+                  perturb_max_iterations=perturb_max_iterations)
+    for name, value in counts.items():
+        if not 0 <= int(value) < 2**30:
+            raise ValueError(f"{name} must be in [0, 2^30), got {value}")
+    actions = _dev(actions.contiguous(), torch.int64, "actions")
+    locs = _dev(locs.contiguous(), torch.float32, "locs")
+    perturb_distances = _dev(perturb_distances.contiguous(), torch.float32, "perturb_distances")
+    dev = actions.device
+    out = torch.empty_like(actions)
+    reward = torch.empty(rows, dtype=torch.float32, device=dev)
+    own = err is None
+    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
+    scans = torch.empty((rows, 1 + 2 * int(n_perturbations)), dtype=torch.int32, device=dev) if return_counts else None
+    accepted = torch.empty(rows, dtype=torch.int32, device=dev) if return_counts else None
+    a = _lib.TspNlsArgs()
+    a.R, a.n_instances, a.N, a.T = rows, inst, n, t
+    a.ls_max_iterations, a.perturb_max_iterations = int(ls_max_iterations), int(perturb_max_iterations)
+    a.n_perturbations, a.reserved0 = int(n_perturbations), 0
+    a.locs, a.perturb_distances, a.actions = _ptr(locs), _ptr(perturb_distances), _ptr(actions)
+    a.out_actions, a.out_reward, a.scans, a.accepted, a.err = _ptr(out), _ptr(reward), _ptr(scans), _ptr(accepted), _ptr(err)
+    st = _lib.lib().rl4co_tsp_nls(C.byref(a), _stream())
+    _lib.check(st, "rl4co_tsp_nls")
+    if own:
+        raise_if_error(err)
+    return (out, reward, scans, accepted) if return_counts else (out, reward)
+
+
 def aco_lds_nodes() -> int:
     """Largest node count at which the Ant System kernel keeps logits and pheromone in LDS (a host query)."""
     return int(_lib.lib().rl4co_aco_tsp_lds_nodes())

@@ -13,6 +13,10 @@ Next to the times: the mean best tour length after the last iteration, in float6
 ``--env cvrp`` times the CVRP search (csrc/aco_cvrp.hip) instead: 4096 x CVRP-100 from the environment's generator, 48 ants,
 10 iterations, ``multisample`` decoding (every ant starts at the depot), heuristic -log(distance). One leg, ``fused``: there
 is no earlier CVRP path to compare with. Writes profiles/aco_cvrp_bench.json unless ``--out`` says otherwise.
+
+``--nls`` times one iteration's neural-guided local search (csrc/tsp_nls.hip) instead: 1024 x TSP-100, 20 ants, 5
+perturbations of at most 5 scans; the fused launch against the composition of the 2-opt and reward kernels on the same
+tours (``main_nls``). Writes profiles/aco_nls_bench.json unless ``--out`` says otherwise.
 """
 import argparse
 import json
@@ -110,12 +114,15 @@ def main():
     ap.add_argument("--iterations", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--env", choices=("tsp", "cvrp"), default="tsp")
+    ap.add_argument("--nls", action="store_true", help="time the neural-guided local search instead (TSP)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("aco_bench needs the MI355X: a time taken anywhere else says nothing")
     dev = torch.device("cuda", 0)
     if a.env == "cvrp":
         return main_cvrp(a, dev)
+    if a.nls:
+        return main_nls(a, dev)
     g = torch.Generator().manual_seed(1234)
     locs = torch.rand(a.batch, a.num_loc, 2, generator=g).to(dev)
     dist = (locs[:, :, None] - locs[:, None, :]).norm(p=2, dim=-1)
@@ -174,6 +181,75 @@ def main_cvrp(a, dev):
                        case=f"cvrp{a.num_loc}x{a.batch}, {a.ants} ants, {a.iterations} iterations, multisample",
                        what="AntSystem.run end to end (host work included), HIP events around the call, synchronised",
                        rows=[row]), f, indent=1)
+
+
+def main_nls(a, dev):
+    """``--nls``: the neural-guided local search of ONE iteration at DeepACO's own shape (TSP-100, 20 ants, 5 perturbations
+    of at most 5 scans), on the tours a SAMPLE launch drew. Two legs on the same inputs, alternating round by round after one
+    warm-up round, min and median of ``--reps`` repeats, HIP events around the call (host work included), synchronised:
+      fused        AntSystem(use_nls=True).local_search: one rl4co_tsp_nls launch
+      composition  the same search written with the kernels merged before it: 1 + 2 P rl4co_tsp_two_opt launches over
+                   matrices tiled per ant, as many reward launches, compare / select glue in torch
+    The two must agree bit for bit (checked here before anything is written)."""
+    from rl4co_amd import _lib
+    from rl4co_amd import kernels as K
+
+    batch = a.batch if a.batch != 4096 else 1024  # (the TSP default of this script is sized for the sampling kernel)
+    ants, n, n_pert, pert_cap = 20, a.num_loc, 5, 5
+    g = torch.Generator().manual_seed(1234)
+    locs = torch.rand(batch, n, 2, generator=g).to(dev)
+    dist = (locs[:, :, None] - locs[:, None, :]).norm(p=2, dim=-1)
+    heu = -torch.log(dist + 1e9 * torch.eye(n, device=dev))
+    env = get_env("tsp", generator_params=dict(num_loc=n, device=dev), device=dev)
+    td = env.reset(TensorDict({"locs": locs}, batch_size=[batch]))
+    aco = AntSystem(heu, n_ants=ants, use_local_search=True, use_nls=True, n_perturbations=n_pert,
+                    perturbation_params={"max_iterations": pert_cap})
+    starts = aco._start_nodes(td, env, {})[None].contiguous()
+    sampled = K.aco_tsp(aco.pheromone, n_ants=ants, phases=_lib.ACO_SAMPLE, log_heuristic=heu, locs=locs, start_nodes=starts,
+                        philox_seed=1234)["actions"]
+    pert = aco.heuristic_dist
+    rows = sampled.shape[0]
+
+    def fused():
+        return aco.local_search(td, env, sampled, {})
+
+    def composition():  # one error word and one read-back, as the fused leg has; no validity check, as the fused leg has none
+        err = K.new_error_word(dev)
+        tiled = {"locs": locs.repeat(rows // batch, 1, 1)}
+        tiled_pert = pert.repeat(rows // batch, 1, 1)
+        cur = K.tsp_two_opt(sampled, locs=tiled["locs"], err=err)
+        best, best_r = cur.clone(), env.get_reward(tiled, cur, check_solution=False)
+        for _ in range(n_pert):
+            cur = K.tsp_two_opt(cur, distances=tiled_pert, max_iterations=pert_cap, err=err)
+            cur = K.tsp_two_opt(cur, locs=tiled["locs"], err=err)
+            r = env.get_reward(tiled, cur, check_solution=False)
+            win = r > best_r
+            best, best_r = torch.where(win[:, None], cur, best), torch.where(win, r, best_r)
+        K.raise_if_error(err)
+        return best, best_r
+
+    legs = [Leg("fused", fused), Leg("composition", composition)]
+    for it in range(a.reps + 1):  # one warm-up round; the legs alternate inside every round
+        for leg in legs:
+            leg.launch(keep=it >= 1)
+    (fa, fr), (ca, cr) = legs[0].tours, legs[1].tours
+    if not (torch.equal(fa, ca) and torch.equal(fr, cr)):
+        raise SystemExit("aco_bench --nls: the fused launch and the composition disagree; no time is recorded")
+    out_rows = []
+    for leg in legs:
+        t = sorted(leg.times)
+        out_rows.append(dict(leg=leg.kind, reps=len(t), median_ms=t[len(t) // 2], min_ms=t[0], max_ms=t[-1],
+                             mean_length_f64=float(-leg.tours[1].double().mean())))
+        print(json.dumps(out_rows[-1]), flush=True)
+    out = a.out or "profiles/aco_nls_bench.json"
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(dict(device=torch.cuda.get_device_name(0), when=time.strftime("%Y-%m-%d"),
+                       case=f"tsp{n}x{batch}, {ants} ants ({rows} tour rows), {n_pert} perturbations of <= {pert_cap} scans, "
+                            f"tours from one SAMPLE launch",
+                       what="one iteration's neural-guided local search (host work included), HIP events around the call, "
+                            "synchronised; the two legs agree bit for bit",
+                       rows=out_rows), f, indent=1)
 
 
 if __name__ == "__main__":
