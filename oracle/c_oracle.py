@@ -70,6 +70,8 @@ def lib() -> C.CDLL:
     h.oracle_uniform_f32.argtypes = [vp, C.c_int64, C.c_float, C.c_float, C.c_uint64, C.c_uint32, i, C.c_float]
     h.oracle_exp1_noise.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
     h.oracle_exp1_noise.restype = C.c_float
+    h.oracle_philox4x32.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]
+    h.oracle_philox4x32.restype = None
     return h
 
 

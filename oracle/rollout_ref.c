@@ -930,6 +930,8 @@ float oracle_tanhf(float x) { return rl4co_tanhf(x); }
 float oracle_exp1_noise(uint64_t seed, uint64_t step, uint32_t traj, uint32_t node) {
   return rl4co_exp1_noise(seed, step, traj, node);
 }
+/* the raw Philox4x32-10 block of the header, in place (tests/test_philox_cpu.py: the published known answers) */
+void oracle_philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) { rl4co_philox4x32(c, k0, k1); }
 
 /* array form (fn: 0 exp, 1 log, 2 tanh) so tests/test_math.py can sweep millions of arguments */
 int oracle_math_array(int fn, const float* x, int64_t n, float* y) {
