@@ -1,8 +1,9 @@
-// lds_tour_reward.h — minus the closed tour length of a TSP tour held in LDS, computed by one wave: tour_length.hip's
+// lds_tour_reward.h — minus the closed length of a tour held in LDS, computed by one wave: tour_length.hip's
 // arithmetic RESTATED in the same order (ATen's vector_norm over two elements, then SumKernel's 8-lane / 4-ILP / 4-level
 // cascade; lanes 0..7 of the wave play the SIMD lanes). The expression text is kept equal to that file's TourView::seg,
 // lane_row_sum and kernel epilogue — change both together. Bit-equal to TSPEnv.get_reward / rl4co_tour_length_f32 (tested
-// through aco_tsp.hip and tsp_nls.hip, the two kernels that include this).
+// through aco_tsp.hip, tsp_nls.hip and aco_cvrp.hip, the three kernels that include this; aco_cvrp.hip passes
+// [depot, actions] with n = W + 1: rl4co_tour_length_f32 with prepend_depot on the W-wide row).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,7 +1,8 @@
 """Ant System search for CVRP on the MI355X (csrc/aco_cvrp.hip, rl4co_amd/aco.py): the update against the records of the
 reference's own AntSystem with its CVRPEnv and the CPU restatement (tests/aco_cvrp_ref.py) with no tolerance, the per-step
 log-probs within STEP_TOL (4 x the reference's own fp32-vs-float64 deviation), mask and selection rule exactly in both entry
-modes and three capacity regimes, the W-wide reward bit for bit, fused against split launches on both sides of the LDS tier,
+modes and three capacity regimes, the W-wide reward bit for bit (also on rows of 520 and more segments, where the summation
+cascade has more than one level), fused against split launches on both sides of the LDS tier,
 the class surface with the reference's ragged final_actions, and the sticky error bits on inputs the kernel has to survive."""
 from functools import lru_cache
 
@@ -279,6 +280,31 @@ def test_both_sides_of_the_lds_tier_follow_the_restatement(side):
     assert torch.equal(phe.cpu(), state["pheromone"])
     assert torch.equal(out["final_reward"], state["final_reward"])
     assert torch.equal(out["final_actions"], torch.stack(state["final_actions"], 0))
+
+
+LONG_ROW_SEED = 2730  # (the locs of the two cases below; the N = 273 case failed on the kernel's earlier private reward)
+
+
+@pytest.mark.parametrize("n", [273, 261])
+def test_reward_of_long_rows_equals_tour_length(n):
+    """Rows of 520 and more segments (W + 1 >= 520, n >= 261: more than 64 eight-lane vectors, so SumKernel's cascade has
+    non-zero higher levels AND a non-zero tail when it folds): every demand is 0.6 of the capacity, so every customer forces
+    a depot return, every row is 2 C - 1 = W long and ends at a customer. Global-memory tier, one ant per wave, in-kernel
+    Philox. The kernel's reward is bit for bit rl4co_tour_length_f32 with the depot prepended and ATen's own sum."""
+    c, w = n - 1, R.width(n)
+    locs, heu, phe0 = _instance(1, n, LONG_ROW_SEED + n)
+    assert n > _K().aco_cvrp_lds_nodes() and (w + 1) // 8 > 64
+    out = _K().aco_cvrp(phe0.cuda(), n_ants=4, phases=SAMPLE, log_heuristic=heu.cuda(), locs=locs.cuda(),
+                        demand=torch.full((1, c), 0.6).cuda(), vehicle_capacity=torch.ones(1).cuda(), philox_seed=n)
+    assert out["actions"].shape == (4, w) and bool((out["lengths"] == w).all())
+    _valid(locs, torch.full((1, c), 0.6), torch.ones(1), out["actions"])
+    want = _K().tour_length(locs.cuda(), out["actions"], prepend_depot=True, negate=True)
+    host = R.reward_w(locs, out["actions"].cpu())
+    bits = out["reward"].cpu().view(torch.int32)  # (same sign, same binade: a difference of the words is one in ulps)
+    print(f"n {n}: reward {out['reward'].tolist()}, off tour_length by {(bits - want.cpu().view(torch.int32)).tolist()} ulps, "
+          f"off ATen on the CPU by {(bits - host.view(torch.int32)).tolist()} ulps")
+    assert torch.equal(out["reward"], want)
+    assert torch.equal(out["reward"].cpu(), host)
 
 
 # ---- 6. the class surface --------------------------------------------------------------------------------------------------
