@@ -48,8 +48,10 @@ extern "C" {
  *      RL4CO_EBIT_TOUR_INDEX.
  *  18: rl4co_aco_tsp / rl4co_aco_tsp_lds_nodes (Ant System search on a heatmap, rl4co_aco_tsp_args, RL4CO_ACO_*).
  *  19: rl4co_aco_cvrp / rl4co_aco_cvrp_lds_nodes (the same search for CVRP, rl4co_aco_cvrp_args).
- *  20: rl4co_tsp_nls / rl4co_tsp_nls_lds_nodes (neural-guided local search for TSP, rl4co_tsp_nls_args). */
-#define RL4CO_ABI_VERSION 20
+ *  20: rl4co_tsp_nls / rl4co_tsp_nls_lds_nodes (neural-guided local search for TSP, rl4co_tsp_nls_args).
+ *  21: rl4co_nargnn_heatmap / rl4co_nargnn_lds_nodes / rl4co_nargnn_scratch_bytes (DeepACO's heatmap encoder,
+ *      rl4co_nargnn_args). */
+#define RL4CO_ABI_VERSION 21
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -767,6 +769,62 @@ typedef struct rl4co_tsp_nls_args {
 int rl4co_tsp_nls(const rl4co_tsp_nls_args* args, void* stream);
 /* Largest N whose distance matrix rl4co_tsp_nls keeps in LDS (the kernel's LDS budget, tsp_nls.hip header). */
 int rl4co_tsp_nls_lds_nodes(void);
+
+/* --------------------------------------------------------------------------
+ * DeepACO's heatmap encoder for TSP (NARGNNEncoder in inference: models/zoo/nargnn/encoder.py, the anisotropic edge-gated
+ * GNN of models/nn/graph/gnn.py and the EdgeHeatmapGenerator MLP) as ONE launch in fp32, one workgroup per instance with a
+ * grid-stride loop over the instances (nargnn.hip). The TSP graph is regular: node u has exactly K out-edges (u, v) to
+ * neighbors[b][u][0 .. K-1], so the edge state is a dense [N, K, D] array, D = 64, and node u pools over its own K rows.
+ *   x = silu(init(locs));  w = silu(edge_embed(edge_cost))
+ *   L times, both lines reading the layer's incoming x and w:
+ *     x <- x + silu(bn_v(v_lin1(x)[u] + mean_k(sigmoid(w[u][k]) * v_lin2(x)[v])))
+ *     w <- w + silu(bn_e(e_lin(w) + v_lin3(x)[u] + v_lin4(x)[v]))
+ *   h = sigmoid(out(silu(lin_{H-1}(... silu(lin_1(w))))))
+ *   heatmap[b][u][v] = log(h + small_value) at the K neighbours of u, fill_value everywhere else (diagonal included).
+ * silu(y) = y / (1 + exp(-y)); the batch norms are eval-mode, folded by the host into a per-channel scale and shift
+ * (y * scale + shift). The 64-long dot products run on v_mfma_f32_16x16x4_f32 (the hardware's summation order).
+ * Three tiers by where the state lives (nargnn.hip header): up to rl4co_nargnn_lds_nodes(K) nodes the edge state and the
+ * two gathered node planes stay in LDS; above, the edge state lives in `scratch`; above 300 nodes every plane does.
+ * `scratch` holds n_workgroups * rl4co_nargnn_scratch_bytes(N, K) bytes, 16-byte aligned.
+ * A neighbour index outside [0, N) sets RL4CO_EBIT_TOUR_INDEX; that instance's outputs are left untouched.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_nargnn_args {
+  int32_t B;                /* instances, >= 1                                              */
+  int32_t N;                /* nodes, 2 .. 1024                                             */
+  int32_t K;                /* out-edges per node, 1 .. min(N - 1, 256)                     */
+  int32_t D;                /* embedding width: 64                                          */
+  int32_t L;                /* GNN layers, >= 0                                             */
+  int32_t H;                /* heatmap MLP layers with the output layer, >= 1               */
+  int32_t n_workgroups;     /* grid, 1 .. B                                                 */
+  int32_t reserved0;        /* 0                                                            */
+  float small_value;        /* added to h before the log                                    */
+  float fill_value;         /* log(small_value) as the host computed it                     */
+  const float* locs;        /* [B,N,2]                                                      */
+  const int32_t* neighbors; /* [B,N,K]                                                      */
+  const float* edge_cost;   /* [B,N,K]                                                      */
+  const float* init_w;      /* [D,2]                                                        */
+  const float* init_b;      /* [D]                                                          */
+  const float* edge_w;      /* [D] (Linear(1, D))                                           */
+  const float* edge_b;      /* [D]                                                          */
+  const float* lin_w;       /* [L,5,D,D]: v_lin1 .. v_lin4, e_lin; NULL allowed when L == 0  */
+  const float* lin_b;       /* [L,5,D]                                                      */
+  const float* bn;          /* [L,2,2,D]: (v_bn, e_bn) x (scale, shift)                     */
+  const float* mlp_w;       /* [H-1,D,D]; NULL allowed when H == 1                          */
+  const float* mlp_b;       /* [H-1,D] or NULL (linear_bias = False)                        */
+  const float* out_w;       /* [D]                                                          */
+  const float* out_b;       /* [1] or NULL                                                  */
+  float* scratch;           /* n_workgroups * rl4co_nargnn_scratch_bytes(N, K) bytes        */
+  int64_t scratch_bytes;
+  float* heatmap;           /* [B,N,N] out                                                  */
+  float* node_embed;        /* [B,N,D] out: init(locs), before the activation               */
+  int32_t* err;             /* sticky error bits                                            */
+} rl4co_nargnn_args;
+
+int rl4co_nargnn_heatmap(const rl4co_nargnn_args* args, void* stream);
+/* Largest N at which rl4co_nargnn_heatmap keeps the edge state of K out-edges per node in LDS (nargnn.hip header). */
+int rl4co_nargnn_lds_nodes(int K);
+/* Bytes of `scratch` one workgroup needs at this shape (0 < result; the tier is the kernel's own choice). */
+int64_t rl4co_nargnn_scratch_bytes(int N, int K);
 
 /* --------------------------------------------------------------------------
  * a11-a13  fused encoder + decoder-cache fold on the matrix cores (inference rollouts).

@@ -1,0 +1,256 @@
+"""DeepACO's front end: the reference's ``NARGNNEncoder`` (models/zoo/nargnn/encoder.py: TSP init and edge embeddings, the
+anisotropic edge-gated GNN of models/nn/graph/gnn.py, the ``EdgeHeatmapGenerator`` MLP) in inference as ONE kernel launch
+(``rl4co_nargnn_heatmap``, csrc/nargnn.hip), and the val / test path of ``DeepACOPolicy.forward``
+(models/zoo/deepaco/policy.py:122-127, 165-184) on top of it and of :class:`rl4co_amd.aco.AntSystem`: instance -> heatmap ->
+ants -> tours, all on the device.
+
+The modules carry the reference's ``state_dict`` keys (``graph_network.layers.{i}.v_bn.module.*`` is how PyG's
+``BatchNorm`` wraps ``BatchNorm1d``), so a reference checkpoint loads with ``load_state_dict(strict=True)``. The neighbour
+lists are the reference's own selection (distance matrix, ``+inf`` on the diagonal, ``torch.topk(largest=False,
+sorted=False)``) taken for the whole batch on the device; the eval-mode batch norms are folded into a per-channel scale and
+shift (in float64, rounded once). Training, CPU tensors, other environments, activations, aggregations and widths are
+refused with ``NotImplementedError``: there is no torch fall-back."""
+from __future__ import annotations
+
+from functools import partial
+
+import torch
+from torch import Tensor, nn
+
+from . import kernels as K
+from .aco import AntSystem
+
+SMALL_VALUE = 1e-12  # encoder.py:81-82: the fp32 heatmap's guard against log(0)
+
+
+class _TSPInitEmbedding(nn.Module):
+    """env_embeddings/init.py:55-68"""
+
+    def __init__(self, embed_dim: int, linear_bias: bool = True):
+        super().__init__()
+        self.init_embed = nn.Linear(2, embed_dim, linear_bias)
+
+
+class _TSPEdgeEmbedding(nn.Module):
+    """env_embeddings/edge.py:53-116 (sparsify=True): the parameters and the rule for k."""
+
+    def __init__(self, embed_dim: int, linear_bias: bool = True, k_sparse: int | None = None):
+        super().__init__()
+        self.k_sparse = k_sparse
+        self.edge_embed = nn.Linear(1, embed_dim, linear_bias)
+
+    def num_neighbors(self, n: int) -> int:
+        k = max(n // 5, 10) if self.k_sparse is None else int(self.k_sparse)
+        return min(k, n - 1)  # ops.py:183
+
+
+class _BatchNorm(nn.Module):
+    """torch_geometric.nn.BatchNorm: a ``BatchNorm1d`` under the attribute ``module``."""
+
+    def __init__(self, units: int):
+        super().__init__()
+        self.module = nn.BatchNorm1d(units)
+
+
+class _GNNLayer(nn.Module):
+    """gnn.py:14-43"""
+
+    def __init__(self, units: int):
+        super().__init__()
+        self.v_lin1 = nn.Linear(units, units)
+        self.v_lin2 = nn.Linear(units, units)
+        self.v_lin3 = nn.Linear(units, units)
+        self.v_lin4 = nn.Linear(units, units)
+        self.v_bn = _BatchNorm(units)
+        self.e_lin = nn.Linear(units, units)
+        self.e_bn = _BatchNorm(units)
+
+
+class _GNNEncoder(nn.Module):
+    """gnn.py:64-82"""
+
+    def __init__(self, num_layers: int, embed_dim: int):
+        super().__init__()
+        self.layers = nn.ModuleList([_GNNLayer(embed_dim) for _ in range(num_layers)])
+
+
+class _EdgeHeatmapGenerator(nn.Module):
+    """encoder.py:20-48"""
+
+    def __init__(self, embed_dim: int, num_layers: int, linear_bias: bool = True):
+        super().__init__()
+        self.linears = nn.ModuleList([nn.Linear(embed_dim, embed_dim, bias=linear_bias) for _ in range(num_layers - 1)])
+        self.output = nn.Linear(embed_dim, 1, bias=linear_bias)
+
+
+def _fold_batch_norm(bn: nn.BatchNorm1d) -> Tensor:
+    """Eval-mode batch norm as (scale, shift) [2, D]: scale = gamma / sqrt(running_var + eps), shift = beta - running_mean
+    * scale, in float64 and rounded once."""
+    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    shift = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+    return torch.stack((scale, shift), 0).float()
+
+
+class NARGNNEncoder(nn.Module):
+    """encoder.py:96-193 for TSP in inference: ``forward(td)`` returns ``(heatmap_logits [B, N, N], node_embed [B, N, D])``."""
+
+    def __init__(self, embed_dim: int = 64, env_name: str = "tsp", init_embedding: nn.Module | None = None,
+                 edge_embedding: nn.Module | None = None, graph_network: nn.Module | None = None,
+                 heatmap_generator: nn.Module | None = None, num_layers_heatmap_generator: int = 5,
+                 num_layers_graph_encoder: int = 15, act_fn="silu", agg_fn="mean", linear_bias: bool = True,
+                 k_sparse: int | None = None):
+        super().__init__()
+        self.env_name = env_name
+        self.embed_dim = embed_dim
+        self.act_fn, self.agg_fn = act_fn, agg_fn
+        given = dict(init_embedding=init_embedding, edge_embedding=edge_embedding, graph_network=graph_network,
+                     heatmap_generator=heatmap_generator)
+        self.custom = [name for name, module in given.items() if module is not None]
+        self.init_embedding = _TSPInitEmbedding(embed_dim) if init_embedding is None else init_embedding
+        self.edge_embedding = _TSPEdgeEmbedding(embed_dim, k_sparse=k_sparse) if edge_embedding is None else edge_embedding
+        self.graph_network = (_GNNEncoder(num_layers_graph_encoder, embed_dim) if graph_network is None else graph_network)
+        self.heatmap_generator = (_EdgeHeatmapGenerator(embed_dim, num_layers_heatmap_generator, linear_bias)
+                                  if heatmap_generator is None else heatmap_generator)
+        self._packed: tuple | None = None  # (key, tensors): the kernel's view of the parameters, rebuilt when one changes
+
+    # ---- what the kernel serves -------------------------------------------------------------------------------------------
+    def _check(self, locs: Tensor) -> None:
+        if self.training:
+            raise NotImplementedError("NARGNNEncoder serves inference only: a training-mode batch norm needs the statistics "
+                                      "of the whole batch (call .eval())")
+        if self.custom:
+            raise NotImplementedError(f"NARGNNEncoder serves its own sub-modules only, got a custom {', '.join(self.custom)}")
+        if self.env_name != "tsp":
+            raise NotImplementedError(f"NARGNNEncoder serves the tsp environment only (the regular k-nearest graph), got "
+                                      f"{self.env_name!r}")
+        if self.act_fn != "silu":
+            raise NotImplementedError(f"NARGNNEncoder serves act_fn='silu' only, got {self.act_fn!r}")
+        if self.agg_fn != "mean":
+            raise NotImplementedError(f"NARGNNEncoder serves agg_fn='mean' only, got {self.agg_fn!r}")
+        if self.embed_dim != 64:
+            raise NotImplementedError(f"NARGNNEncoder serves embed_dim=64 only, got {self.embed_dim}")
+        if not locs.is_cuda:
+            raise NotImplementedError(f"NARGNNEncoder runs inside the MI355X kernel (rl4co_nargnn_heatmap) only: td['locs'] "
+                                      f"on {locs.device}")
+
+    def packed_parameters(self, device) -> dict:
+        """The parameters as the kernel reads them (stacked per layer, batch norms folded), cached until one changes."""
+        tensors = list(self.parameters()) + list(self.buffers())
+        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in tensors)
+        if self._packed is not None and self._packed[0] == key:
+            return self._packed[1]
+
+        def f32(t):
+            return None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+        layers = list(self.graph_network.layers)
+        gen = self.heatmap_generator
+        p = dict(init_w=f32(self.init_embedding.init_embed.weight), init_b=f32(self.init_embedding.init_embed.bias),
+                 edge_w=f32(self.edge_embedding.edge_embed.weight), edge_b=f32(self.edge_embedding.edge_embed.bias),
+                 lin_w=None, lin_b=None, bn=None, mlp_w=None, mlp_b=None, out_w=f32(gen.output.weight), out_b=f32(gen.output.bias))
+        if layers:
+            lins = [[getattr(layer, n) for n in ("v_lin1", "v_lin2", "v_lin3", "v_lin4", "e_lin")] for layer in layers]
+            p["lin_w"] = f32(torch.stack([torch.stack([m.weight for m in row], 0) for row in lins], 0))
+            p["lin_b"] = f32(torch.stack([torch.stack([m.bias for m in row], 0) for row in lins], 0))
+            p["bn"] = f32(torch.stack([torch.stack((_fold_batch_norm(layer.v_bn.module), _fold_batch_norm(layer.e_bn.module)), 0)
+                                       for layer in layers], 0))
+        if len(gen.linears):
+            p["mlp_w"] = f32(torch.stack([m.weight for m in gen.linears], 0))
+            if gen.linears[0].bias is not None:
+                p["mlp_b"] = f32(torch.stack([m.bias for m in gen.linears], 0))
+        self._packed = (key, p)
+        return p
+
+    def neighbors(self, locs: Tensor) -> tuple[Tensor, Tensor]:
+        """edge.py:88-104 and ops.py:169-199 for the whole batch: (neighbors [B, N, K] int32, edge_cost [B, N, K])."""
+        n = locs.shape[1]
+        cost = (locs[..., :, None, :] - locs[..., None, :, :]).norm(p=2, dim=-1)
+        cost.diagonal(dim1=1, dim2=2).fill_(torch.inf)
+        values, indices = torch.topk(cost, k=self.edge_embedding.num_neighbors(n), dim=-1, largest=False, sorted=False)
+        return indices.to(torch.int32).contiguous(), values.contiguous()
+
+    @torch.no_grad()
+    def forward(self, td):
+        locs = td["locs"]
+        self._check(locs)
+        locs = locs.detach().to(torch.float32).contiguous()
+        neighbors, cost = self.neighbors(locs)
+        return K.nargnn_heatmap(locs, neighbors, cost, small_value=SMALL_VALUE, **self.packed_parameters(locs.device))
+
+
+def _merge_with_defaults(value, **defaults) -> dict:
+    """utils/utils.py merge_with_defaults: an int for every phase, a dict over the defaults, None for the defaults."""
+    if value is None:
+        return dict(defaults)
+    if isinstance(value, dict):
+        return {**defaults, **value}
+    return {key: value for key in defaults}
+
+
+class DeepACOPolicy(nn.Module):
+    """policy.py:22-184, the val / test path: encoder, ``heatmap / temperature``, ``AntSystem.run``. The constructor takes
+    the reference's arguments; ``phase="train"`` (the constructive training path), ``top_k`` / ``top_p`` above 0 and an
+    explicit ``k_sparse`` on the policy (the reference then hands ``top_k`` to the sampler) are refused."""
+
+    def __init__(self, encoder: nn.Module | None = None, env_name: str = "tsp", temperature: float = 1.0, top_p: float = 0.0,
+                 top_k: int = 0, aco_class: type | None = None, aco_kwargs: dict = {}, train_with_local_search: bool = False,
+                 n_ants: int | dict | None = None, n_iterations: int | dict | None = None, start_node: int | None = None,
+                 multistart: bool = False, k_sparse: int | None = None, **encoder_kwargs):
+        super().__init__()
+        if k_sparse is not None:
+            raise NotImplementedError("DeepACOPolicy(k_sparse=...) makes the reference pass top_k to the sampler, which the "
+                                      "Ant System kernel does not serve; set k_sparse on the encoder alone")
+        if top_k > 0 or top_p > 0:
+            raise NotImplementedError(f"top_k / top_p filtering of the heatmap is not served (top_k={top_k}, top_p={top_p})")
+        if encoder is None:
+            encoder = NARGNNEncoder(env_name=env_name, **encoder_kwargs)
+        self.encoder = encoder
+        self.env_name = env_name
+        self.temperature = temperature
+        self.top_p, self.top_k = top_p, top_k
+        self.decode_type = "multistart_sampling" if env_name == "tsp" or multistart else "sampling"
+        self.default_decoding_kwargs: dict = {"select_best": False}
+        if "multistart" in self.decode_type:
+            self.default_decoding_kwargs.update(
+                {"multistart": True, "select_start_nodes_fn": partial(self.select_start_node_fn, start_node=start_node)})
+        else:
+            self.default_decoding_kwargs.update({"multisample": True})
+        self.aco_class = AntSystem if aco_class is None else aco_class
+        self.aco_kwargs = aco_kwargs
+        self.train_with_local_search = train_with_local_search
+        if train_with_local_search:
+            assert self.aco_kwargs.get("use_local_search", False)
+        self.n_ants = _merge_with_defaults(n_ants, train=30, val=48, test=48)
+        self.n_iterations = _merge_with_defaults(n_iterations, train=1, val=5, test=10)
+        self.last_aco = None  # the search object of the last forward (its log_heuristic, pheromone, last_iterations)
+
+    @staticmethod
+    def select_start_node_fn(td, env, num_starts: int, start_node: int | None = None):
+        """policy.py:97-106"""
+        mask = td["action_mask"]
+        if env.name == "tsp" and start_node is not None:
+            return start_node * torch.ones(mask.shape[0] * num_starts, dtype=torch.long, device=mask.device)
+        return torch.multinomial(mask.float(), num_starts, replacement=True).view(-1)
+
+    def forward(self, td_initial, env=None, phase: str = "train", return_actions: bool = True, **decoding_kwargs):
+        if phase not in ("val", "test"):
+            raise NotImplementedError(f"DeepACOPolicy serves phase='val' and phase='test' (the Ant System search); "
+                                      f"phase={phase!r} is the constructive training path")
+        n_ants = self.n_ants[phase]
+        decoding_kwargs.update(self.default_decoding_kwargs)
+        decoding_kwargs.update({"num_starts": n_ants} if "multistart" in self.decode_type else {"num_samples": n_ants})
+        if env is None or isinstance(env, str):
+            from .envs import get_env
+
+            env = get_env(self.env_name if env is None else env)
+        heatmap, _ = self.encoder(td_initial)
+        heatmap /= self.temperature
+        aco = self.aco_class(heatmap, n_ants=n_ants, **self.aco_kwargs)
+        self.last_aco = aco
+        n_iterations = self.n_iterations[phase]
+        actions, iter_rewards = aco.run(td_initial, env, n_iterations, decoding_kwargs)
+        out = {"reward": iter_rewards[n_iterations - 1]}
+        out.update({f"reward_{i:03d}": iter_rewards[i] for i in range(n_iterations)})
+        if return_actions:
+            out["actions"] = actions
+        return out
