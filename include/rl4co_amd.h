@@ -50,8 +50,9 @@ extern "C" {
  *  19: rl4co_aco_cvrp / rl4co_aco_cvrp_lds_nodes (the same search for CVRP, rl4co_aco_cvrp_args).
  *  20: rl4co_tsp_nls / rl4co_tsp_nls_lds_nodes (neural-guided local search for TSP, rl4co_tsp_nls_args).
  *  21: rl4co_nargnn_heatmap / rl4co_nargnn_lds_nodes / rl4co_nargnn_scratch_bytes (DeepACO's heatmap encoder,
- *      rl4co_nargnn_args). */
-#define RL4CO_ABI_VERSION 21
+ *      rl4co_nargnn_args).
+ *  22: rl4co_aco_prize / rl4co_aco_prize_lds_nodes (the Ant System search for OP and PCTSP, rl4co_aco_prize_args). */
+#define RL4CO_ABI_VERSION 22
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -724,6 +725,83 @@ typedef struct rl4co_aco_cvrp_args {
 int rl4co_aco_cvrp(const rl4co_aco_cvrp_args* args, void* stream);
 /* Largest N at which rl4co_aco_cvrp keeps the logits and the pheromone in LDS (the kernel's LDS budget, aco_cvrp.hip header). */
 int rl4co_aco_cvrp_lds_nodes(void);
+
+/* --------------------------------------------------------------------------
+ * Ant System search on a heatmap for the prize problems, OP and PCTSP (the same reference class with OPEnv / PCTSPEnv), as
+ * ONE launch (aco_prize.hip). env is RL4CO_ENV_OP or RL4CO_ENV_PCTSP (SPCTSP is PCTSP with the stochastic prize passed as
+ * `prize`). N is the heatmap side with the depot as node 0, rows = n_ants * B ant-major as in rl4co_aco_tsp, and a row is
+ * W = N wide: at most N - 1 customers, then the depot. One workgroup serves instances b, b + n_workgroups, ...
+ * (n_workgroups == 0: one workgroup per instance); the results do not depend on n_workgroups.
+ *   SAMPLE  L as in rl4co_aco_tsp. Every ant starts at the depot with nothing visited and samples its first action from row
+ *           0 of L. A distance is d(i, j) = sqrtf(fmaf(dy, dy, dx * dx)), dx = x_j - x_i, dy = y_j - y_i.
+ *           OP (op/env.py:67-154): state cur, visited (the depot included), tour_length, the step index; customer j is
+ *           infeasible when visited, when the depot has been visited, or when tour_length + d(cur, j) > max_length[j]
+ *           (`max_length` is the environment's per-node table: the budget minus the node's distance to the depot minus
+ *           1e-6); the depot is always feasible; a step adds d(cur, a) to tour_length; done = (a == 0 and t > 0), so a row
+ *           may take the depot at step 0 and again at step 1.
+ *           PCTSP (pctsp/env.py:62-144): state cur, visited, cur_total_prize, the step index; customer j is infeasible
+ *           when visited or when the depot has been visited; the depot is infeasible while cur_total_prize < 1 and an
+ *           unvisited customer remains; a step adds prize[a]; done = (t > 0 and a == 0).
+ *           A step is rl4co_aco_tsp's over the feasible nodes; ln_noise is [iterations, W, rows, N] (step t reads
+ *           [it][t][row]), the Philox step counter is philox_offset + it * W + t. An ant stops at done: lengths[row]
+ *           counts its actions, the rest of the row is 0 (log-probs 0).
+ *   REWARD  at the fixed width W, every sum in rl4co_tour_length_f32's order (lds_tour_reward.h: 8 lanes, 4 accumulators,
+ *           the 4-level cascade) over the W-wide zero-filled row. OP: the sum of prize[a_t], t = 0 .. W - 1. PCTSP:
+ *           S - (len + P) with S the sum of penalty[a_t] over the row, len the closed length of [depot, a_0 .. a_{W-1}]
+ *           (rl4co_tour_length_f32 with prepend_depot) and P the sum of penalty[1 .. N - 1].
+ *   UPDATE  rl4co_aco_cvrp's ((0, 0) edges skipped, final_iteration, rows of any width T >= 2 with UPDATE alone).
+ * phases, the one-phase-alone rule, the LDS tier (rl4co_aco_prize_lds_nodes(env), logits_scratch above it) and the sticky
+ * bits are rl4co_aco_cvrp's; RL4CO_EBIT_TOUR_INDEX covers a forced / UPDATE-only action outside [0, N): that instance is
+ * left untouched.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_aco_prize_args {
+  int32_t B;                /* instances, >= 1                                              */
+  int32_t N;                /* nodes with the depot, 2 .. 1024                              */
+  int32_t n_ants;           /* >= 1; n_ants * B <= 2^31 - 1                                 */
+  int32_t iterations;       /* >= 1; 1 unless both phases are set                           */
+  int32_t phases;           /* RL4CO_ACO_SAMPLE | RL4CO_ACO_UPDATE                          */
+  int32_t has_best;         /* 0: final_reward / final_actions hold nothing yet             */
+  int32_t T;                /* width of actions / final_actions: W = N with SAMPLE, else >= 2 */
+  int32_t iteration_base;   /* added to the iteration index written to final_iteration      */
+  int32_t env;              /* RL4CO_ENV_OP or RL4CO_ENV_PCTSP                              */
+  int32_t n_workgroups;     /* 0: B; else 1 .. B workgroups striding over the instances     */
+  float alpha;
+  float beta;
+  float decay;
+  float Q;
+  float temperature;        /* > 0                                                          */
+  int32_t reserved0;        /* 0                                                            */
+  uint64_t philox_seed;     /* in-kernel noise when ln_noise == NULL                        */
+  uint64_t philox_offset;
+  const uint64_t* philox_seed_dev; /* optional device word XOR-ed into philox_seed          */
+  const float* log_heuristic;   /* [B,N,N] (SAMPLE)                                         */
+  float* pheromone;             /* [B,N,N] in / out                                         */
+  const float* locs;            /* [B,N,2], depot first (SAMPLE)                            */
+  const float* prize;           /* [B,N], 0 at the depot (SAMPLE)                           */
+  const float* penalty;         /* [B,N], 0 at the depot (SAMPLE, PCTSP)                    */
+  const float* max_length;      /* [B,N] per-node entry limits (SAMPLE, OP)                 */
+  const float* ln_noise;        /* [iterations,W,rows,N] or NULL                            */
+  const int64_t* forced_actions;/* [rows,W] or NULL (SAMPLE, iterations == 1)               */
+  float* logits_scratch;        /* [B,N,N]; required above rl4co_aco_prize_lds_nodes(env)   */
+  int64_t* actions;             /* [rows,T] last iteration's rows (UPDATE alone: input)     */
+  int32_t* lengths;             /* [rows] actions up to and including done (SAMPLE)         */
+  float* reward;                /* [rows] last iteration's rewards (UPDATE alone: input)    */
+  float* logps;                 /* [rows,W] or NULL                                         */
+  float* all_logps;             /* [rows,W,N] or NULL                                       */
+  int64_t* iter_actions;        /* [iterations,rows,W] or NULL                              */
+  int32_t* iter_lengths;        /* [iterations,rows] or NULL                                */
+  float* iter_reward;           /* [iterations,rows] or NULL                                */
+  float* final_reward;          /* [B] in / out (UPDATE)                                    */
+  int64_t* final_actions;       /* [B,T] in / out (UPDATE)                                  */
+  int32_t* final_iteration;     /* [B] or NULL: written where the record is replaced        */
+  float* final_reward_cache;    /* [iterations,B] or NULL                                   */
+  int32_t* err;                 /* sticky error bits                                        */
+} rl4co_aco_prize_args;
+
+int rl4co_aco_prize(const rl4co_aco_prize_args* args, void* stream);
+/* Largest N at which rl4co_aco_prize keeps the logits and the pheromone in LDS for `env` (aco_prize.hip header); -1 for an
+ * environment it does not serve. */
+int rl4co_aco_prize_lds_nodes(int env);
 
 /* --------------------------------------------------------------------------
  * Neural-guided local search for TSP (DeepACO's NLS: AntSystem.local_search with use_nls, antsystem.py:173-230) as ONE

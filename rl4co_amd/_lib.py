@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 21  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 22  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -171,6 +171,22 @@ class AcoCvrpArgs(C.Structure):
     ]
 
 
+class AcoPrizeArgs(C.Structure):
+    """Mirror of ``struct rl4co_aco_prize_args`` (field order and types must match the header)."""
+
+    _fields_ = [
+        ("B", _i32), ("N", _i32), ("n_ants", _i32), ("iterations", _i32), ("phases", _i32), ("has_best", _i32),
+        ("T", _i32), ("iteration_base", _i32), ("env", _i32), ("n_workgroups", _i32),
+        ("alpha", _f32), ("beta", _f32), ("decay", _f32), ("Q", _f32), ("temperature", _f32), ("reserved0", _i32),
+        ("philox_seed", C.c_uint64), ("philox_offset", C.c_uint64), ("philox_seed_dev", _vp),
+        ("log_heuristic", _vp), ("pheromone", _vp), ("locs", _vp), ("prize", _vp), ("penalty", _vp), ("max_length", _vp),
+        ("ln_noise", _vp), ("forced_actions", _vp), ("logits_scratch", _vp), ("actions", _vp),
+        ("lengths", _vp), ("reward", _vp), ("logps", _vp), ("all_logps", _vp), ("iter_actions", _vp), ("iter_lengths", _vp),
+        ("iter_reward", _vp), ("final_reward", _vp), ("final_actions", _vp), ("final_iteration", _vp),
+        ("final_reward_cache", _vp), ("err", _vp),
+    ]
+
+
 class EnvReplayArgs(C.Structure):
     """Mirror of ``struct rl4co_env_replay_args``."""
 
@@ -275,6 +291,8 @@ SYMBOLS = {
     "rl4co_aco_tsp_lds_nodes": (C.c_int, []),
     "rl4co_aco_cvrp": (C.c_int, [C.POINTER(AcoCvrpArgs), _vp]),
     "rl4co_aco_cvrp_lds_nodes": (C.c_int, []),
+    "rl4co_aco_prize": (C.c_int, [C.POINTER(AcoPrizeArgs), _vp]),
+    "rl4co_aco_prize_lds_nodes": (C.c_int, [C.c_int]),
     "rl4co_tsp_nls": (C.c_int, [C.POINTER(TspNlsArgs), _vp]),
     "rl4co_tsp_nls_lds_nodes": (C.c_int, []),
     "rl4co_nargnn_heatmap": (C.c_int, [C.POINTER(NargnnArgs), _vp]),

@@ -19,7 +19,13 @@ default: every ant starts at the depot) or ``multistart`` with ``num_starts == n
 is the external HGS library, so ``use_local_search`` and with it ``use_nls`` stay refused). The kernel's rows are
 ``W = max(C + 1, 2 C - 1)`` wide and zero-filled after each row's length, and every reward is the one of that W-wide row (csrc/aco_cvrp.hip states why). ``final_actions`` is the reference's
 ragged list: entry ``b`` has the width the reference's batch had in the iteration that last replaced it, the longest row of
-that iteration, which takes one small read-back (with the error word) after the launch."""
+that iteration, which takes one small read-back (with the error word) after the launch.
+
+OP and PCTSP (``env.name`` "op", "pctsp" or "spctsp"; ``rl4co_aco_prize``, csrc/aco_prize.hip): ``multisample`` with
+``num_samples == n_ants`` only, no local search (the reference's destroy-and-repair search is not served) and no
+``multistart``. ``td`` is the environment's reset state: ``prize`` and ``max_length`` (OP), ``real_prize`` and ``penalty``
+(PCTSP; ``real_prize`` is the stochastic prize under ``SPCTSPEnv``). Rows are ``W = n`` wide and zero-filled after each
+row's length, the reward is ``env.get_reward`` on that W-wide row, ``final_actions`` is the ragged list as for CVRP."""
 from __future__ import annotations
 
 from functools import cached_property
@@ -32,6 +38,8 @@ from . import kernels as K
 
 _SERVED_KWARGS = ("multistart", "num_starts", "select_best", "select_start_nodes_fn", "temperature")
 _SERVED_KWARGS_CVRP = _SERVED_KWARGS + ("multisample", "num_samples")
+_SERVED_KWARGS_PRIZE = ("multisample", "num_samples", "select_best", "temperature")
+_PRIZE_ENVS = ("op", "pctsp", "spctsp")  # rl4co_aco_prize; spctsp is pctsp with the stochastic prize in td["real_prize"]
 
 
 class AntSystem:
@@ -82,9 +90,11 @@ class AntSystem:
     def _check(self, td, env, decoding_kwargs: dict) -> float:
         if getattr(env, "name", None) == "cvrp":
             return self._check_cvrp(td, decoding_kwargs)
+        if getattr(env, "name", None) in _PRIZE_ENVS:
+            return self._check_prize(td, env.name, decoding_kwargs)
         if getattr(env, "name", None) != "tsp":
-            raise NotImplementedError(f"AntSystem serves the tsp and cvrp environments only (rl4co_aco_tsp, rl4co_aco_cvrp), "
-                                      f"got {getattr(env, 'name', env)!r}")
+            raise NotImplementedError(f"AntSystem serves the tsp, cvrp, op, pctsp and spctsp environments only (rl4co_aco_tsp, "
+                                      f"rl4co_aco_cvrp, rl4co_aco_prize), got {getattr(env, 'name', env)!r}")
         for key in decoding_kwargs:
             if key not in _SERVED_KWARGS:
                 raise NotImplementedError(f"decoding_kwargs[{key!r}] is not served by the Ant System kernel")
@@ -120,6 +130,28 @@ class AntSystem:
                 raise NotImplementedError(f"AntSystem runs inside the MI355X kernel (rl4co_aco_cvrp) only: {name} on {t.device}")
         return float(decoding_kwargs.get("temperature", 1.0))
 
+    def _check_prize(self, td, name: str, decoding_kwargs: dict) -> float:
+        if self.use_local_search:
+            raise NotImplementedError(f"use_local_search is not served for {name}: the reference's destroy-and-repair local "
+                                      f"search is not part of the Ant System kernel")
+        if decoding_kwargs.get("multistart", False):
+            raise NotImplementedError(f"decoding_kwargs['multistart'] is not served for {name}: every ant starts at the depot "
+                                      f"(multisample)")
+        for key in decoding_kwargs:
+            if key not in _SERVED_KWARGS_PRIZE and key != "multistart":
+                raise NotImplementedError(f"decoding_kwargs[{key!r}] is not served by the Ant System kernel for {name}")
+        if not decoding_kwargs.get("multisample", False):
+            raise NotImplementedError(f"decoding_kwargs['multisample'] must be True for {name}")
+        if decoding_kwargs.get("num_samples", self.n_ants) != self.n_ants:
+            raise NotImplementedError(f"decoding_kwargs['num_samples'] must equal n_ants = {self.n_ants}")
+        if decoding_kwargs.get("select_best", False):
+            raise NotImplementedError("decoding_kwargs['select_best'] must be False: the update needs every ant's tour")
+        for what, t in (("log_heuristic", self.log_heuristic), ("pheromone", self.pheromone), ("td['locs']", td["locs"])):
+            if not t.is_cuda:  # (before td['prize'], td['max_length'], td['real_prize'] or td['penalty'] is touched)
+                raise NotImplementedError(f"AntSystem runs inside the MI355X kernel (rl4co_aco_prize) only, env {name!r}: "
+                                          f"{what} on {t.device}")
+        return float(decoding_kwargs.get("temperature", 1.0))
+
     def _tensors(self, td):
         dev = self.log_heuristic.device
         heu = self.log_heuristic.detach().to(torch.float32).contiguous()
@@ -153,8 +185,9 @@ class AntSystem:
     # ---- AntSystem.run (antsystem.py:87-118) -----------------------------------------------------------------------------
     def run(self, td_initial, env, n_iterations: int, decoding_kwargs: dict, disable_tqdm: bool = True):
         temperature = self._check(td_initial, env, decoding_kwargs)
-        if env.name == "cvrp":
-            out = self._sampling_cvrp(td_initial, env, decoding_kwargs, temperature, n_iterations)
+        if env.name == "cvrp" or env.name in _PRIZE_ENVS:
+            sampling = self._sampling_cvrp if env.name == "cvrp" else self._sampling_prize
+            out = sampling(td_initial, env, decoding_kwargs, temperature, n_iterations)
             for i in range(n_iterations):
                 self.final_reward_cache[i] = out["final_reward_cache"][i].clone()
             self.last_iterations = {"actions": out["iter_actions"], "reward": out["iter_reward"], "lengths": out["iter_lengths"]}
@@ -191,6 +224,9 @@ class AntSystem:
         if env.name == "cvrp":  # actions [rows, W], zero-filled after each row's length
             out = self._sampling_cvrp(td, env, decoding_kwargs, temperature, 1)
             return out["actions"], out["reward"]
+        if env.name in _PRIZE_ENVS:  # actions [rows, n], zero-filled after each row's length
+            out = self._sampling_prize(td, env, decoding_kwargs, temperature, 1)
+            return out["actions"], out["reward"]
         heu, locs = self._tensors(td)
         starts = self._start_nodes(td, env, decoding_kwargs)[None].contiguous()
         seed, offset = self._next_seed()
@@ -218,7 +254,7 @@ class AntSystem:
     # ---- CVRP: sampling and update of ``n_iterations`` iterations in one launch (rl4co_aco_cvrp) -----------------------------
     def _sampling_cvrp(self, td, env, decoding_kwargs: dict, temperature: float, n_iterations: int) -> dict:
         heu, locs = self._tensors(td)
-        dev, b = heu.device, self.batch_size
+        dev = heu.device
         demand = td["demand"].detach().to(device=dev, dtype=torch.float32).contiguous()
         capacity = td["vehicle_capacity"].detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
         starts = None
@@ -226,16 +262,24 @@ class AntSystem:
             starts = torch.stack([self._start_nodes(td, env, decoding_kwargs) for _ in range(n_iterations)], 0).contiguous()
         seed, offset = self._next_seed()
         err = K.new_error_word(dev)
-        width = K.aco_cvrp_width(heu.shape[1])
+        record = self._padded_record(K.aco_cvrp_width(heu.shape[1]))
+        out = K.aco_cvrp(self.pheromone, iterations=n_iterations, log_heuristic=heu, locs=locs, demand=demand,
+                         vehicle_capacity=capacity, start_nodes=starts, philox_seed=seed, philox_offset=offset,
+                         record_iterations=True, err=err, **record, **self._common(temperature))
+        self._take_ragged_record(out, err, record["has_best"])
+        return out
+
+    def _padded_record(self, width: int) -> dict:
         has = self.final_reward is not None
         record = dict(has_best=has, final_reward=self.final_reward if has else None, final_actions=None)
         if has:  # the ragged list, zero-padded to the kernel's width
             record["final_actions"] = torch.stack(
                 [torch.nn.functional.pad(t, (0, width - t.shape[0])) for t in self.final_actions], 0).contiguous()
-        out = K.aco_cvrp(self.pheromone, iterations=n_iterations, log_heuristic=heu, locs=locs, demand=demand,
-                         vehicle_capacity=capacity, start_nodes=starts, philox_seed=seed, philox_offset=offset,
-                         record_iterations=True, err=err, **record, **self._common(temperature))
-        # the one read-back of the run: the error word, which iteration last replaced each record, every iteration's width
+        return record
+
+    def _take_ragged_record(self, out: dict, err: Tensor, has: bool) -> None:
+        """The one read-back of the run: the error word, which iteration last replaced each record, every iteration's width."""
+        b = self.batch_size
         widths = out["iter_lengths"].amax(1).to(torch.int32)
         host = torch.cat((err, out["final_iteration"], widths)).tolist()
         _lib.raise_for_error_bits(host[0])
@@ -246,6 +290,26 @@ class AntSystem:
         for i, it in enumerate(replaced):  # antsystem.py:238-245: the entry has the width of its iteration's batch
             if it >= 0:
                 self.final_actions[i] = out["final_actions"][i, : widths[it]].clone()
+
+    # ---- OP / PCTSP: sampling and update of ``n_iterations`` iterations in one launch (rl4co_aco_prize) -----------------------
+    def _sampling_prize(self, td, env, decoding_kwargs: dict, temperature: float, n_iterations: int) -> dict:
+        heu, locs = self._tensors(td)
+        dev = heu.device
+
+        def vec(key):
+            return td[key].detach().to(device=dev, dtype=torch.float32).contiguous()
+
+        if env.name == "op":
+            data = dict(prize=vec("prize"), max_length=vec("max_length"))
+        else:  # real_prize: the deterministic prize, or the stochastic one under SPCTSPEnv (the env's reset picked it)
+            data = dict(prize=vec("real_prize"), penalty=vec("penalty"))
+        seed, offset = self._next_seed()
+        err = K.new_error_word(dev)
+        record = self._padded_record(heu.shape[1])
+        out = K.aco_prize(self.pheromone, env=env.name, iterations=n_iterations, log_heuristic=heu, locs=locs,
+                          philox_seed=seed, philox_offset=offset, record_iterations=True, err=err, **data, **record,
+                          **self._common(temperature))
+        self._take_ragged_record(out, err, record["has_best"])
         return out
 
     # ---- AntSystem.local_search (antsystem.py:173-230), without the host round trip --------------------------------------

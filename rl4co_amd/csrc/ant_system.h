@@ -1,4 +1,4 @@
-// ant_system.h — what the Ant System kernels (aco_tsp.hip, aco_cvrp.hip) share, stated once: the constants and the scratch
+// ant_system.h — what the Ant System kernels (aco_tsp.hip, aco_cvrp.hip, aco_prize.hip) share, stated once: the constants and the scratch
 // words, the index pre-check, stage A (the logits), one sampling step of one wave, stage U (record, reward map, pheromone)
 // and the host side (launch, the LDS-tier search, the argument checks common to both entry points). A kernel keeps its
 // LDS layout, its per-ant state, its tour / actions / logps stores and its R stage (lds_tour_reward.h).
@@ -242,9 +242,10 @@ inline int lds_nodes(BytesFn lds_bytes) {
   return n;
 }
 
-// one workgroup per instance with `lds_bytes` of dynamic LDS
+// one workgroup per instance with `lds_bytes` of dynamic LDS; `grid` > 0: that many workgroups (a kernel that strides
+// over the instances itself)
 template <auto Kernel, typename Args>
-int launch(const Args& a, int lds_bytes, hipStream_t stream) {
+int launch(const Args& a, int lds_bytes, hipStream_t stream, int grid = 0) {
   hipFuncAttributes fa;
   RL4CO_HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(Kernel)));
   RL4CO_REQUIRE((int64_t)fa.sharedSizeBytes <= kStaticLds);  // the budget behind *_lds_nodes() holds
@@ -252,12 +253,12 @@ int launch(const Args& a, int lds_bytes, hipStream_t stream) {
     RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       lds_bytes));
   }
-  hipLaunchKernelGGL(Kernel, dim3(a.B), dim3(kThreads), lds_bytes, stream, a);
+  hipLaunchKernelGGL(Kernel, dim3(grid > 0 ? grid : a.B), dim3(kThreads), lds_bytes, stream, a);
   RL4CO_HIP_TRY(hipGetLastError());
   return RL4CO_OK;
 }
 
-// the requirements rl4co_aco_tsp_args and rl4co_aco_cvrp_args share
+// the requirements rl4co_aco_tsp_args, rl4co_aco_cvrp_args and rl4co_aco_prize_args share
 template <typename Args>
 int require_common(const Args& a) {
   RL4CO_REQUIRE(a.B >= 1);

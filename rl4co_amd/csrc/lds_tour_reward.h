@@ -2,8 +2,8 @@
 // arithmetic RESTATED in the same order (ATen's vector_norm over two elements, then SumKernel's 8-lane / 4-ILP / 4-level
 // cascade; lanes 0..7 of the wave play the SIMD lanes). The expression text is kept equal to that file's TourView::seg,
 // lane_row_sum and kernel epilogue — change both together. Bit-equal to TSPEnv.get_reward / rl4co_tour_length_f32 (tested
-// through aco_tsp.hip, tsp_nls.hip and aco_cvrp.hip, the three kernels that include this; aco_cvrp.hip passes
-// [depot, actions] with n = W + 1: rl4co_tour_length_f32 with prepend_depot on the W-wide row).
+// through aco_tsp.hip, tsp_nls.hip and aco_cvrp.hip; aco_cvrp.hip passes [depot, actions] with n = W + 1:
+// rl4co_tour_length_f32 with prepend_depot on the W-wide row). aco_prize.hip also sums other terms in the same order.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -24,7 +24,9 @@ struct AntTour {
   }
 };
 
-__device__ inline float lane_row_sum(const AntTour& tv, int lane8, int nvec) {
+// `Terms` is any view with `n` terms and `seg(t)`, term t: AntTour's segments, or (aco_prize.hip) a vector gathered along a row
+template <typename Terms>
+__device__ inline float lane_row_sum(const Terms& tv, int lane8, int nvec) {
   constexpr int kIlp = 4;
   constexpr int kLevels = 4;
   const int size = nvec / kIlp;  // size_ilp
@@ -62,7 +64,8 @@ __device__ inline float lane_row_sum(const AntTour& tv, int lane8, int nvec) {
 }
 
 // minus the closed tour length, valid in lane 0; the whole wave calls it (tour_length_kernel's body for one trajectory)
-__device__ inline float ant_reward(const AntTour& tv, int lane) {
+template <typename Terms>
+__device__ inline float ant_reward(const Terms& tv, int lane) {
   const int n = tv.n;
   const int nvec = n / 8;
   if (n < 8) {  // ATen's scalar_inner_sum

@@ -930,6 +930,135 @@ def aco_cvrp(pheromone: Tensor, *, n_ants: int, phases: int = _lib.ACO_SAMPLE | 
     return out
 
 
+_ACO_PRIZE_ENVS = {"op": _lib.ENV_OP, "pctsp": _lib.ENV_PCTSP, "spctsp": _lib.ENV_PCTSP}  # spctsp: the caller's prize is the stochastic one
+
+
+def aco_prize_lds_nodes(env: str) -> int:
+    """Largest node count (depot included) at which the OP / PCTSP Ant System kernel keeps logits and pheromone in LDS."""
+    return int(_lib.lib().rl4co_aco_prize_lds_nodes(_ACO_PRIZE_ENVS[env]))
+
+
+def aco_prize(pheromone: Tensor, *, env: str, n_ants: int, phases: int = _lib.ACO_SAMPLE | _lib.ACO_UPDATE,
+              iterations: int = 1, log_heuristic: Tensor | None = None, locs: Tensor | None = None,
+              prize: Tensor | None = None, penalty: Tensor | None = None, max_length: Tensor | None = None,
+              alpha: float = 1.0, beta: float = 1.0, decay: float = 0.95, Q: float = 1.0, temperature: float = 1.0,
+              ln_noise: Tensor | None = None, philox_seed: int = 0, philox_offset: int = 0,
+              philox_seed_dev: Tensor | None = None, forced_actions: Tensor | None = None, actions: Tensor | None = None,
+              reward: Tensor | None = None, final_reward: Tensor | None = None, final_actions: Tensor | None = None,
+              final_iteration: Tensor | None = None, has_best: bool = False, iteration_base: int = 0,
+              all_logps: bool = False, record_iterations: bool = False, n_workgroups: int = 0,
+              err: Tensor | None = None) -> dict:
+    """Ant System iterations for the prize problems (``env``: "op", "pctsp" or "spctsp") on ``pheromone`` [B, n, n] (fp32, the
+    depot is node 0, updated IN PLACE) in one launch (rl4co_aco_prize; the header states the arithmetic). Rows are
+    ant-major as in :func:`aco_tsp`; sampled rows are ``W = n`` wide, zero-filled after ``lengths[row]``.
+
+    ``locs`` [B, n, 2] with the depot at 0; ``prize`` [B, n] with 0 at the depot (OP: ``td["prize"]``; PCTSP:
+    ``td["real_prize"]``); ``penalty`` [B, n] (PCTSP); ``max_length`` [B, n], the environment's per-node table (OP).
+    ``ln_noise`` fp32 [iterations, W, rows, n] (parity mode) or None for the in-kernel Philox. SAMPLE alone samples (or,
+    with ``forced_actions`` [rows, W], evaluates) once; UPDATE alone takes ``actions`` [rows, T] of any width T >= 2 and
+    ``reward`` [rows]. The reward is the environment's ``get_reward`` on the W-wide row. ``n_workgroups``: 0 for one
+    workgroup per instance, else that many workgroups striding over the instances (the same results). The record
+    arguments, the returned dict and ``err`` are :func:`aco_cvrp`'s."""
+    if env not in _ACO_PRIZE_ENVS:
+        raise NotImplementedError(f"aco_prize (rl4co_aco_prize) serves {sorted(_ACO_PRIZE_ENVS)}, got env = {env!r}")
+    for name, t in (("pheromone", pheromone), ("log_heuristic", log_heuristic), ("locs", locs), ("prize", prize),
+                    ("penalty", penalty), ("max_length", max_length)):
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError(f"aco_prize runs inside the MI355X kernel (rl4co_aco_prize) only: {name} on {t.device}")
+    pheromone = _dev(pheromone, torch.float32, "pheromone")
+    if pheromone.dim() != 3 or pheromone.shape[1] != pheromone.shape[2]:
+        raise ValueError(f"pheromone must be [B, n, n], got {tuple(pheromone.shape)}")
+    b, n, _ = pheromone.shape
+    if not 2 <= n <= 1024:
+        raise NotImplementedError(f"aco_prize serves 2..1024 nodes (depot included), got n = {n}")
+    n_ants, iterations = int(n_ants), int(iterations)
+    rows, w = n_ants * b, n
+    dev = pheromone.device
+    sample, update = bool(phases & _lib.ACO_SAMPLE), bool(phases & _lib.ACO_UPDATE)
+    is_op = env == "op"
+
+    def shaped(t, dtype, shape, name):
+        if t is None:
+            return None
+        t = _dev(t, dtype, name)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    log_heuristic = shaped(log_heuristic, torch.float32, (b, n, n), "log_heuristic")
+    locs = shaped(locs, torch.float32, (b, n, 2), "locs")
+    prize = shaped(prize, torch.float32, (b, n), "prize")
+    penalty = shaped(penalty, torch.float32, (b, n), "penalty")
+    max_length = shaped(max_length, torch.float32, (b, n), "max_length")
+    ln_noise = shaped(ln_noise, torch.float32, (iterations, w, rows, n), "ln_noise")
+    forced_actions = shaped(forced_actions, torch.int64, (rows, w), "forced_actions")
+    if sample:
+        if actions is not None or reward is not None:
+            raise ValueError("actions / reward are outputs of the SAMPLE phase")
+        if locs is None or prize is None or (max_length if is_op else penalty) is None:
+            raise ValueError("the SAMPLE phase takes locs [B, n, 2], prize [B, n] and "
+                             + ("max_length [B, n]" if is_op else "penalty [B, n]"))
+        actions = torch.zeros((rows, w), dtype=torch.int64, device=dev)
+        reward = torch.zeros(rows, dtype=torch.float32, device=dev)
+        t = w
+    elif actions is None or reward is None:
+        raise ValueError("the UPDATE phase alone takes actions [rows, T] and reward [rows]")
+    else:
+        t = actions.shape[-1]
+        if t < 2:
+            raise ValueError(f"actions must be [rows, T] with T >= 2, got {tuple(actions.shape)}")
+    actions = shaped(actions, torch.int64, (rows, t), "actions")
+    reward = shaped(reward, torch.float32, (rows,), "reward")
+    out = {"actions": actions, "reward": reward}
+    if sample:
+        out["lengths"] = torch.zeros(rows, dtype=torch.int32, device=dev)
+        out["logps"] = torch.zeros((rows, w), dtype=torch.float32, device=dev)
+        if all_logps:
+            out["all_logps"] = torch.zeros((rows, w, n), dtype=torch.float32, device=dev)
+        if record_iterations:
+            out["iter_actions"] = torch.zeros((iterations, rows, w), dtype=torch.int64, device=dev)
+            out["iter_lengths"] = torch.zeros((iterations, rows), dtype=torch.int32, device=dev)
+            out["iter_reward"] = torch.zeros((iterations, rows), dtype=torch.float32, device=dev)
+    if update:
+        if (final_reward is None) != (final_actions is None):
+            raise ValueError("final_reward and final_actions come together")
+        if final_reward is None:
+            if has_best:
+                raise ValueError("has_best needs final_reward and final_actions")
+            final_reward = torch.zeros(b, dtype=torch.float32, device=dev)
+            final_actions = torch.zeros((b, t), dtype=torch.int64, device=dev)
+        if final_iteration is None:
+            final_iteration = torch.full((b,), -1, dtype=torch.int32, device=dev)
+        out["final_reward"] = shaped(final_reward, torch.float32, (b,), "final_reward")
+        out["final_actions"] = shaped(final_actions, torch.int64, (b, t), "final_actions")
+        out["final_iteration"] = shaped(final_iteration, torch.int32, (b,), "final_iteration")
+        out["final_reward_cache"] = torch.zeros((iterations, b), dtype=torch.float32, device=dev)
+    scratch = torch.empty((b, n, n), dtype=torch.float32, device=dev) if n > aco_prize_lds_nodes(env) else None
+    own = err is None
+    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
+    a = _lib.AcoPrizeArgs()
+    a.B, a.N, a.n_ants, a.iterations, a.phases, a.has_best = b, n, n_ants, iterations, int(phases), int(bool(has_best))
+    a.T, a.iteration_base, a.env, a.n_workgroups = t, int(iteration_base), _ACO_PRIZE_ENVS[env], int(n_workgroups)
+    a.alpha, a.beta, a.decay, a.Q, a.temperature, a.reserved0 = alpha, beta, decay, Q, temperature, 0
+    a.philox_seed, a.philox_offset = int(philox_seed) & (2**64 - 1), int(philox_offset) & (2**64 - 1)
+    a.philox_seed_dev = _ptr(philox_seed_dev)
+    a.log_heuristic, a.pheromone, a.locs = _ptr(log_heuristic), _ptr(pheromone), _ptr(locs)
+    a.prize, a.penalty, a.max_length = _ptr(prize), _ptr(penalty), _ptr(max_length)
+    a.ln_noise, a.forced_actions, a.logits_scratch = _ptr(ln_noise), _ptr(forced_actions), _ptr(scratch)
+    a.actions, a.lengths, a.reward = _ptr(actions), _ptr(out.get("lengths")), _ptr(reward)
+    a.logps, a.all_logps = _ptr(out.get("logps")), _ptr(out.get("all_logps"))
+    a.iter_actions, a.iter_lengths = _ptr(out.get("iter_actions")), _ptr(out.get("iter_lengths"))
+    a.iter_reward = _ptr(out.get("iter_reward"))
+    a.final_reward, a.final_actions = _ptr(out.get("final_reward")), _ptr(out.get("final_actions"))
+    a.final_iteration, a.final_reward_cache = _ptr(out.get("final_iteration")), _ptr(out.get("final_reward_cache"))
+    a.err = _ptr(err)
+    st = _lib.lib().rl4co_aco_prize(C.byref(a), _stream())
+    _lib.check(st, "rl4co_aco_prize")
+    if own:
+        raise_if_error(err)
+    return out
+
+
 def decoding_filter(top_k, top_p, n: int) -> tuple[int, float]:
     """The top-k / top-p arguments of utils/decoding.py:109-188 as the kernel takes them: ``top_k <= 0`` is off and is
     clamped to ``n`` (k >= n removes nothing: 0); ``top_p <= 0`` or ``>= 1`` is off (0.0); ``top_p > 1`` raises the

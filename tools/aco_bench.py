@@ -14,6 +14,12 @@ Next to the times: the mean best tour length after the last iteration, in float6
 10 iterations, ``multisample`` decoding (every ant starts at the depot), heuristic -log(distance). One leg, ``fused``: there
 is no earlier CVRP path to compare with. Writes profiles/aco_cvrp_bench.json unless ``--out`` says otherwise.
 
+``--env prize`` times the OP and PCTSP search (csrc/aco_prize.hip): 256 x OP-50 and 256 x PCTSP-50 from the environments'
+generators (``--batch`` / ``--num-loc`` when given), 48 ants, 10 iterations, ``multisample`` decoding, heuristic
+-log(distance). Two legs per environment, alternating: ``fused`` (one rl4co_aco_prize launch) and ``torch_per_step`` (this
+script's torch loop over the decoding steps with the environment's mask, for scale only). Next to the times: the mean best
+reward after the last iteration. Writes profiles/aco_prize_bench.json unless ``--out`` says otherwise.
+
 ``--nls`` times one iteration's neural-guided local search (csrc/tsp_nls.hip) instead: 1024 x TSP-100, 20 ants, 5
 perturbations of at most 5 scans; the fused launch against the composition of the 2-opt and reward kernels on the same
 tours (``main_nls``). Writes profiles/aco_nls_bench.json unless ``--out`` says otherwise.
@@ -113,7 +119,7 @@ def main():
     ap.add_argument("--ants", type=int, default=48)
     ap.add_argument("--iterations", type=int, default=10)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--env", choices=("tsp", "cvrp"), default="tsp")
+    ap.add_argument("--env", choices=("tsp", "cvrp", "prize"), default="tsp")
     ap.add_argument("--nls", action="store_true", help="time the neural-guided local search instead (TSP)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -121,6 +127,8 @@ def main():
     dev = torch.device("cuda", 0)
     if a.env == "cvrp":
         return main_cvrp(a, dev)
+    if a.env == "prize":
+        return main_prize(a, dev)
     if a.nls:
         return main_nls(a, dev)
     g = torch.Generator().manual_seed(1234)
@@ -181,6 +189,106 @@ def main_cvrp(a, dev):
                        case=f"cvrp{a.num_loc}x{a.batch}, {a.ants} ants, {a.iterations} iterations, multisample",
                        what="AntSystem.run end to end (host work included), HIP events around the call, synchronised",
                        rows=[row]), f, indent=1)
+
+
+def torch_prize_ant_system(name, heu, td, n_ants, iterations, alpha=1.0, beta=1.0, decay=0.95):
+    """The Ant System loop for OP / PCTSP from torch ops, one decoding step at a time (ant-major rows, the environment's mask
+    and reward in its own expressions). Returns the best reward per instance."""
+    b, n, _ = heu.shape
+    rows, q, dev = n_ants * b, 1 / n_ants / decay, heu.device
+    ar, inst = torch.arange(rows, device=dev), torch.arange(rows, device=dev) % b
+    bidx = torch.arange(b, device=dev)
+    locs = td["locs"][inst]
+    prize = td["prize" if name == "op" else "real_prize"][inst]
+    limit = td["max_length"][inst] if name == "op" else None
+    penalty = td["penalty"][inst] if name != "op" else None
+    phe = torch.ones_like(heu)
+    best_reward = None
+    for _ in range(iterations):
+        logits = alpha * torch.log(phe) + beta * heu
+        cur = torch.zeros(rows, dtype=torch.int64, device=dev)
+        visited = torch.zeros(rows, n, dtype=torch.bool, device=dev)
+        acc = torch.zeros(rows, device=dev)
+        done = torch.zeros(rows, dtype=torch.bool, device=dev)
+        steps = []
+        for t in range(n):
+            mask = visited | visited[:, 0:1]
+            if name == "op":
+                mask = mask | (acc[:, None] + (locs - locs[ar, cur][:, None, :]).norm(p=2, dim=-1) > limit)
+                mask[:, 0] = False
+            else:
+                mask[:, 0] = (acc < 1.0) & (visited[:, 1:].sum(-1) < n - 1)
+            lp = torch.log_softmax(logits[inst, cur].masked_fill(mask, float("-inf")), -1)
+            nxt = torch.where(done, torch.zeros_like(cur), torch.multinomial(lp.exp(), 1).squeeze(1))
+            acc = acc + ((locs[ar, nxt] - locs[ar, cur]).norm(p=2, dim=-1) if name == "op" else prize[ar, nxt])
+            visited[ar, nxt] = True
+            done = done | ((nxt == 0) & (t > 0))
+            cur = nxt
+            steps.append(nxt)
+        actions = torch.stack(steps, 1)
+        if name == "op":
+            reward = prize.gather(1, actions).sum(-1)
+        else:
+            pts = locs[ar[:, None], torch.cat((torch.zeros_like(actions[:, :1]), actions), 1)]
+            length = (pts.roll(-1, 1) - pts).norm(p=2, dim=-1).sum(1)
+            reward = penalty.gather(1, actions).sum(-1) - (length + penalty[:, 1:].sum(-1))
+        rew, act = reward.view(n_ants, b).t(), actions.view(n_ants, b, n)
+        top_reward = rew.max(-1).values
+        best_reward = top_reward.clone() if best_reward is None else torch.maximum(best_reward, top_reward)
+        hi, lo = rew.max(-1, keepdim=True).values, rew.min(-1, keepdim=True).values
+        v = ((rew - lo) / (hi - lo)) ** 2 * q
+        delta = torch.zeros_like(phe)
+        for j in range(n_ants):
+            delta[bidx[:, None], act[j, :, :-1], act[j, :, 1:]] += v[:, j : j + 1]
+        delta[:, 0, 0] = 0
+        phe = phe * decay + delta
+    return best_reward
+
+
+def main_prize(a, dev):
+    batch = a.batch if a.batch != 4096 else 256  # (the defaults of this script are sized for TSP-100)
+    num_loc = a.num_loc if a.num_loc != 100 else 50
+    kwargs = dict(multisample=True, num_samples=a.ants, select_best=False)
+    rows = []
+    for name in ("op", "pctsp"):
+        torch.manual_seed(1234)
+        env = get_env(name, generator_params=dict(num_loc=num_loc, device=dev), device=dev)
+        td = env.reset(batch_size=[batch])
+        locs = td["locs"]  # [B, num_loc + 1, 2], the depot first
+        dist = (locs[:, :, None] - locs[:, None, :]).norm(p=2, dim=-1)
+        heu = -torch.log(dist + 1e9 * torch.eye(num_loc + 1, device=dev))
+        state = {}
+
+        def fused():
+            torch.manual_seed(0)
+            aco = AntSystem(heu, n_ants=a.ants)
+            state["tours"] = aco.run(td, env, a.iterations, kwargs)[0]
+            return aco.final_reward
+
+        def per_step():
+            torch.manual_seed(0)
+            return torch_prize_ant_system(name, heu, td, a.ants, a.iterations)
+
+        legs = [Leg("fused", fused, lambda _locs, reward: reward.double()),
+                Leg("torch_per_step", per_step, lambda _locs, reward: reward.double())]
+        for it in range(a.reps + 1):  # one warm-up round; the legs alternate inside every round
+            for leg in legs:
+                leg.launch(keep=it >= 1)
+        env.check_solution_validity(td, state["tours"])
+        for leg in legs:
+            row = leg.result(locs)
+            row = dict(env=name, case=f"{name}{num_loc}x{batch}", **row)
+            row["mean_best_reward_f64"] = row.pop("mean_best_length_f64")
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    out = a.out or "profiles/aco_prize_bench.json"
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(dict(device=torch.cuda.get_device_name(0), when=time.strftime("%Y-%m-%d"),
+                       case=f"op{num_loc} and pctsp{num_loc} x {batch}, {a.ants} ants, {a.iterations} iterations, multisample",
+                       what="AntSystem.run end to end (host work included), HIP events around the call, synchronised; "
+                            "torch_per_step is this script's torch loop on the same card, for scale only",
+                       rows=rows), f, indent=1)
 
 
 def main_nls(a, dev):
