@@ -51,8 +51,10 @@ extern "C" {
  *  20: rl4co_tsp_nls / rl4co_tsp_nls_lds_nodes (neural-guided local search for TSP, rl4co_tsp_nls_args).
  *  21: rl4co_nargnn_heatmap / rl4co_nargnn_lds_nodes / rl4co_nargnn_scratch_bytes (DeepACO's heatmap encoder,
  *      rl4co_nargnn_args).
- *  22: rl4co_aco_prize / rl4co_aco_prize_lds_nodes (the Ant System search for OP and PCTSP, rl4co_aco_prize_args). */
-#define RL4CO_ABI_VERSION 22
+ *  22: rl4co_aco_prize / rl4co_aco_prize_lds_nodes (the Ant System search for OP and PCTSP, rl4co_aco_prize_args).
+ *  23: rl4co_nargnn_depot_heatmap / rl4co_nargnn_depot_lds_nodes / rl4co_nargnn_depot_scratch_bytes (the heatmap encoder
+ *      for the depot graphs of CVRP, OP and PCTSP, rl4co_nargnn_depot_args). */
+#define RL4CO_ABI_VERSION 23
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -903,6 +905,66 @@ int rl4co_nargnn_heatmap(const rl4co_nargnn_args* args, void* stream);
 int rl4co_nargnn_lds_nodes(int K);
 /* Bytes of `scratch` one workgroup needs at this shape (0 < result; the tier is the kernel's own choice). */
 int64_t rl4co_nargnn_scratch_bytes(int N, int K);
+
+/* --------------------------------------------------------------------------
+ * The same encoder for the depot graphs of CVRP, OP and PCTSP (NARGNNEncoder(env_name=...) in inference with
+ * VRP / OP / PCTSPInitEmbedding and CVRPEdgeEmbedding, env_embeddings/edge.py:119-176) as ONE launch in fp32
+ * (nargnn_depot.hip). Node 0 is the depot, nodes 1 .. C = N - 1 the customers. Customer u has K + 1 out-edges: to
+ * neighbors[b][u-1][0 .. K-1] (customers, values in 1 .. N-1) and to the depot; the depot has C out-edges, one to every
+ * customer: C (K + 2) edges. The layer equations are rl4co_nargnn_args', the mean pooled by SOURCE node: over K + 1
+ * rows for a customer, over C rows for the depot (eight partial sums).
+ *   x[0] = silu(depot(locs[0]));  x[u] = silu(init(locs[u], feats[u-1]));  w = silu(edge_embed(cost))
+ *   heatmap[b][u][v_k], heatmap[b][u][0] and heatmap[b][0][i] = log(h + small_value); fill_value everywhere else
+ *   (the diagonal and heatmap[b][0][0] included).
+ * feats: CVRP demand; OP prize[:, 1:]; PCTSP (expected_prize, penalty[:, 1:]). depot_cost[b][u-1] is the one distance of
+ * (u -> 0) and (0 -> u). The layer, MLP and output parameters are packed exactly as in rl4co_nargnn_args.
+ * Tiers as above with C (K + 2) edge rows: up to rl4co_nargnn_depot_lds_nodes(K) nodes the edge state and the two
+ * gathered node planes stay in LDS; above, the edge state lives in `scratch`; above 300 nodes every plane does.
+ * `scratch` holds n_workgroups * rl4co_nargnn_depot_scratch_bytes(N, K) bytes, 16-byte aligned.
+ * A neighbour index outside [1, N) (0, the depot, included: it would repeat the depot edge) sets
+ * RL4CO_EBIT_TOUR_INDEX; that instance's outputs are left untouched.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_nargnn_depot_args {
+  int32_t B;                /* instances, >= 1                                              */
+  int32_t N;                /* nodes with the depot, 3 .. 1024                              */
+  int32_t K;                /* customer neighbours per customer, 1 .. min(N - 2, 256)       */
+  int32_t F;                /* customer features behind the coordinates: 1 or 2             */
+  int32_t D;                /* embedding width: 64                                          */
+  int32_t L;                /* GNN layers, >= 0                                             */
+  int32_t H;                /* heatmap MLP layers with the output layer, >= 1               */
+  int32_t n_workgroups;     /* grid, 1 .. B                                                 */
+  float small_value;        /* added to h before the log                                    */
+  float fill_value;         /* log(small_value) as the host computed it                     */
+  const float* locs;        /* [B,N,2]                                                      */
+  const float* feats;       /* [B,N-1,F]                                                    */
+  const int32_t* neighbors; /* [B,N-1,K], values in 1 .. N-1                                */
+  const float* edge_cost;   /* [B,N-1,K]                                                    */
+  const float* depot_cost;  /* [B,N-1]                                                      */
+  const float* init_w;      /* [D,2+F] (customers)                                          */
+  const float* init_b;      /* [D]                                                          */
+  const float* depot_w;     /* [D,2]                                                        */
+  const float* depot_b;     /* [D]                                                          */
+  const float* edge_w;      /* [D] (Linear(1, D))                                           */
+  const float* edge_b;      /* [D]                                                          */
+  const float* lin_w;       /* [L,5,D,D]: v_lin1 .. v_lin4, e_lin; NULL allowed when L == 0  */
+  const float* lin_b;       /* [L,5,D]                                                      */
+  const float* bn;          /* [L,2,2,D]: (v_bn, e_bn) x (scale, shift)                     */
+  const float* mlp_w;       /* [H-1,D,D]; NULL allowed when H == 1                          */
+  const float* mlp_b;       /* [H-1,D] or NULL (linear_bias = False)                        */
+  const float* out_w;       /* [D]                                                          */
+  const float* out_b;       /* [1] or NULL                                                  */
+  float* scratch;           /* n_workgroups * rl4co_nargnn_depot_scratch_bytes(N, K) bytes  */
+  int64_t scratch_bytes;
+  float* heatmap;           /* [B,N,N] out                                                  */
+  float* node_embed;        /* [B,N,D] out: the init embeddings, before the activation      */
+  int32_t* err;             /* sticky error bits                                            */
+} rl4co_nargnn_depot_args;
+
+int rl4co_nargnn_depot_heatmap(const rl4co_nargnn_depot_args* args, void* stream);
+/* Largest N at which rl4co_nargnn_depot_heatmap keeps the (N - 1)(K + 2) edge rows in LDS (nargnn_depot.hip header). */
+int rl4co_nargnn_depot_lds_nodes(int K);
+/* Bytes of `scratch` one workgroup needs at this shape (0 outside the supported range). */
+int64_t rl4co_nargnn_depot_scratch_bytes(int N, int K);
 
 /* --------------------------------------------------------------------------
  * a11-a13  fused encoder + decoder-cache fold on the matrix cores (inference rollouts).

@@ -7,7 +7,7 @@ See DESIGN.md for the path, the boundary and what is out of scope.
 """
 __version__ = "0.1.0"
 
-__all__ = ["AntSystem", "DeepACOPolicy", "NARGNNEncoder"]
+__all__ = ["AntSystem", "DeepACOPolicy", "NARGNNDepotEncoder", "NARGNNEncoder"]
 
 
 def __getattr__(name):
@@ -15,7 +15,8 @@ def __getattr__(name):
         from .aco import AntSystem
 
         return AntSystem
-    if name in ("NARGNNEncoder", "DeepACOPolicy"):  # rl4co_amd.nargnn: DeepACO's heatmap encoder on rl4co_nargnn_heatmap
+    # rl4co_amd.nargnn: DeepACO's heatmap encoders on rl4co_nargnn_heatmap / rl4co_nargnn_depot_heatmap
+    if name in ("NARGNNEncoder", "NARGNNDepotEncoder", "DeepACOPolicy"):
         from . import nargnn
 
         return getattr(nargnn, name)

@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 22  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 23  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -136,6 +136,19 @@ class NargnnArgs(C.Structure):
         ("B", _i32), ("N", _i32), ("K", _i32), ("D", _i32), ("L", _i32), ("H", _i32), ("n_workgroups", _i32), ("reserved0", _i32),
         ("small_value", _f32), ("fill_value", _f32),
         ("locs", _vp), ("neighbors", _vp), ("edge_cost", _vp), ("init_w", _vp), ("init_b", _vp), ("edge_w", _vp), ("edge_b", _vp),
+        ("lin_w", _vp), ("lin_b", _vp), ("bn", _vp), ("mlp_w", _vp), ("mlp_b", _vp), ("out_w", _vp), ("out_b", _vp),
+        ("scratch", _vp), ("scratch_bytes", _i64), ("heatmap", _vp), ("node_embed", _vp), ("err", _vp),
+    ]
+
+
+class NargnnDepotArgs(C.Structure):
+    """Mirror of ``struct rl4co_nargnn_depot_args`` (field order and types must match the header)."""
+
+    _fields_ = [
+        ("B", _i32), ("N", _i32), ("K", _i32), ("F", _i32), ("D", _i32), ("L", _i32), ("H", _i32), ("n_workgroups", _i32),
+        ("small_value", _f32), ("fill_value", _f32),
+        ("locs", _vp), ("feats", _vp), ("neighbors", _vp), ("edge_cost", _vp), ("depot_cost", _vp),
+        ("init_w", _vp), ("init_b", _vp), ("depot_w", _vp), ("depot_b", _vp), ("edge_w", _vp), ("edge_b", _vp),
         ("lin_w", _vp), ("lin_b", _vp), ("bn", _vp), ("mlp_w", _vp), ("mlp_b", _vp), ("out_w", _vp), ("out_b", _vp),
         ("scratch", _vp), ("scratch_bytes", _i64), ("heatmap", _vp), ("node_embed", _vp), ("err", _vp),
     ]
@@ -298,6 +311,9 @@ SYMBOLS = {
     "rl4co_nargnn_heatmap": (C.c_int, [C.POINTER(NargnnArgs), _vp]),
     "rl4co_nargnn_lds_nodes": (C.c_int, [C.c_int]),
     "rl4co_nargnn_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "rl4co_nargnn_depot_heatmap": (C.c_int, [C.POINTER(NargnnDepotArgs), _vp]),
+    "rl4co_nargnn_depot_lds_nodes": (C.c_int, [C.c_int]),
+    "rl4co_nargnn_depot_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "rl4co_select_start_nodes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "rl4co_augment_dihedral8_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_augment_symmetric_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp]),

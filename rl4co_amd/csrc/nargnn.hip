@@ -17,11 +17,8 @@
 // Both updates of a layer read the layer's incoming x and w: the node update of a wave's nodes runs before the edge update
 // of the same nodes' rows, and x1 .. x4 were taken from x in A.
 //
-// MFMA v_mfma_f32_16x16x4_f32, operands as csrc/enc_f32.h states them: lane = 16 g + c holds A[row c][k-slot g] and
-// B[k-slot g][col c]; a lane's 16-byte fragment (k = 16 j + 4 g .. + 3) feeds four steps, component s of both operands in
-// step s. B is the weight row-major as torch keeps it ([out][in]): lane (c, g) of column tile ct reads
-// W[16 ct + c][16 j + 4 g ..]. A wave holds one matrix (16 fragments, 64 VGPRs) for all of its row tiles. D[row 4 g + r]
-// [col 16 ct + c] arrives in register r of accumulator ct. The sum over the 64 inputs is the hardware's (16 steps of 4).
+// MFMA v_mfma_f32_16x16x4_f32: the operand layout, the tile product and the node GEMM are nargnn_tile.h's, shared with
+// nargnn_depot.hip.
 //
 // Where the state lives (rows of kRS = 68 floats: the 16 lanes of one g read 16 distinct bank quads):
 //   tier 0  N <= rl4co_nargnn_lds_nodes(K): x2, x4 and the edge state in LDS; x, x1, x3 in `scratch`
@@ -38,19 +35,18 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "nargnn_tile.h"
 
 namespace {
 
-constexpr int kD = 64;
-constexpr int kRS = kD + 4;
+using namespace rl4co::nargnn;  // kD, kRS, f32x4, sigmoidf, siluf, load_wfrags, gemm_tile, node_gemm
+
 constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
 constexpr int kCuLds = 160 * 1024;
 constexpr int kStaticLds = 64;
 constexpr int kHeadBytes = 64;
 constexpr int kNodeLdsMax = 300;  // tier 1: 64 + 2 * 300 * 272 + 64 <= 160 KiB
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __host__ __device__ constexpr int64_t lds_bytes(int tier, int N, int K) {
   const int64_t rows = tier == 0 ? 2 * (int64_t)N + (int64_t)N * K : (tier == 1 ? 2 * (int64_t)N : 0);
@@ -63,59 +59,6 @@ __host__ __device__ constexpr int64_t scratch_floats(int tier, int N, int K) {
 inline int tier_of(int N, int K) {
   if (lds_bytes(0, N, K) + kStaticLds <= kCuLds) return 0;
   return N <= kNodeLdsMax ? 1 : 2;
-}
-
-__device__ inline float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ inline float siluf(float x) { return x / (1.0f + expf(-x)); }
-
-__device__ inline f32x4 mfma4(float a, float b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// the wave's copy of one 64 x 64 weight, row-major [out][in]: fragment [ct][j] of lane (c, g) is W[16 ct + c][16 j + 4 g ..]
-__device__ inline void load_wfrags(f32x4 (&wf)[4][4], const float* W, int lane) {
-  const float* row = W + (lane & 15) * kD + 4 * (lane >> 4);
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wf[ct][j] = *reinterpret_cast<const f32x4*>(row + 16 * ct * kD + 16 * j);
-}
-
-// acc[ct] = (16 rows) . W^T for the four column tiles; `arow` is the lane's row c at float 4 g
-__device__ inline void gemm_tile(f32x4 (&acc)[4], const f32x4 (&wf)[4][4], const float* arow) {
-  f32x4 a[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) a[j] = *reinterpret_cast<const f32x4*>(arow + 16 * j);
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) acc[ct] = mfma4(a[j][s], wf[ct][j][s], acc[ct]);
-}
-
-// Y[n] = X[n] . W^T + bias for the node tiles tile0, tile0 + 2, ...
-__device__ inline void node_gemm(float* Y, const float* X, const float* W, const float* bias, int N, int tile0, int lane) {
-  const int c = lane & 15, g = lane >> 4;
-  f32x4 wf[4][4];
-  load_wfrags(wf, W, lane);
-  float bcol[4];
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) bcol[ct] = bias[16 * ct + c];
-  const int tiles = (N + 15) >> 4;
-  for (int t = tile0; t < tiles; t += 2) {
-    const int row = min(16 * t + c, N - 1);  // rows past N repeat the last node and are not stored
-    f32x4 acc[4];
-    gemm_tile(acc, wf, X + row * kRS + 4 * g);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int n = 16 * t + 4 * g + r;
-      if (n < N) {
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) Y[n * kRS + 16 * ct + c] = acc[ct][r] + bcol[ct];
-      }
-    }
-  }
 }
 
 template <int TIER>

@@ -704,6 +704,105 @@ def nargnn_heatmap(locs: Tensor, neighbors: Tensor, edge_cost: Tensor, *, init_w
     return heatmap, node_embed
 
 
+def nargnn_depot_lds_nodes(k: int) -> int:
+    """Largest node count (depot included) at which the depot-graph heatmap encoder keeps its (N - 1)(k + 2) edge rows in
+    LDS."""
+    return int(_lib.lib().rl4co_nargnn_depot_lds_nodes(int(k)))
+
+
+def nargnn_depot_heatmap(locs: Tensor, feats: Tensor, neighbors: Tensor, edge_cost: Tensor, depot_cost: Tensor, *,
+                         init_w: Tensor, init_b: Tensor, depot_w: Tensor, depot_b: Tensor, edge_w: Tensor, edge_b: Tensor,
+                         lin_w: Tensor | None, lin_b: Tensor | None, bn: Tensor | None, mlp_w: Tensor | None,
+                         mlp_b: Tensor | None, out_w: Tensor, out_b: Tensor | None, small_value: float = 1e-12,
+                         fill_value: float | None = None, n_workgroups: int | None = None, err: Tensor | None = None):
+    """DeepACO's heatmap encoder for the depot graphs of CVRP, OP and PCTSP in one launch (rl4co_nargnn_depot_heatmap),
+    fp32.
+
+    ``locs`` [B, N, 2] (node 0 the depot), ``feats`` [B, N - 1, F] with F in {1, 2}, ``neighbors`` [B, N - 1, K] int32
+    (customer u's customer neighbours, values in 1 .. N - 1), ``edge_cost`` [B, N - 1, K], ``depot_cost`` [B, N - 1] (the
+    distance between customer u and the depot, for both directions); ``init_w`` [64, 2 + F], ``init_b`` [64], ``depot_w``
+    [64, 2], ``depot_b`` [64]; every other parameter as :func:`nargnn_heatmap` takes it. Returns ``(heatmap_logits
+    [B, N, N], node_embed [B, N, 64])``. With ``err`` the sticky bits are OR-ed into the caller's word and nothing is
+    synchronised; without it the word is read back and a neighbour index outside [1, N) raises."""
+    if locs.dim() != 3 or locs.shape[2] != 2:
+        raise ValueError(f"locs must be [B, N, 2], got {tuple(locs.shape)}")
+    b, n, _ = locs.shape
+    c = n - 1
+    if feats.dim() != 3 or tuple(feats.shape[:2]) != (b, c):
+        raise ValueError(f"feats must be [B, N - 1, F] = [{b}, {c}, F], got {tuple(feats.shape)}")
+    f = feats.shape[2]
+    if neighbors.dim() != 3 or tuple(neighbors.shape[:2]) != (b, c):
+        raise ValueError(f"neighbors must be [B, N - 1, K] = [{b}, {c}, K], got {tuple(neighbors.shape)}")
+    k = neighbors.shape[2]
+    if tuple(edge_cost.shape) != (b, c, k):
+        raise ValueError(f"edge_cost must be [B, N - 1, K] = {(b, c, k)}, got {tuple(edge_cost.shape)}")
+    if tuple(depot_cost.shape) != (b, c):
+        raise ValueError(f"depot_cost must be [B, N - 1] = {(b, c)}, got {tuple(depot_cost.shape)}")
+    if init_w.dim() != 2 or init_w.shape[1] != 2 + f:
+        raise ValueError(f"init_w must be [D, 2 + F] = [D, {2 + f}], got {tuple(init_w.shape)}")
+    d = init_w.shape[0]
+    if d != 64:
+        raise NotImplementedError(f"nargnn_depot_heatmap serves embed_dim = 64 only, got {d}")
+    if f not in (1, 2):
+        raise NotImplementedError(f"nargnn_depot_heatmap serves F = 1 or 2 customer features, got {f}")
+    if b < 1 or not 3 <= n <= 1024 or not 1 <= k <= min(n - 2, 256):
+        raise NotImplementedError(f"nargnn_depot_heatmap serves B >= 1, 3 <= N <= 1024 and 1 <= K <= min(N - 2, 256), got "
+                                  f"B = {b}, N = {n}, K = {k}")
+    layers = 0 if lin_w is None else lin_w.shape[0]
+    if layers and (lin_b is None or bn is None):
+        raise ValueError("lin_w needs lin_b and bn")
+    hidden = 0 if mlp_w is None else mlp_w.shape[0]
+    want = {"init_b": (init_b, (d,)), "depot_w": (depot_w, (d, 2)), "depot_b": (depot_b, (d,)), "edge_b": (edge_b, (d,)),
+            "lin_w": (lin_w, (layers, 5, d, d)), "lin_b": (lin_b if layers else None, (layers, 5, d)),
+            "bn": (bn if layers else None, (layers, 2, 2, d)), "mlp_w": (mlp_w, (hidden, d, d)),
+            "mlp_b": (mlp_b, (hidden, d)), "out_b": (out_b, (1,))}
+    for name, (t, shape) in want.items():
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    if mlp_b is not None and hidden == 0:
+        mlp_b = None
+    edge_w, out_w = edge_w.reshape(-1), out_w.reshape(-1)
+    if edge_w.numel() != d or out_w.numel() != d:
+        raise ValueError(f"edge_w and out_w must hold {d} values, got {edge_w.numel()} and {out_w.numel()}")
+    locs = _dev(locs, torch.float32, "locs")
+    feats = _dev(feats, torch.float32, "feats")
+    neighbors = _dev(neighbors, torch.int32, "neighbors")
+    edge_cost = _dev(edge_cost, torch.float32, "edge_cost")
+    depot_cost = _dev(depot_cost, torch.float32, "depot_cost")
+    named = dict(init_w=init_w, init_b=init_b, depot_w=depot_w, depot_b=depot_b, edge_w=edge_w, edge_b=edge_b,
+                 lin_w=lin_w if layers else None, lin_b=lin_b if layers else None, bn=bn if layers else None,
+                 mlp_w=mlp_w if hidden else None, mlp_b=mlp_b, out_w=out_w, out_b=out_b)
+    named = {key: (None if t is None else _dev(t, torch.float32, key)) for key, t in named.items()}
+    dev = locs.device
+    if fill_value is None:
+        fill_value = float(torch.log(torch.tensor(small_value, dtype=torch.float32)))
+    per_wg = int(_lib.lib().rl4co_nargnn_depot_scratch_bytes(n, k))
+    if n_workgroups is None:  # one workgroup per CU (eight waves above 128 VGPRs: a second one does not fit), within the cap
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        n_workgroups = min(b, cus, max(1, _NARGNN_SCRATCH_CAP // per_wg))
+    if not 1 <= n_workgroups <= b:
+        raise ValueError(f"n_workgroups must be in [1, B = {b}], got {n_workgroups}")
+    scratch = torch.empty(n_workgroups * per_wg // 4, dtype=torch.float32, device=dev)
+    heatmap = torch.empty((b, n, n), dtype=torch.float32, device=dev)
+    node_embed = torch.empty((b, n, d), dtype=torch.float32, device=dev)
+    own = err is None
+    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
+    a = _lib.NargnnDepotArgs()
+    a.B, a.N, a.K, a.F, a.D, a.L, a.H, a.n_workgroups = b, n, k, f, d, layers, hidden + 1, int(n_workgroups)
+    a.small_value, a.fill_value = float(small_value), float(fill_value)
+    a.locs, a.feats, a.neighbors, a.edge_cost, a.depot_cost = (_ptr(locs), _ptr(feats), _ptr(neighbors), _ptr(edge_cost),
+                                                               _ptr(depot_cost))
+    for key, t in named.items():
+        setattr(a, key, _ptr(t))
+    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * 4
+    a.heatmap, a.node_embed, a.err = _ptr(heatmap), _ptr(node_embed), _ptr(err)
+    st = _lib.lib().rl4co_nargnn_depot_heatmap(C.byref(a), _stream())
+    _lib.check(st, "rl4co_nargnn_depot_heatmap")
+    if own:
+        raise_if_error(err)
+    return heatmap, node_embed
+
+
 def aco_lds_nodes() -> int:
     """Largest node count at which the Ant System kernel keeps logits and pheromone in LDS (a host query)."""
     return int(_lib.lib().rl4co_aco_tsp_lds_nodes())

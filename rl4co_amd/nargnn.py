@@ -2,7 +2,9 @@
 anisotropic edge-gated GNN of models/nn/graph/gnn.py, the ``EdgeHeatmapGenerator`` MLP) in inference as ONE kernel launch
 (``rl4co_nargnn_heatmap``, csrc/nargnn.hip), and the val / test path of ``DeepACOPolicy.forward``
 (models/zoo/deepaco/policy.py:122-127, 165-184) on top of it and of :class:`rl4co_amd.aco.AntSystem`: instance -> heatmap ->
-ants -> tours, all on the device.
+ants -> tours, all on the device. ``NARGNNDepotEncoder`` is the same encoder for CVRP, OP and PCTSP, whose graph has a
+depot (``CVRPEdgeEmbedding``: every customer's nearest customers plus the depot, the depot to every customer), on
+``rl4co_nargnn_depot_heatmap`` (csrc/nargnn_depot.hip).
 
 The modules carry the reference's ``state_dict`` keys (``graph_network.layers.{i}.v_bn.module.*`` is how PyG's
 ``BatchNorm`` wraps ``BatchNorm1d``), so a reference checkpoint loads with ``load_state_dict(strict=True)``. The neighbour
@@ -94,6 +96,9 @@ def _fold_batch_norm(bn: nn.BatchNorm1d) -> Tensor:
 class NARGNNEncoder(nn.Module):
     """encoder.py:96-193 for TSP in inference: ``forward(td)`` returns ``(heatmap_logits [B, N, N], node_embed [B, N, D])``."""
 
+    ENVS: tuple = ("tsp",)  # what the class's kernel serves
+    KERNEL = "rl4co_nargnn_heatmap"
+
     def __init__(self, embed_dim: int = 64, env_name: str = "tsp", init_embedding: nn.Module | None = None,
                  edge_embedding: nn.Module | None = None, graph_network: nn.Module | None = None,
                  heatmap_generator: nn.Module | None = None, num_layers_heatmap_generator: int = 5,
@@ -106,31 +111,40 @@ class NARGNNEncoder(nn.Module):
         given = dict(init_embedding=init_embedding, edge_embedding=edge_embedding, graph_network=graph_network,
                      heatmap_generator=heatmap_generator)
         self.custom = [name for name, module in given.items() if module is not None]
-        self.init_embedding = _TSPInitEmbedding(embed_dim) if init_embedding is None else init_embedding
+        self.init_embedding = self._own_init_embedding(embed_dim) if init_embedding is None else init_embedding
         self.edge_embedding = _TSPEdgeEmbedding(embed_dim, k_sparse=k_sparse) if edge_embedding is None else edge_embedding
         self.graph_network = (_GNNEncoder(num_layers_graph_encoder, embed_dim) if graph_network is None else graph_network)
         self.heatmap_generator = (_EdgeHeatmapGenerator(embed_dim, num_layers_heatmap_generator, linear_bias)
                                   if heatmap_generator is None else heatmap_generator)
         self._packed: tuple | None = None  # (key, tensors): the kernel's view of the parameters, rebuilt when one changes
 
+    def _own_init_embedding(self, embed_dim: int) -> nn.Module:
+        return _TSPInitEmbedding(embed_dim)
+
+    def _extra_parameters(self, f32) -> dict:
+        """What a subclass's kernel reads beyond ``rl4co_nargnn_args``' parameters."""
+        return {}
+
     # ---- what the kernel serves -------------------------------------------------------------------------------------------
     def _check(self, locs: Tensor) -> None:
+        me = type(self).__name__
         if self.training:
-            raise NotImplementedError("NARGNNEncoder serves inference only: a training-mode batch norm needs the statistics "
+            raise NotImplementedError(f"{me} serves inference only: a training-mode batch norm needs the statistics "
                                       "of the whole batch (call .eval())")
         if self.custom:
-            raise NotImplementedError(f"NARGNNEncoder serves its own sub-modules only, got a custom {', '.join(self.custom)}")
-        if self.env_name != "tsp":
-            raise NotImplementedError(f"NARGNNEncoder serves the tsp environment only (the regular k-nearest graph), got "
+            raise NotImplementedError(f"{me} serves its own sub-modules only, got a custom {', '.join(self.custom)}")
+        if self.env_name not in self.ENVS:
+            raise NotImplementedError(f"{me} serves the {' / '.join(self.ENVS)} environment only (NARGNNEncoder: the regular "
+                                      f"k-nearest graph; NARGNNDepotEncoder: the depot graphs of cvrp, op and pctsp), got "
                                       f"{self.env_name!r}")
         if self.act_fn != "silu":
-            raise NotImplementedError(f"NARGNNEncoder serves act_fn='silu' only, got {self.act_fn!r}")
+            raise NotImplementedError(f"{me} serves act_fn='silu' only, got {self.act_fn!r}")
         if self.agg_fn != "mean":
-            raise NotImplementedError(f"NARGNNEncoder serves agg_fn='mean' only, got {self.agg_fn!r}")
+            raise NotImplementedError(f"{me} serves agg_fn='mean' only, got {self.agg_fn!r}")
         if self.embed_dim != 64:
-            raise NotImplementedError(f"NARGNNEncoder serves embed_dim=64 only, got {self.embed_dim}")
+            raise NotImplementedError(f"{me} serves embed_dim=64 only, got {self.embed_dim}")
         if not locs.is_cuda:
-            raise NotImplementedError(f"NARGNNEncoder runs inside the MI355X kernel (rl4co_nargnn_heatmap) only: td['locs'] "
+            raise NotImplementedError(f"{me} runs inside the MI355X kernel ({self.KERNEL}) only: td['locs'] "
                                       f"on {locs.device}")
 
     def packed_parameters(self, device) -> dict:
@@ -158,6 +172,7 @@ class NARGNNEncoder(nn.Module):
             p["mlp_w"] = f32(torch.stack([m.weight for m in gen.linears], 0))
             if gen.linears[0].bias is not None:
                 p["mlp_b"] = f32(torch.stack([m.bias for m in gen.linears], 0))
+        p.update(self._extra_parameters(f32))
         self._packed = (key, p)
         return p
 
@@ -176,6 +191,68 @@ class NARGNNEncoder(nn.Module):
         locs = locs.detach().to(torch.float32).contiguous()
         neighbors, cost = self.neighbors(locs)
         return K.nargnn_heatmap(locs, neighbors, cost, small_value=SMALL_VALUE, **self.packed_parameters(locs.device))
+
+
+class _DepotInitEmbedding(nn.Module):
+    """env_embeddings/init.py: VRPInitEmbedding (115-136), PCTSPInitEmbedding (221-251), OPInitEmbedding (254-280): one
+    linear over (x, y, features) for the customers, one over (x, y) for the depot."""
+
+    def __init__(self, embed_dim: int, node_dim: int, linear_bias: bool = True):
+        super().__init__()
+        self.init_embed = nn.Linear(node_dim, embed_dim, linear_bias)
+        self.init_embed_depot = nn.Linear(2, embed_dim, linear_bias)
+
+
+def _depot_features(env_name: str, td) -> Tensor:
+    """The customers' features behind their coordinates, [B, N - 1, F], in the reference's order."""
+    if env_name == "cvrp":
+        return td["demand"][..., None]
+    if env_name == "op":
+        return td["prize"][..., 1:, None]
+    return torch.stack((td["expected_prize"], td["penalty"][..., 1:]), -1)
+
+
+DEPOT_ENVS = {"cvrp": 1, "op": 1, "pctsp": 2}  # environment -> F, the customer features behind the coordinates
+
+
+class NARGNNDepotEncoder(NARGNNEncoder):
+    """encoder.py:96-193 for CVRP, OP and PCTSP in inference, on ``rl4co_nargnn_depot_heatmap``: the graph of
+    ``CVRPEdgeEmbedding`` (every customer's nearest customers plus the depot, the depot to every customer)."""
+
+    ENVS = tuple(DEPOT_ENVS)
+    KERNEL = "rl4co_nargnn_depot_heatmap"
+
+    def __init__(self, embed_dim: int = 64, env_name: str = "cvrp", **kwargs):
+        super().__init__(embed_dim=embed_dim, env_name=env_name, **kwargs)
+
+    def _own_init_embedding(self, embed_dim: int) -> nn.Module:
+        return _DepotInitEmbedding(embed_dim, 2 + DEPOT_ENVS.get(self.env_name, 1))
+
+    def _extra_parameters(self, f32) -> dict:
+        depot = self.init_embedding.init_embed_depot
+        return dict(depot_w=f32(depot.weight), depot_b=f32(depot.bias))
+
+    def neighbors(self, locs: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+        """edge.py:125-163 for the whole batch: (neighbors [B, C, K] int32 with values in 1 .. N - 1, edge_cost [B, C, K],
+        depot_cost [B, C]). The selection runs on the customer block of the distance matrix; k comes from N with the depot."""
+        n = locs.shape[1]
+        cost = (locs[..., :, None, :] - locs[..., None, :, :]).norm(p=2, dim=-1)
+        depot_cost = cost[:, 1:, 0].contiguous()
+        block = cost[:, 1:, 1:].clone()
+        block.diagonal(dim1=1, dim2=2).fill_(torch.inf)
+        k = max(n // 5, 10) if self.edge_embedding.k_sparse is None else int(self.edge_embedding.k_sparse)
+        values, indices = torch.topk(block, k=min(k, n - 2), dim=-1, largest=False, sorted=False)
+        return (indices + 1).to(torch.int32).contiguous(), values.contiguous(), depot_cost
+
+    @torch.no_grad()
+    def forward(self, td):
+        locs = td["locs"]
+        self._check(locs)
+        locs = locs.detach().to(torch.float32).contiguous()
+        feats = _depot_features(self.env_name, td).detach().to(torch.float32).contiguous()
+        neighbors, cost, depot_cost = self.neighbors(locs)
+        return K.nargnn_depot_heatmap(locs, feats, neighbors, cost, depot_cost, small_value=SMALL_VALUE,
+                                      **self.packed_parameters(locs.device))
 
 
 def _merge_with_defaults(value, **defaults) -> dict:
@@ -203,7 +280,7 @@ class DeepACOPolicy(nn.Module):
         if top_k > 0 or top_p > 0:
             raise NotImplementedError(f"top_k / top_p filtering of the heatmap is not served (top_k={top_k}, top_p={top_p})")
         if encoder is None:
-            encoder = NARGNNEncoder(env_name=env_name, **encoder_kwargs)
+            encoder = (NARGNNDepotEncoder if env_name in DEPOT_ENVS else NARGNNEncoder)(env_name=env_name, **encoder_kwargs)
         self.encoder = encoder
         self.env_name = env_name
         self.temperature = temperature
