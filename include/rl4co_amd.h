@@ -53,8 +53,10 @@ extern "C" {
  *      rl4co_nargnn_args).
  *  22: rl4co_aco_prize / rl4co_aco_prize_lds_nodes (the Ant System search for OP and PCTSP, rl4co_aco_prize_args).
  *  23: rl4co_nargnn_depot_heatmap / rl4co_nargnn_depot_lds_nodes / rl4co_nargnn_depot_scratch_bytes (the heatmap encoder
- *      for the depot graphs of CVRP, OP and PCTSP, rl4co_nargnn_depot_args). */
-#define RL4CO_ABI_VERSION 23
+ *      for the depot graphs of CVRP, OP and PCTSP, rl4co_nargnn_depot_args).
+ *  24: rl4co_aco_tsp_logp_grad / rl4co_aco_tsp_grad_lds_entries (the backward of the ants' log-likelihoods with respect
+ *      to the heatmap, DeepACO's training path, rl4co_aco_tsp_grad_args). */
+#define RL4CO_ABI_VERSION 24
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -655,6 +657,42 @@ typedef struct rl4co_aco_tsp_args {
 int rl4co_aco_tsp(const rl4co_aco_tsp_args* args, void* stream);
 /* Largest N at which rl4co_aco_tsp keeps the logits and the pheromone in LDS (the kernel's LDS budget, aco_tsp.hip header). */
 int rl4co_aco_tsp_lds_nodes(void);
+
+/* --------------------------------------------------------------------------
+ * The backward of rl4co_aco_tsp's SAMPLE phase with alpha = beta = 1 and a pheromone of ones (DeepACO's training path,
+ * models/zoo/deepaco/policy.py:138-163): the gradient of the ants' log-likelihoods with respect to the heatmap, fp32, one
+ * launch (aco_tsp_grad.hip). Rows are ant-major as above. For the ant of row r = j * B + b with tour a_0 .. a_{N-1} and
+ * step t = 1 .. N - 1: i = a_{t-1}, F = the nodes not among a_0 .. a_{t-1}, p = softmax(heatmap[b, i, F] / temperature) in
+ * rl4co_aco_tsp's own order of operations (p_n = exp of the log-prob the forward reports),
+ * g = grad_ll[r] + grad_steps[r, t], and for n in F
+ *   grad_heatmap[b, i, n] += g * ((n == a_t) - p_n) / temperature.
+ * Every word of grad_heatmap is written (0 where nothing contributes: the diagonal, the rows of refused instances). Each
+ * word is a sum over the ants in ascending order: two launches, and any row_split, give identical bits. A step whose feasible
+ * logits are all -inf contributes nothing; a -inf logit among finite ones gets gradient 0.
+ * Grid B x row_split: workgroup s of an instance takes the heatmap rows i = s (mod row_split).
+ * Per instance, before anything is read through an action: an action outside [0, N) sets RL4CO_EBIT_TOUR_INDEX, a row that
+ * is not a permutation of 0 .. N - 1 sets RL4CO_EBIT_INVALID_TOUR; that instance's gradient is all zeros.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_aco_tsp_grad_args {
+  int32_t B;                /* instances, >= 1                                              */
+  int32_t N;                /* nodes, 2 .. 1024                                             */
+  int32_t n_ants;           /* >= 1; n_ants * B <= 2^31 - 1                                 */
+  int32_t row_split;        /* workgroups per instance, 1 .. N                              */
+  float temperature;        /* > 0; the forward's                                           */
+  int32_t reserved0;        /* 0                                                            */
+  const float* heatmap;     /* [B,N,N] the logits the forward sampled from (not divided)    */
+  const int64_t* actions;   /* [rows,N] the ants' tours                                     */
+  const float* grad_ll;     /* [rows] upstream gradient of each row's summed log-likelihood */
+  const float* grad_steps;  /* [rows,N] upstream gradient of the per-step log-probs or NULL; column 0 is ignored */
+  uint16_t* pos_scratch;    /* [B*row_split,n_ants,N]; required when n_ants * N > rl4co_aco_tsp_grad_lds_entries(); used
+                               whenever it is not NULL                                      */
+  float* grad_heatmap;      /* [B,N,N] out                                                  */
+  int32_t* err;             /* sticky error bits                                            */
+} rl4co_aco_tsp_grad_args;
+
+int rl4co_aco_tsp_logp_grad(const rl4co_aco_tsp_grad_args* args, void* stream);
+/* Largest n_ants * N whose inverse-permutation table rl4co_aco_tsp_logp_grad keeps in LDS (aco_tsp_grad.hip header). */
+int rl4co_aco_tsp_grad_lds_entries(void);
 
 /* --------------------------------------------------------------------------
  * Ant System search on a heatmap for CVRP (the same reference class with CVRPEnv) as ONE launch, one workgroup per

@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 23  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 24  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -168,6 +168,16 @@ class AcoTspArgs(C.Structure):
     ]
 
 
+class AcoTspGradArgs(C.Structure):
+    """Mirror of ``struct rl4co_aco_tsp_grad_args`` (field order and types must match the header)."""
+
+    _fields_ = [
+        ("B", _i32), ("N", _i32), ("n_ants", _i32), ("row_split", _i32), ("temperature", _f32), ("reserved0", _i32),
+        ("heatmap", _vp), ("actions", _vp), ("grad_ll", _vp), ("grad_steps", _vp), ("pos_scratch", _vp),
+        ("grad_heatmap", _vp), ("err", _vp),
+    ]
+
+
 class AcoCvrpArgs(C.Structure):
     """Mirror of ``struct rl4co_aco_cvrp_args`` (field order and types must match the header)."""
 
@@ -302,6 +312,8 @@ SYMBOLS = {
     "rl4co_tsp_two_opt_lds_nodes": (C.c_int, []),
     "rl4co_aco_tsp": (C.c_int, [C.POINTER(AcoTspArgs), _vp]),
     "rl4co_aco_tsp_lds_nodes": (C.c_int, []),
+    "rl4co_aco_tsp_logp_grad": (C.c_int, [C.POINTER(AcoTspGradArgs), _vp]),
+    "rl4co_aco_tsp_grad_lds_entries": (C.c_int, []),
     "rl4co_aco_cvrp": (C.c_int, [C.POINTER(AcoCvrpArgs), _vp]),
     "rl4co_aco_cvrp_lds_nodes": (C.c_int, []),
     "rl4co_aco_prize": (C.c_int, [C.POINTER(AcoPrizeArgs), _vp]),

@@ -25,7 +25,11 @@ OP and PCTSP (``env.name`` "op", "pctsp" or "spctsp"; ``rl4co_aco_prize``, csrc/
 ``num_samples == n_ants`` only, no local search (the reference's destroy-and-repair search is not served) and no
 ``multistart``. ``td`` is the environment's reset state: ``prize`` and ``max_length`` (OP), ``real_prize`` and ``penalty``
 (PCTSP; ``real_prize`` is the stochastic prize under ``SPCTSPEnv``). Rows are ``W = n`` wide and zero-filled after each
-row's length, the reward is ``env.get_reward`` on that W-wide row, ``final_actions`` is the ragged list as for CVRP."""
+row's length, the reward is ``env.get_reward`` on that W-wide row, ``final_actions`` is the ragged list as for CVRP.
+
+Training (TSP): :func:`heatmap_rollout` is DeepACO's constructive training decode — the SAMPLE launch of ``rl4co_aco_tsp``
+forward, ``rl4co_aco_tsp_logp_grad`` (csrc/aco_tsp_grad.hip) backward, joined by a ``torch.autograd.Function`` — and
+:func:`deepaco_loss` the model's REINFORCE loss with the shared baseline (deepaco/model.py:79-91)."""
 from __future__ import annotations
 
 from functools import cached_property
@@ -40,6 +44,100 @@ _SERVED_KWARGS = ("multistart", "num_starts", "select_best", "select_start_nodes
 _SERVED_KWARGS_CVRP = _SERVED_KWARGS + ("multisample", "num_samples")
 _SERVED_KWARGS_PRIZE = ("multisample", "num_samples", "select_best", "temperature")
 _PRIZE_ENVS = ("op", "pctsp", "spctsp")  # rl4co_aco_prize; spctsp is pctsp with the stochastic prize in td["real_prize"]
+
+
+class _AntLogLikelihood(torch.autograd.Function):
+    """The ants' per-step log-probs and their sum as functions of the heatmap: the forward is the SAMPLE launch of
+    ``rl4co_aco_tsp`` (pheromone of ones, alpha = beta = 1: ``rl4co_logf(1) == 0`` exactly, so its logits ARE the heatmap),
+    the backward is ``rl4co_aco_tsp_logp_grad``. Nothing is saved unless the heatmap requires a gradient; there is no
+    double backward."""
+
+    @staticmethod
+    def forward(ctx, heatmap, locs, start_nodes, forced, n_ants, temperature, seed, err):
+        out = K.aco_tsp(torch.ones_like(heatmap), n_ants=n_ants, phases=_lib.ACO_SAMPLE, log_heuristic=heatmap, locs=locs,
+                        start_nodes=start_nodes[None].contiguous(), forced_actions=forced, temperature=temperature,
+                        philox_seed=seed, philox_offset=0, err=err)
+        actions, logps, reward = out["actions"], out["logps"], out["reward"]
+        ctx.temperature, ctx.err = temperature, err
+        ctx.set_materialize_grads(False)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(heatmap, actions)
+        ctx.mark_non_differentiable(actions, reward)
+        return logps, logps.sum(1), actions, reward
+
+    @staticmethod
+    def backward(ctx, grad_logps, grad_ll, _grad_actions, _grad_reward):
+        if torch.is_grad_enabled():
+            raise RuntimeError("heatmap_rollout has no double backward: rl4co_aco_tsp_logp_grad is not differentiable "
+                               "(create_graph=True is not served)")
+        heatmap, actions = ctx.saved_tensors
+        if grad_ll is None:
+            grad_ll = torch.zeros(actions.shape[0], dtype=torch.float32, device=heatmap.device)
+        grad_ll = grad_ll.to(torch.float32).contiguous()
+        if grad_logps is not None:
+            grad_logps = grad_logps.to(torch.float32).contiguous()
+        own = ctx.err is None
+        err = K.new_error_word(heatmap.device) if own else ctx.err
+        grad = K.aco_tsp_logp_grad(heatmap, actions, grad_ll, grad_steps=grad_logps, temperature=ctx.temperature, err=err)
+        if own:
+            _lib.raise_for_error_bits(int(err.item()))
+        return grad, None, None, None, None, None, None, None
+
+
+def heatmap_rollout(heatmap: Tensor, locs: Tensor, *, n_ants: int, start_nodes: Tensor | None = None,
+                    actions: Tensor | None = None, temperature: float = 1.0, seed: int | None = None,
+                    err: Tensor | None = None) -> dict:
+    """DeepACO's constructive training rollout for TSP (``ConstructivePolicy.forward`` under ``NonAutoregressiveDecoder``:
+    ``n_ants`` tours per instance sampled step by step from ``softmax(heatmap[b, current, unvisited] / temperature)``) as
+    ONE launch, with the gradient back to ``heatmap`` [B, N, N] as one more.
+
+    Rows are ant-major: row ``j * B + b`` is ant ``j`` of instance ``b``. ``start_nodes`` int64 [rows] (None: ant ``j``
+    starts at node ``j % N``, TSPEnv's own multistart choice); ``actions`` [rows, N]: these tours are followed and only
+    evaluated (the reference's ``forced_actions``). Returns ``actions`` [rows, N], ``logps`` [rows, N] (column 0 is 0),
+    ``log_likelihood`` [rows] and ``reward`` [rows] (bit-equal to ``TSPEnv.get_reward``); ``logps`` and
+    ``log_likelihood`` carry the gradient when ``heatmap.requires_grad``. ``seed``: the Philox key (None: drawn from
+    torch's CPU generator). ``err``: the caller's sticky error word, both launches OR into it and nothing is synchronised;
+    None: the forward launch reads its own word back and a set bit raises, and so does the backward launch."""
+    for name, t in (("heatmap", heatmap), ("locs", locs)):
+        if not t.is_cuda:
+            raise NotImplementedError(f"heatmap_rollout runs inside the MI355X kernel (rl4co_aco_tsp) only: {name} on {t.device}")
+    if heatmap.dim() != 3 or heatmap.shape[1] != heatmap.shape[2]:
+        raise ValueError(f"heatmap must be [B, N, N], got {tuple(heatmap.shape)}")
+    b, n, _ = heatmap.shape
+    n_ants = int(n_ants)
+    rows = n_ants * b
+    dev = heatmap.device
+    heatmap = heatmap.to(torch.float32).contiguous()
+    locs = locs.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if actions is not None:
+        actions = actions.detach().to(device=dev, dtype=torch.int64).contiguous()
+        if tuple(actions.shape) != (rows, n):
+            raise ValueError(f"actions must be {(rows, n)}, got {tuple(actions.shape)}")
+        start_nodes = actions[:, 0]
+    elif start_nodes is None:
+        start_nodes = (torch.arange(n_ants, device=dev) % n).repeat_interleave(b)
+    start_nodes = start_nodes.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    if start_nodes.shape[0] != rows:
+        raise ValueError(f"start_nodes must be [n_ants * B] = [{rows}], got {tuple(start_nodes.shape)}")
+    if seed is None:
+        seed = int(torch.randint(0, 2**62, (1,)).item())
+    # err goes through as it is: with None the forward launch (K.aco_tsp) and the backward launch each read their own word
+    logps, ll, acts, reward = _AntLogLikelihood.apply(heatmap, locs, start_nodes, actions, n_ants, float(temperature),
+                                                      int(seed), err)
+    return {"actions": acts, "logps": logps, "log_likelihood": ll, "reward": reward}
+
+
+def deepaco_loss(out: dict, train_with_local_search: bool = False, ls_reward_aug_W: float = 0.95) -> Tensor:
+    """deepaco/model.py:79-91: REINFORCE with the mean over an instance's ants as the shared baseline; with local search
+    the advantage is ``(1 - W)`` of the sampled tours' and ``W`` of the improved tours'. ``out``: ``reward``,
+    ``log_likelihood`` and (local search) ``ls_reward``, each [B, n_ants]."""
+    reward = out["reward"]
+    advantage = reward - reward.mean(dim=1, keepdim=True)
+    if train_with_local_search:
+        ls_reward = out["ls_reward"]
+        ls_advantage = ls_reward - ls_reward.mean(dim=1, keepdim=True)
+        advantage = advantage * (1 - ls_reward_aug_W) + ls_advantage * ls_reward_aug_W
+    return -(advantage * out["log_likelihood"]).mean()
 
 
 class AntSystem:

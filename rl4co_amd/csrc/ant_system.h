@@ -1,7 +1,8 @@
 // ant_system.h — what the Ant System kernels (aco_tsp.hip, aco_cvrp.hip, aco_prize.hip) share, stated once: the constants and the scratch
 // words, the index pre-check, stage A (the logits), one sampling step of one wave, stage U (record, reward map, pheromone)
 // and the host side (launch, the LDS-tier search, the argument checks common to both entry points). A kernel keeps its
-// LDS layout, its per-ant state, its tour / actions / logps stores and its R stage (lds_tour_reward.h).
+// LDS layout, its per-ant state, its tour / actions / logps stores and its R stage (lds_tour_reward.h). aco_tsp_grad.hip (the
+// backward of the ants' log-likelihoods) takes the constants, the index pre-check, the log-softmax statistics and the launch.
 // Thread layout of both: one workgroup of kWaves waves per instance, one wave per ant, lane l owns nodes l, l + 64, ...
 // Every floating-point expression below is part of the parity contract (-ffp-contract=off; tests compare bit for bit).
 #pragma once
@@ -67,6 +68,38 @@ __device__ inline void build_logits(float* Lm, const float* Pm, const float* heu
   }
 }
 
+// The two statistics of a masked log-softmax in the project's order: log_softmax_max, the max butterfly over the feasible
+// logits, and log_softmax_lse = rl4co_logf of the butterfly of the lane-strided (ascending k) sum of rl4co_expf(z - zmax);
+// lp[n] = (z - zmax) - lse.
+// z(k, n) is the logit of node n = lane + 64 k, already divided by the temperature; it is asked only where n < N and
+// feasible(k). `nan_seen`: a feasible logit of THIS lane is NaN. Stated once for ant_step and for the backward
+// (aco_tsp_grad.hip), which therefore sees the probabilities the forward's log-probs report.
+template <typename ZFn, typename FeasFn>
+__device__ inline float log_softmax_max(int N, int K, int lane, ZFn z, FeasFn feasible, bool& nan_seen) {
+  nan_seen = false;
+  float zmax = kNegInf;
+  for (int k = 0; k < K; ++k) {
+    const int n = lane + 64 * k;
+    if (n < N && feasible(k)) {
+      const float zn = z(k, n);
+      nan_seen |= zn != zn;
+      zmax = fmaxf(zmax, zn);
+    }
+  }
+  return rl4co::bfly_max<1, 64>(zmax);
+}
+
+template <typename ZFn, typename FeasFn>
+__device__ inline float log_softmax_lse(int N, int K, int lane, ZFn z, FeasFn feasible, float zmax) {
+  float zsum = 0.0f;
+  for (int k = 0; k < K; ++k) {
+    const int n = lane + 64 * k;
+    if (n < N && feasible(k)) zsum = zsum + rl4co_expf(z(k, n) - zmax);
+  }
+  zsum = rl4co::bfly_sum<1, 64>(zsum);
+  return rl4co_logf(zsum);
+}
+
 // One sampling step of one wave: row `lrow` of L over the nodes of `feas` (bit k of a lane: node lane + 64 k is feasible;
 // bits of nodes >= N are not read), divided by `temp` when it is not 1, log-softmax in the project's order (max butterfly,
 // lane-strided sum of rl4co_expf, butterfly, rl4co_logf), then the argmax over feasible n of lp[n] - ln_noise[n], lowest
@@ -79,32 +112,18 @@ __device__ inline void build_logits(float* Lm, const float* Pm, const float* heu
 __device__ inline int ant_step(const float* lrow, int N, int K, int lane, uint32_t feas, float temp, int forced, float* alp,
                                const float* lnz, unsigned long long seed, uint64_t counter, uint32_t row, float& logp,
                                uint32_t& errbits) {
-  bool nan_seen = false;
-  float zmax = kNegInf;
-  for (int k = 0; k < K; ++k) {
-    const int n = lane + 64 * k;
-    if (n < N && ((feas >> k) & 1u)) {
-      float z = lrow[n];
-      if (temp != 1.0f) z = z / temp;
-      nan_seen |= z != z;
-      zmax = fmaxf(zmax, z);
-    }
-  }
-  zmax = rl4co::bfly_max<1, 64>(zmax);
+  const auto z_of = [&](int, int n) {
+    float z = lrow[n];
+    if (temp != 1.0f) z = z / temp;
+    return z;
+  };
+  const auto feas_of = [&](int k) { return ((feas >> k) & 1u) != 0; };
+  bool nan_seen;
+  const float zmax = log_softmax_max(N, K, lane, z_of, feas_of, nan_seen);
   if (__any(nan_seen)) errbits |= RL4CO_EBIT_NAN_LOGIT;
   const bool dead = !(zmax > kNegInf);  // every feasible logit is -inf (or NaN): the lowest feasible node is taken
   if (dead) errbits |= RL4CO_EBIT_INFEASIBLE;
-  float zsum = 0.0f;
-  for (int k = 0; k < K; ++k) {
-    const int n = lane + 64 * k;
-    if (n < N && ((feas >> k) & 1u)) {
-      float z = lrow[n];
-      if (temp != 1.0f) z = z / temp;
-      zsum = zsum + rl4co_expf(z - zmax);
-    }
-  }
-  zsum = rl4co::bfly_sum<1, 64>(zsum);
-  const float lse = rl4co_logf(zsum);
+  const float lse = log_softmax_lse(N, K, lane, z_of, feas_of, zmax);
 
   float best = kNegInf, blp = kNegInf;  // best key of this lane, its log-prob (forced: the forced node's)
   int bi = kEmpty;

@@ -900,6 +900,75 @@ def aco_tsp(pheromone: Tensor, *, n_ants: int, phases: int = _lib.ACO_SAMPLE | _
     return out
 
 
+def aco_grad_lds_entries() -> int:
+    """Largest ``n_ants * N`` whose inverse-permutation table the log-likelihood backward keeps in LDS (a host query)."""
+    return int(_lib.lib().rl4co_aco_tsp_grad_lds_entries())
+
+
+def aco_grad_row_split(b: int, n: int, cus: int) -> int:
+    """Workgroups per instance of :func:`aco_tsp_logp_grad` when the caller names none: about two workgroups per CU, at
+    least sixteen heatmap rows per workgroup (each repeats the table build). An estimate, not a measured optimum."""
+    return max(1, min(n // 16, (2 * cus) // b))
+
+
+def aco_tsp_logp_grad(heatmap: Tensor, actions: Tensor, grad_ll: Tensor, *, grad_steps: Tensor | None = None,
+                      temperature: float = 1.0, row_split: int | None = None, pos_in_scratch: bool | None = None,
+                      err: Tensor | None = None) -> Tensor:
+    """The gradient of the ants' log-likelihoods with respect to the heatmap in one launch (rl4co_aco_tsp_logp_grad; the
+    header states the arithmetic): ``heatmap`` [B, N, N] fp32 (the logits the forward sampled from, not divided by the
+    temperature), ``actions`` [rows, N] int64 with rows = n_ants * B ant-major, ``grad_ll`` [rows] fp32 and optionally
+    ``grad_steps`` [rows, N] fp32 (column 0 ignored) -> ``grad_heatmap`` [B, N, N] fp32, every word written.
+
+    ``row_split``: workgroups per instance (None: :func:`aco_grad_row_split`); any value gives the same bits.
+    ``pos_in_scratch``: keep the inverse-permutation table in a global scratch instead of LDS (None: only above
+    :func:`aco_grad_lds_entries`). ``err`` as in :func:`aco_tsp`."""
+    for name, t, dtype in (("heatmap", heatmap, torch.float32), ("actions", actions, torch.int64),
+                           ("grad_ll", grad_ll, torch.float32), ("grad_steps", grad_steps, torch.float32)):
+        if t is not None and t.dtype != dtype:
+            raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    if heatmap.dim() != 3 or heatmap.shape[1] != heatmap.shape[2]:
+        raise ValueError(f"heatmap must be [B, N, N], got {tuple(heatmap.shape)}")
+    b, n, _ = heatmap.shape
+    if not 2 <= n <= 1024:
+        raise NotImplementedError(f"aco_tsp_logp_grad serves 2..1024 nodes, got N = {n}")
+    if actions.dim() != 2 or actions.shape[1] != n or actions.shape[0] == 0 or actions.shape[0] % b:
+        raise ValueError(f"actions must be [n_ants * B, N] = [k * {b}, {n}], got {tuple(actions.shape)}")
+    rows = actions.shape[0]
+    n_ants = rows // b
+    if tuple(grad_ll.shape) != (rows,):
+        raise ValueError(f"grad_ll must be {(rows,)}, got {tuple(grad_ll.shape)}")
+    if grad_steps is not None and tuple(grad_steps.shape) != (rows, n):
+        raise ValueError(f"grad_steps must be {(rows, n)}, got {tuple(grad_steps.shape)}")
+    if not temperature > 0:
+        raise ValueError(f"temperature must be positive, got {temperature}")
+    if row_split is not None and not 1 <= int(row_split) <= n:
+        raise ValueError(f"row_split must be in [1, N = {n}], got {row_split}")
+    _dev(heatmap, None, "heatmap"), _dev(actions, None, "actions"), _dev(grad_ll, None, "grad_ll")
+    if grad_steps is not None:
+        _dev(grad_steps, None, "grad_steps")
+    dev = heatmap.device
+    if row_split is None:
+        row_split = aco_grad_row_split(b, n, torch.cuda.get_device_properties(dev).multi_processor_count)
+    fits = n_ants * n <= aco_grad_lds_entries()
+    if pos_in_scratch is None:
+        pos_in_scratch = not fits
+    elif not pos_in_scratch and not fits:
+        raise ValueError(f"n_ants * N = {n_ants * n} is above the LDS table's {aco_grad_lds_entries()} entries")
+    scratch = torch.empty((b * int(row_split), n_ants, n), dtype=torch.int16, device=dev) if pos_in_scratch else None
+    grad = torch.empty((b, n, n), dtype=torch.float32, device=dev)
+    own = err is None
+    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
+    a = _lib.AcoTspGradArgs()
+    a.B, a.N, a.n_ants, a.row_split, a.temperature, a.reserved0 = b, n, n_ants, int(row_split), float(temperature), 0
+    a.heatmap, a.actions, a.grad_ll, a.grad_steps = _ptr(heatmap), _ptr(actions), _ptr(grad_ll), _ptr(grad_steps)
+    a.pos_scratch, a.grad_heatmap, a.err = _ptr(scratch), _ptr(grad), _ptr(err)
+    st = _lib.lib().rl4co_aco_tsp_logp_grad(C.byref(a), _stream())
+    _lib.check(st, "rl4co_aco_tsp_logp_grad")
+    if own:
+        raise_if_error(err)
+    return grad
+
+
 def aco_cvrp_lds_nodes() -> int:
     """Largest node count (depot included) at which the CVRP Ant System kernel keeps logits and pheromone in LDS."""
     return int(_lib.lib().rl4co_aco_cvrp_lds_nodes())

@@ -20,7 +20,7 @@ import torch
 from torch import Tensor, nn
 
 from . import kernels as K
-from .aco import AntSystem
+from .aco import AntSystem, heatmap_rollout
 
 SMALL_VALUE = 1e-12  # encoder.py:81-82: the fp32 heatmap's guard against log(0)
 
@@ -265,9 +265,12 @@ def _merge_with_defaults(value, **defaults) -> dict:
 
 
 class DeepACOPolicy(nn.Module):
-    """policy.py:22-184, the val / test path: encoder, ``heatmap / temperature``, ``AntSystem.run``. The constructor takes
-    the reference's arguments; ``phase="train"`` (the constructive training path), ``top_k`` / ``top_p`` above 0 and an
-    explicit ``k_sparse`` on the policy (the reference then hands ``top_k`` to the sampler) are refused."""
+    """policy.py:22-184. The val / test path: encoder, ``heatmap / temperature``, ``AntSystem.run``. ``phase="train"`` (the
+    constructive training path, TSP) is served when the caller supplied ``encoder=``, a differentiable module returning
+    ``(heatmap [B, N, N], anything)``: the ants' rollout and its backward are one launch each
+    (:func:`rl4co_amd.aco.heatmap_rollout`); with the policy's own inference-only kernel encoder it is refused. The
+    constructor takes the reference's arguments; ``top_k`` / ``top_p`` above 0 and an explicit ``k_sparse`` on the policy
+    (the reference then hands ``top_k`` to the sampler) are refused."""
 
     def __init__(self, encoder: nn.Module | None = None, env_name: str = "tsp", temperature: float = 1.0, top_p: float = 0.0,
                  top_k: int = 0, aco_class: type | None = None, aco_kwargs: dict = {}, train_with_local_search: bool = False,
@@ -281,6 +284,9 @@ class DeepACOPolicy(nn.Module):
             raise NotImplementedError(f"top_k / top_p filtering of the heatmap is not served (top_k={top_k}, top_p={top_p})")
         if encoder is None:
             encoder = (NARGNNDepotEncoder if env_name in DEPOT_ENVS else NARGNNEncoder)(env_name=env_name, **encoder_kwargs)
+            self._own_encoder = True  # the kernel encoder: inference only, no gradient
+        else:
+            self._own_encoder = False
         self.encoder = encoder
         self.env_name = env_name
         self.temperature = temperature
@@ -310,9 +316,13 @@ class DeepACOPolicy(nn.Module):
         return torch.multinomial(mask.float(), num_starts, replacement=True).view(-1)
 
     def forward(self, td_initial, env=None, phase: str = "train", return_actions: bool = True, **decoding_kwargs):
+        if phase == "train" and not self._own_encoder:
+            return self._forward_train(td_initial, env, return_actions, decoding_kwargs)
         if phase not in ("val", "test"):
+            why = (": its gradient reaches a caller-supplied differentiable encoder= only, the policy's own kernel encoder "
+                   "is inference-only") if phase == "train" else ""
             raise NotImplementedError(f"DeepACOPolicy serves phase='val' and phase='test' (the Ant System search); "
-                                      f"phase={phase!r} is the constructive training path")
+                                      f"phase={phase!r} is the constructive training path{why}")
         n_ants = self.n_ants[phase]
         decoding_kwargs.update(self.default_decoding_kwargs)
         decoding_kwargs.update({"num_starts": n_ants} if "multistart" in self.decode_type else {"num_samples": n_ants})
@@ -330,4 +340,51 @@ class DeepACOPolicy(nn.Module):
         out.update({f"reward_{i:03d}": iter_rewards[i] for i in range(n_iterations)})
         if return_actions:
             out["actions"] = actions
+        return out
+
+    def _forward_train(self, td_initial, env, return_actions: bool, decoding_kwargs: dict) -> dict:
+        """policy.py:138-163 through ``ConstructivePolicy.forward`` for TSP: ``n_ants['train']`` constructive rollouts per
+        instance from the caller's encoder's heatmap in one launch (:func:`rl4co_amd.aco.heatmap_rollout`), the gradient
+        back to the heatmap in one more. The heatmap is not divided by the temperature: the temperature goes to the step."""
+        if self.env_name != "tsp":
+            raise NotImplementedError(f"DeepACOPolicy phase='train' serves env_name='tsp' only (the backward kernel rests on "
+                                      f"a TSP tour being a permutation), got env_name={self.env_name!r}")
+        if decoding_kwargs.pop("actions", None) is not None:
+            raise NotImplementedError("DeepACOPolicy phase='train' does not serve actions= (the reference's 'evaluate' "
+                                      "strategy under multistart)")
+        if decoding_kwargs.pop("return_entropy", False):
+            raise NotImplementedError("DeepACOPolicy phase='train' does not serve return_entropy=True")
+        if not decoding_kwargs.pop("return_sum_log_likelihood", True):
+            raise NotImplementedError("DeepACOPolicy phase='train' does not serve return_sum_log_likelihood=False")
+        return_hidden = decoding_kwargs.pop("return_hidden", True)
+        n_ants = self.n_ants["train"]
+        decoding_kwargs.setdefault("temperature", self.temperature)
+        decoding_kwargs.update(self.default_decoding_kwargs)
+        decoding_kwargs.update({"num_starts": n_ants})
+        if env is None or isinstance(env, str):
+            from .envs import get_env
+
+            env = get_env(self.env_name if env is None else env)
+        # the refusals come before the encoder runs: the search's own check on an empty heatmap on the instances' device
+        # (every decoding keyword it refuses, then CPU tensors)
+        locs = td_initial["locs"]
+        self.aco_class(locs.new_empty((locs.shape[0], 0, 0)), n_ants=n_ants, **self.aco_kwargs)._check(td_initial, env, decoding_kwargs)
+        heatmap, _ = self.encoder(td_initial)
+        aco = self.aco_class(heatmap.detach(), n_ants=n_ants, **self.aco_kwargs)
+        temperature = aco._check(td_initial, env, decoding_kwargs)  # (the encoder's output device)
+        starts = aco._start_nodes(td_initial, env, decoding_kwargs)  # select_start_nodes_fn, called once
+        rolled = heatmap_rollout(heatmap, td_initial["locs"], n_ants=n_ants, start_nodes=starts, temperature=temperature)
+
+        def unbatchify(x):  # [rows] ant-major -> [B, n_ants]
+            return x.view(n_ants, -1).t()
+
+        out = {"reward": unbatchify(rolled["reward"]), "log_likelihood": unbatchify(rolled["log_likelihood"])}
+        if return_actions:
+            out["actions"] = rolled["actions"]
+        if return_hidden:
+            out["hidden"] = heatmap
+        if self.train_with_local_search:
+            self.last_aco = aco
+            _, ls_reward = aco.local_search(td_initial, env, rolled["actions"], decoding_kwargs)
+            out["ls_reward"] = unbatchify(ls_reward)
         return out

@@ -23,6 +23,12 @@ reward after the last iteration. Writes profiles/aco_prize_bench.json unless ``-
 ``--nls`` times one iteration's neural-guided local search (csrc/tsp_nls.hip) instead: 1024 x TSP-100, 20 ants, 5
 perturbations of at most 5 scans; the fused launch against the composition of the 2-opt and reward kernels on the same
 tours (``main_nls``). Writes profiles/aco_nls_bench.json unless ``--out`` says otherwise.
+
+``--train`` times DeepACO's training decode instead (csrc/aco_tsp.hip SAMPLE + csrc/aco_tsp_grad.hip): forward plus
+backward of the ants' log-likelihoods from a free heatmap at TSP-100 x 30 ants, for a batch below (64) and a batch above
+(512) the card's CU count; ``kernels`` (``heatmap_rollout``: two launches) against ``torch_per_step`` (the step loop in
+torch ops with autograd on the same card, what the reference executes), alternating (``main_train``). No threshold: both
+times and their ratio are reported. Writes profiles/aco_train_bench.json unless ``--out`` says otherwise.
 """
 import argparse
 import json
@@ -114,17 +120,22 @@ class Leg:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--batch", type=int, default=None, help="default 4096 (--train: 64 and 512)")
     ap.add_argument("--num-loc", type=int, default=100)
-    ap.add_argument("--ants", type=int, default=48)
+    ap.add_argument("--ants", type=int, default=None, help="default 48 (--train: 30)")
     ap.add_argument("--iterations", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--env", choices=("tsp", "cvrp", "prize"), default="tsp")
     ap.add_argument("--nls", action="store_true", help="time the neural-guided local search instead (TSP)")
+    ap.add_argument("--train", action="store_true", help="time the training decode, forward plus backward, instead (TSP)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("aco_bench needs the MI355X: a time taken anywhere else says nothing")
     dev = torch.device("cuda", 0)
+    if a.train:  # its own defaults: an explicit --ants / --batch is taken as given
+        return main_train(a, dev)
+    a.batch = 4096 if a.batch is None else a.batch
+    a.ants = 48 if a.ants is None else a.ants
     if a.env == "cvrp":
         return main_cvrp(a, dev)
     if a.env == "prize":
@@ -358,6 +369,87 @@ def main_nls(a, dev):
                        what="one iteration's neural-guided local search (host work included), HIP events around the call, "
                             "synchronised; the two legs agree bit for bit",
                        rows=out_rows), f, indent=1)
+
+
+def torch_train_step(heat, locs, n_ants, temperature=1.0):
+    """The reference's training decode from torch ops with autograd, one decoding step at a time (ant-major rows): gather
+    the row, mask, log-softmax, multinomial, gather the log-prob. Returns (log_likelihood [rows], reward [rows])."""
+    b, n, _ = heat.shape
+    rows, dev = n_ants * b, heat.device
+    ar, inst = torch.arange(rows, device=dev), torch.arange(rows, device=dev) % b
+    cur = (ar // b) % n
+    mask = torch.ones(rows, n, dtype=torch.bool, device=dev)
+    mask[ar, cur] = False
+    steps, logps = [cur], []
+    for _t in range(1, n):
+        lp = torch.log_softmax(heat[inst, cur].masked_fill(~mask, float("-inf")) / temperature, -1)
+        cur = torch.multinomial(lp.detach().exp(), 1).squeeze(1)
+        logps.append(lp[ar, cur])
+        mask = mask.clone()
+        mask[ar, cur] = False
+        steps.append(cur)
+    actions = torch.stack(steps, 1)
+    pts = locs[inst[:, None], actions]
+    return torch.stack(logps, 1).sum(1), -(pts.roll(-1, 1) - pts).norm(p=2, dim=-1).sum(1)
+
+
+def main_train(a, dev):
+    """``--train``: forward plus backward of DeepACO's training decode from a free heatmap, per batch size two legs
+    alternating round by round after one warm-up round, HIP events around forward, loss and backward (host work included),
+    synchronised."""
+    from rl4co_amd.aco import deepaco_loss, heatmap_rollout
+
+    n = a.num_loc
+    ants = 30 if a.ants is None else a.ants  # DeepACO trains with 30 ants
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    batches = (64, 512) if a.batch is None else (a.batch,)
+    rows_out = []
+    for batch in batches:
+        g = torch.Generator().manual_seed(1234)
+        locs = torch.rand(batch, n, 2, generator=g).to(dev)
+        dist = (locs[:, :, None] - locs[:, None, :]).norm(p=2, dim=-1)
+        heat = (-torch.log(dist + 1e9 * torch.eye(n, device=dev))).requires_grad_(True)
+        state = {}
+
+        def finish(ll, reward):
+            loss = deepaco_loss({"reward": reward.view(ants, batch).t(), "log_likelihood": ll.view(ants, batch).t()})
+            heat.grad = None
+            loss.backward()
+            state["grad"], state["length"] = heat.grad, -reward.double().mean()
+            return state["grad"]
+
+        def kernels():
+            out = heatmap_rollout(heat, locs, n_ants=ants, seed=1234)
+            return finish(out["log_likelihood"], out["reward"])
+
+        def per_step():
+            return finish(*torch_train_step(heat, locs, ants))
+
+        legs = [Leg("kernels", kernels), Leg("torch_per_step", per_step)]
+        for it in range(a.reps + 1):  # one warm-up round; the legs alternate inside every round
+            for leg in legs:
+                leg.launch(keep=it >= 1)
+        results = []
+        for leg in legs:
+            t = sorted(leg.times)
+            if not bool(torch.isfinite(leg.tours).all()) or float(leg.tours.abs().max()) == 0.0:
+                raise SystemExit(f"aco_bench --train: leg {leg.kind} produced no usable gradient; no time is recorded")
+            results.append(dict(leg=leg.kind, case=f"tsp{n}x{batch}", batch=batch, relation_to_cus=f"{batch} instances, {cus} CUs",
+                                reps=len(t), median_ms=t[len(t) // 2], min_ms=t[0], max_ms=t[-1]))
+        ratio = results[1]["median_ms"] / results[0]["median_ms"]
+        for r in results:
+            r["torch_over_kernels_median"] = ratio
+            rows_out.append(r)
+            print(json.dumps(r), flush=True)
+    out = a.out or "profiles/aco_train_bench.json"
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(dict(device=torch.cuda.get_device_name(0), when=time.strftime("%Y-%m-%d"),
+                       case=f"tsp{n}, {ants} ants, batches {list(batches)}, free heatmap -log(distance)",
+                       what="training decode forward + deepaco_loss + backward to the heatmap (host work included), HIP events "
+                            "around the step, synchronised; torch_per_step is this script's torch loop with autograd on the same "
+                            "card (it draws other tours than the kernel); no threshold was fixed in advance",
+                       rows=rows_out), f, indent=1)
 
 
 if __name__ == "__main__":
