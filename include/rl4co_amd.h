@@ -55,8 +55,10 @@ extern "C" {
  *  23: rl4co_nargnn_depot_heatmap / rl4co_nargnn_depot_lds_nodes / rl4co_nargnn_depot_scratch_bytes (the heatmap encoder
  *      for the depot graphs of CVRP, OP and PCTSP, rl4co_nargnn_depot_args).
  *  24: rl4co_aco_tsp_logp_grad / rl4co_aco_tsp_grad_lds_entries (the backward of the ants' log-likelihoods with respect
- *      to the heatmap, DeepACO's training path, rl4co_aco_tsp_grad_args). */
-#define RL4CO_ABI_VERSION 24
+ *      to the heatmap, DeepACO's training path, rl4co_aco_tsp_grad_args).
+ *  25: rl4co_aco_depot_logp_grad / rl4co_aco_depot_grad_lds_entries / rl4co_aco_depot_grad_scratch_bytes (the same backward
+ *      for the depot graphs of CVRP, OP and PCTSP, rl4co_aco_depot_grad_args). */
+#define RL4CO_ABI_VERSION 25
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -693,6 +695,55 @@ typedef struct rl4co_aco_tsp_grad_args {
 int rl4co_aco_tsp_logp_grad(const rl4co_aco_tsp_grad_args* args, void* stream);
 /* Largest n_ants * N whose inverse-permutation table rl4co_aco_tsp_logp_grad keeps in LDS (aco_tsp_grad.hip header). */
 int rl4co_aco_tsp_grad_lds_entries(void);
+
+/* --------------------------------------------------------------------------
+ * The backward of the SAMPLE phases of rl4co_aco_cvrp and rl4co_aco_prize with alpha = beta = 1 and a pheromone of ones
+ * (DeepACO's training path on the depot graphs): the gradient of the ants' log-likelihoods with respect to the heatmap,
+ * fp32, one launch (aco_depot_grad.hip). N is the heatmap side with the depot as node 0, C = N - 1; rows are ant-major and
+ * W wide as the forward writes them (CVRP W = max(C + 1, 2 C - 1); OP, PCTSP W = N), zero-filled after each row's length.
+ * For the ant of row r = j * B + b and every step t below the row's length (step 0 included; with `multistart` column 0 is
+ * a given customer and contributes nothing): i = the node the ant leaves (the depot for t = 0, else a_{t-1}), F = the
+ * environment's feasible set at that step in the forward's own fp32 expressions, p = softmax(heatmap[b, i, F] /
+ * temperature) in the forward's order of operations, g = grad_ll[r] + grad_steps[r, t], and for n in F
+ *   grad_heatmap[b, i, n] += g * ((n == a_t) - p_n) / temperature.
+ * Every word of grad_heatmap is written (0 where nothing contributes). Each word is a sum in (ant, step) order: two
+ * launches, any row_split and either table tier give identical bits. A step whose feasible logits are all -inf contributes
+ * nothing; a -inf logit among finite ones gets gradient 0.
+ * Grid B x row_split: workgroup s of an instance takes the heatmap rows i = s (mod row_split).
+ * Per instance, before any gradient is written, the rows are replayed once: an action outside [0, N) (or a multistart start
+ * that is the depot) sets RL4CO_EBIT_TOUR_INDEX, a customer taken twice RL4CO_EBIT_INVALID_TOUR, a taken action that is
+ * infeasible under the environment's rule or a row not done after W actions RL4CO_EBIT_INFEASIBLE; that instance's gradient
+ * is all zeros, other instances are untouched.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_aco_depot_grad_args {
+  int32_t env;              /* RL4CO_ENV_CVRP, RL4CO_ENV_OP or RL4CO_ENV_PCTSP                */
+  int32_t B;                /* instances, >= 1                                              */
+  int32_t N;                /* nodes with the depot, 2 .. 1024                              */
+  int32_t n_ants;           /* >= 1; n_ants * B <= 2^31 - 1                                 */
+  int32_t row_split;        /* workgroups per instance, 1 .. N                              */
+  int32_t multistart;       /* CVRP: 1 = column 0 is a given customer start; else 0         */
+  float temperature;        /* > 0; the forward's                                           */
+  int32_t reserved0;        /* 0                                                            */
+  const float* heatmap;     /* [B,N,N] the logits the forward sampled from (not divided)    */
+  const int64_t* actions;   /* [rows,W] the ants' rows                                      */
+  const float* grad_ll;     /* [rows] upstream gradient of each row's summed log-likelihood */
+  const float* grad_steps;  /* [rows,W] upstream gradient of the per-step log-probs or NULL */
+  const float* locs;        /* [B,N,2] OP                                                   */
+  const float* demand;      /* [B,C] CVRP                                                   */
+  const float* vehicle_capacity; /* [B] CVRP                                                */
+  const float* prize;       /* [B,N] PCTSP (the prize the environment steps with)           */
+  const float* max_length;  /* [B,N] OP (the environment's per-node table)                  */
+  void* scratch;            /* B * row_split * rl4co_aco_depot_grad_scratch_bytes(n_ants, N) bytes; required when
+                               n_ants * N > rl4co_aco_depot_grad_lds_entries(); used whenever it is not NULL */
+  float* grad_heatmap;      /* [B,N,N] out                                                  */
+  int32_t* err;             /* sticky error bits                                            */
+} rl4co_aco_depot_grad_args;
+
+int rl4co_aco_depot_logp_grad(const rl4co_aco_depot_grad_args* args, void* stream);
+/* Largest n_ants * N whose replay table rl4co_aco_depot_logp_grad keeps in LDS (aco_depot_grad.hip header). */
+int rl4co_aco_depot_grad_lds_entries(void);
+/* Bytes of `scratch` one workgroup takes for its table (16-byte multiple); -1 outside the served sizes. */
+int64_t rl4co_aco_depot_grad_scratch_bytes(int n_ants, int N);
 
 /* --------------------------------------------------------------------------
  * Ant System search on a heatmap for CVRP (the same reference class with CVRPEnv) as ONE launch, one workgroup per

@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 24  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 25  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -178,6 +178,17 @@ class AcoTspGradArgs(C.Structure):
     ]
 
 
+class AcoDepotGradArgs(C.Structure):
+    """Mirror of ``struct rl4co_aco_depot_grad_args`` (field order and types must match the header)."""
+
+    _fields_ = [
+        ("env", _i32), ("B", _i32), ("N", _i32), ("n_ants", _i32), ("row_split", _i32), ("multistart", _i32),
+        ("temperature", _f32), ("reserved0", _i32),
+        ("heatmap", _vp), ("actions", _vp), ("grad_ll", _vp), ("grad_steps", _vp), ("locs", _vp), ("demand", _vp),
+        ("vehicle_capacity", _vp), ("prize", _vp), ("max_length", _vp), ("scratch", _vp), ("grad_heatmap", _vp), ("err", _vp),
+    ]
+
+
 class AcoCvrpArgs(C.Structure):
     """Mirror of ``struct rl4co_aco_cvrp_args`` (field order and types must match the header)."""
 
@@ -314,6 +325,9 @@ SYMBOLS = {
     "rl4co_aco_tsp_lds_nodes": (C.c_int, []),
     "rl4co_aco_tsp_logp_grad": (C.c_int, [C.POINTER(AcoTspGradArgs), _vp]),
     "rl4co_aco_tsp_grad_lds_entries": (C.c_int, []),
+    "rl4co_aco_depot_logp_grad": (C.c_int, [C.POINTER(AcoDepotGradArgs), _vp]),
+    "rl4co_aco_depot_grad_lds_entries": (C.c_int, []),
+    "rl4co_aco_depot_grad_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "rl4co_aco_cvrp": (C.c_int, [C.POINTER(AcoCvrpArgs), _vp]),
     "rl4co_aco_cvrp_lds_nodes": (C.c_int, []),
     "rl4co_aco_prize": (C.c_int, [C.POINTER(AcoPrizeArgs), _vp]),

@@ -27,9 +27,12 @@ OP and PCTSP (``env.name`` "op", "pctsp" or "spctsp"; ``rl4co_aco_prize``, csrc/
 (PCTSP; ``real_prize`` is the stochastic prize under ``SPCTSPEnv``). Rows are ``W = n`` wide and zero-filled after each
 row's length, the reward is ``env.get_reward`` on that W-wide row, ``final_actions`` is the ragged list as for CVRP.
 
-Training (TSP): :func:`heatmap_rollout` is DeepACO's constructive training decode — the SAMPLE launch of ``rl4co_aco_tsp``
-forward, ``rl4co_aco_tsp_logp_grad`` (csrc/aco_tsp_grad.hip) backward, joined by a ``torch.autograd.Function`` — and
-:func:`deepaco_loss` the model's REINFORCE loss with the shared baseline (deepaco/model.py:79-91)."""
+Training: :func:`heatmap_rollout` is DeepACO's constructive training decode — for TSP the SAMPLE launch of
+``rl4co_aco_tsp`` forward, ``rl4co_aco_tsp_logp_grad`` (csrc/aco_tsp_grad.hip) backward; with ``env_name`` "cvrp", "op",
+"pctsp" or "spctsp" the SAMPLE launch of ``rl4co_aco_cvrp`` / ``rl4co_aco_prize`` forward and
+``rl4co_aco_depot_logp_grad`` (csrc/aco_depot_grad.hip) backward; each pair joined by a ``torch.autograd.Function`` — and
+:func:`deepaco_loss` the model's REINFORCE loss with the shared baseline (deepaco/model.py:79-91).
+``rl4co_amd.NonAutoregressivePolicy`` (rl4co_amd/nargnn.py) is the reference's training surface over it."""
 from __future__ import annotations
 
 from functools import cached_property
@@ -84,9 +87,108 @@ class _AntLogLikelihood(torch.autograd.Function):
         return grad, None, None, None, None, None, None, None
 
 
+class _DepotAntLogLikelihood(torch.autograd.Function):
+    """:class:`_AntLogLikelihood` for the depot graphs: the forward is the SAMPLE launch of ``rl4co_aco_cvrp`` /
+    ``rl4co_aco_prize`` (pheromone of ones, alpha = beta = 1), the backward is ``rl4co_aco_depot_logp_grad``. ``data``: the
+    instance tensors the two bindings take by name. Nothing is saved unless the heatmap requires a gradient; there is no
+    double backward."""
+
+    @staticmethod
+    def forward(ctx, heatmap, env_name, locs, data, start_nodes, forced, n_ants, temperature, seed, err):
+        common = dict(n_ants=n_ants, phases=_lib.ACO_SAMPLE, log_heuristic=heatmap, locs=locs, forced_actions=forced,
+                      temperature=temperature, philox_seed=seed, philox_offset=0, err=err)
+        if env_name == "cvrp":
+            out = K.aco_cvrp(torch.ones_like(heatmap), start_nodes=None if start_nodes is None else start_nodes[None].contiguous(),
+                             **data, **common)
+        else:
+            out = K.aco_prize(torch.ones_like(heatmap), env=env_name, **data, **common)
+        actions, lengths, logps, reward = out["actions"], out["lengths"], out["logps"], out["reward"]
+        ctx.set_materialize_grads(False)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(heatmap, actions)
+            ctx.temperature, ctx.err, ctx.env_name, ctx.multistart = temperature, err, env_name, start_nodes is not None
+            if env_name == "cvrp":
+                ctx.data = dict(demand=data["demand"], vehicle_capacity=data["vehicle_capacity"])
+            elif env_name == "op":
+                ctx.data = dict(locs=locs, max_length=data["max_length"])
+            else:
+                ctx.data = dict(prize=data["prize"])
+        ctx.mark_non_differentiable(actions, lengths, reward)
+        return logps, logps.sum(1), actions, lengths, reward
+
+    @staticmethod
+    def backward(ctx, grad_logps, grad_ll, _grad_actions, _grad_lengths, _grad_reward):
+        if torch.is_grad_enabled():
+            raise RuntimeError("heatmap_rollout has no double backward: rl4co_aco_depot_logp_grad is not differentiable "
+                               "(create_graph=True is not served)")
+        heatmap, actions = ctx.saved_tensors
+        if grad_ll is None:
+            grad_ll = torch.zeros(actions.shape[0], dtype=torch.float32, device=heatmap.device)
+        grad_ll = grad_ll.to(torch.float32).contiguous()
+        if grad_logps is not None:
+            grad_logps = grad_logps.to(torch.float32).contiguous()
+        own = ctx.err is None
+        err = K.new_error_word(heatmap.device) if own else ctx.err
+        grad = K.aco_depot_logp_grad(heatmap, actions, grad_ll, env=ctx.env_name, grad_steps=grad_logps,
+                                     multistart=ctx.multistart, temperature=ctx.temperature, err=err, **ctx.data)
+        if own:
+            _lib.raise_for_error_bits(int(err.item()))
+        return grad, None, None, None, None, None, None, None, None, None
+
+
+_DEPOT_TRAIN_ENVS = ("cvrp",) + _PRIZE_ENVS
+
+
+def _depot_rollout(heatmap, locs, td, env_name, n_ants, start_nodes, actions, temperature, seed, err) -> dict:
+    """:func:`heatmap_rollout` for ``env_name`` in cvrp / op / pctsp / spctsp."""
+    if td is None:
+        raise ValueError(f"heatmap_rollout(env_name={env_name!r}) takes td=: the instance's reset state (demand and "
+                         f"vehicle_capacity; prize and max_length; real_prize and penalty)")
+    keys = {"cvrp": ("demand", "vehicle_capacity"), "op": ("prize", "max_length")}.get(env_name, ("real_prize", "penalty"))
+    for key in keys:
+        if not td[key].is_cuda:
+            raise NotImplementedError(f"heatmap_rollout runs inside the MI355X kernels only: td[{key!r}] on {td[key].device}")
+    if heatmap.dim() != 3 or heatmap.shape[1] != heatmap.shape[2]:
+        raise ValueError(f"heatmap must be [B, n, n], got {tuple(heatmap.shape)}")
+    if start_nodes is not None and env_name != "cvrp":
+        raise NotImplementedError(f"start_nodes (multistart) is served for tsp and cvrp, not for {env_name!r}: every ant "
+                                  f"starts at the depot")
+    b, n, _ = heatmap.shape
+    n_ants = int(n_ants)
+    rows, w = n_ants * b, K.aco_depot_width(env_name, n)
+    dev = heatmap.device
+    heatmap = heatmap.to(torch.float32).contiguous()
+
+    def vec(t):
+        return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+    locs = vec(locs)
+    if env_name == "cvrp":
+        data = dict(demand=vec(td["demand"]), vehicle_capacity=vec(td["vehicle_capacity"]).reshape(-1))
+    elif env_name == "op":
+        data = dict(prize=vec(td["prize"]), max_length=vec(td["max_length"]))
+    else:  # real_prize: the deterministic prize, or the stochastic one under SPCTSPEnv (as AntSystem)
+        data = dict(prize=vec(td["real_prize"]), penalty=vec(td["penalty"]))
+    if actions is not None:
+        actions = actions.detach().to(device=dev, dtype=torch.int64).contiguous()
+        if tuple(actions.shape) != (rows, w):
+            raise ValueError(f"actions must be {(rows, w)}, got {tuple(actions.shape)}")
+        if start_nodes is not None:
+            start_nodes = actions[:, 0]
+    if start_nodes is not None:
+        start_nodes = start_nodes.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        if start_nodes.shape[0] != rows:
+            raise ValueError(f"start_nodes must be [n_ants * B] = [{rows}], got {tuple(start_nodes.shape)}")
+    if seed is None:
+        seed = int(torch.randint(0, 2**62, (1,)).item())
+    logps, ll, acts, lengths, reward = _DepotAntLogLikelihood.apply(heatmap, env_name, locs, data, start_nodes, actions,
+                                                                    n_ants, float(temperature), int(seed), err)
+    return {"actions": acts, "lengths": lengths, "logps": logps, "log_likelihood": ll, "reward": reward}
+
+
 def heatmap_rollout(heatmap: Tensor, locs: Tensor, *, n_ants: int, start_nodes: Tensor | None = None,
                     actions: Tensor | None = None, temperature: float = 1.0, seed: int | None = None,
-                    err: Tensor | None = None) -> dict:
+                    err: Tensor | None = None, env_name: str = "tsp", td=None) -> dict:
     """DeepACO's constructive training rollout for TSP (``ConstructivePolicy.forward`` under ``NonAutoregressiveDecoder``:
     ``n_ants`` tours per instance sampled step by step from ``softmax(heatmap[b, current, unvisited] / temperature)``) as
     ONE launch, with the gradient back to ``heatmap`` [B, N, N] as one more.
@@ -97,10 +199,21 @@ def heatmap_rollout(heatmap: Tensor, locs: Tensor, *, n_ants: int, start_nodes: 
     ``log_likelihood`` [rows] and ``reward`` [rows] (bit-equal to ``TSPEnv.get_reward``); ``logps`` and
     ``log_likelihood`` carry the gradient when ``heatmap.requires_grad``. ``seed``: the Philox key (None: drawn from
     torch's CPU generator). ``err``: the caller's sticky error word, both launches OR into it and nothing is synchronised;
-    None: the forward launch reads its own word back and a set bit raises, and so does the backward launch."""
+    None: the forward launch reads its own word back and a set bit raises, and so does the backward launch.
+
+    ``env_name`` "cvrp", "op", "pctsp" or "spctsp" (node 0 of the heatmap is the depot): ``td`` is the environment's reset
+    state (``demand`` and ``vehicle_capacity``; ``prize`` and ``max_length``; ``real_prize`` and ``penalty``). Every ant
+    starts at the depot and samples its first action from row 0; ``start_nodes`` (cvrp only) are given customers. Rows are
+    ``W`` wide (``kernels.aco_depot_width``) and zero-filled after ``lengths`` [rows], which is returned too; ``logps``
+    [rows, W] are 0 there, ``reward`` is the environment's ``get_reward`` on the W-wide row. ``actions`` [rows, W] are
+    followed and evaluated (with ``start_nodes`` given too, column 0 is the multistart start)."""
     for name, t in (("heatmap", heatmap), ("locs", locs)):
         if not t.is_cuda:
             raise NotImplementedError(f"heatmap_rollout runs inside the MI355X kernel (rl4co_aco_tsp) only: {name} on {t.device}")
+    if env_name in _DEPOT_TRAIN_ENVS:
+        return _depot_rollout(heatmap, locs, td, env_name, n_ants, start_nodes, actions, temperature, seed, err)
+    if env_name != "tsp":
+        raise NotImplementedError(f"heatmap_rollout serves tsp, cvrp, op, pctsp and spctsp, got env_name={env_name!r}")
     if heatmap.dim() != 3 or heatmap.shape[1] != heatmap.shape[2]:
         raise ValueError(f"heatmap must be [B, N, N], got {tuple(heatmap.shape)}")
     b, n, _ = heatmap.shape

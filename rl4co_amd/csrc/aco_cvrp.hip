@@ -65,12 +65,14 @@
 // end-to-end time only).
 #include <hip/hip_runtime.h>
 
+#include "ant_rules.h"
 #include "ant_system.h"
 #include "lds_tour_reward.h"
 
 namespace {
 
-using namespace rl4co::aco;  // ant_system.h: the constants, check_indices, build_logits, ant_step, update_phase, launch
+using namespace rl4co::aco;  // ant_system.h: the constants, check_indices, build_logits, ant_step, update_phase, launch;
+                             // ant_rules.h: the capacity test and the load (shared with aco_depot_grad.hip)
 using rl4co::AntTour;        // lds_tour_reward.h: the reward of a tour held in LDS
 using rl4co::ant_reward;
 
@@ -124,7 +126,7 @@ __global__ void __launch_bounds__(kThreads) aco_cvrp_kernel(const rl4co_aco_cvrp
   const float* heu = sample ? a.log_heuristic + (int64_t)b * NN : nullptr;
   const float2* xy = a.locs ? reinterpret_cast<const float2*>(a.locs) + (int64_t)b * N : nullptr;
   const int K = (N + 63) >> 6;  // nodes per lane
-  const float thr = sample ? a.vehicle_capacity[b] + 1e-5f : 0.0f;  // cvrp/env.py:129, one fp32 add
+  const float thr = sample ? cvrp_threshold(a.vehicle_capacity[b]) : 0.0f;  // cvrp/env.py:129, one fp32 add
   uint32_t errbits = 0;
   bool have_best = a.has_best != 0;
   float best_r = have_best ? a.final_reward[b] : 0.0f;  // (uniform: every thread follows the same record)
@@ -145,7 +147,7 @@ __global__ void __launch_bounds__(kThreads) aco_cvrp_kernel(const rl4co_aco_cvrp
         if (lane == 0) wtour[0] = 0;  // the prepended depot of the reward
         if (a.start_nodes) {  // multistart: action 0 is given, log-prob 0, stepped through the state
           cur = __builtin_amdgcn_readfirstlane((int)a.start_nodes[(int64_t)it * rows + row]);
-          used = (used + dnode[cur]) * 1.0f;
+          used = cvrp_advance(used, dnode[cur], 1);  // (a start is a customer: check_indices' lower bound)
           if ((cur & 63) == lane) vis |= 1u << (cur >> 6);
           left = C - 1;
           if (lane == 0) {
@@ -164,10 +166,10 @@ __global__ void __launch_bounds__(kThreads) aco_cvrp_kernel(const rl4co_aco_cvrp
           uint32_t feas = 0u;
           for (int k = 0; k < K; ++k) {
             const int n = lane + 64 * k;
-            if (n >= 1 && n < N && !((vis >> k) & 1u) && !(dnode[n] + used > thr)) feas |= 1u << k;
+            if (n >= 1 && n < N && !((vis >> k) & 1u) && cvrp_fits(dnode[n], used, thr)) feas |= 1u << k;
           }
           const bool any_customer = __any(feas != 0u);
-          if (lane == 0 && !(cur == 0 && any_customer)) feas |= 1u;
+          if (lane == 0 && cvrp_depot_ok(cur, any_customer)) feas |= 1u;
 
           const int forced = a.forced_actions ? (int)a.forced_actions[row * W + t] : -1;
           float* alp = a.all_logps ? a.all_logps + (row * W + t) * N : nullptr;
@@ -179,7 +181,7 @@ __global__ void __launch_bounds__(kThreads) aco_cvrp_kernel(const rl4co_aco_cvrp
           const uint32_t was = __shfl(vis, chosen & 63, 64);
           if (!((could >> (chosen >> 6)) & 1u)) errbits |= RL4CO_EBIT_INFEASIBLE;  // a forced node that is infeasible
           // cvrp/env.py:66-96 (cvrp_step_body's order)
-          used = (used + dnode[chosen]) * (chosen != 0 ? 1.0f : 0.0f);
+          used = cvrp_advance(used, dnode[chosen], chosen);
           if (chosen == 0) {
             depot_seen = true;
           } else {

@@ -64,12 +64,14 @@
 // been profiled (tools/aco_bench.py --env prize records end-to-end time only).
 #include <hip/hip_runtime.h>
 
+#include "ant_rules.h"
 #include "ant_system.h"
 #include "lds_tour_reward.h"
 
 namespace {
 
-using namespace rl4co::aco;  // ant_system.h: the constants, check_indices, build_logits, ant_step, update_phase, launch
+using namespace rl4co::aco;  // ant_system.h: the constants, check_indices, build_logits, ant_step, update_phase, launch;
+                             // ant_rules.h: the budget and prize tests (shared with aco_depot_grad.hip)
 using rl4co::AntTour;        // lds_tour_reward.h: the sums of stage R
 using rl4co::ant_reward;
 
@@ -189,9 +191,8 @@ __global__ void __launch_bounds__(kThreads) aco_prize_kernel(const rl4co_aco_pri
               for (int k = 0; k < K; ++k) {
                 const int n = lane + 64 * k;
                 if (n >= 1 && n < N && !((vis >> k) & 1u) && !depot_seen) {
-                  const float dx = v0[n] - cx, dy = v1[n] - cy;
-                  const float reach = acc + sqrtf(fmaf(dy, dy, dx * dx));
-                  if (!(reach > v2[n])) feas |= 1u << k;
+                  const float reach = op_advance(acc, op_dist(cx, cy, v0[n], v1[n]));
+                  if (op_within(reach, v2[n])) feas |= 1u << k;
                 }
               }
               if (lane == 0) feas |= 1u;
@@ -200,7 +201,7 @@ __global__ void __launch_bounds__(kThreads) aco_prize_kernel(const rl4co_aco_pri
                 const int n = lane + 64 * k;
                 if (n >= 1 && n < N && !((vis >> k) & 1u) && !depot_seen) feas |= 1u << k;
               }
-              if (lane == 0 && !(acc < 1.0f && left > 0)) feas |= 1u;
+              if (lane == 0 && pctsp_depot_ok(acc, left)) feas |= 1u;
             }
 
             const int forced = a.forced_actions ? (int)a.forced_actions[row * W + t] : -1;
@@ -213,10 +214,9 @@ __global__ void __launch_bounds__(kThreads) aco_prize_kernel(const rl4co_aco_pri
             const uint32_t was = __shfl(vis, chosen & 63, 64);
             if (!((could >> (chosen >> 6)) & 1u)) errbits |= RL4CO_EBIT_INFEASIBLE;  // a forced node that is infeasible
             if constexpr (kOp) {  // op/env.py:67-98
-              const float dx = v0[chosen] - v0[cur], dy = v1[chosen] - v1[cur];
-              acc = acc + sqrtf(fmaf(dy, dy, dx * dx));
+              acc = op_advance(acc, op_dist(v0[cur], v1[cur], v0[chosen], v1[chosen]));
             } else {  // pctsp/env.py:62-91
-              acc = acc + v0[chosen];
+              acc = pctsp_advance(acc, v0[chosen]);
             }
             if (chosen == 0) {
               depot_seen = true;

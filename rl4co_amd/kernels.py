@@ -1227,6 +1227,108 @@ def aco_prize(pheromone: Tensor, *, env: str, n_ants: int, phases: int = _lib.AC
     return out
 
 
+_ACO_DEPOT_GRAD_ENVS = {"cvrp": _lib.ENV_CVRP, **_ACO_PRIZE_ENVS}
+
+
+def aco_depot_grad_lds_entries() -> int:
+    """Largest ``n_ants * N`` whose replay table the depot-graph log-likelihood backward keeps in LDS (a host query)."""
+    return int(_lib.lib().rl4co_aco_depot_grad_lds_entries())
+
+
+def aco_depot_width(env: str, n: int) -> int:
+    """The width of a sampled row: :func:`aco_cvrp_width` for cvrp, ``n`` for op / pctsp / spctsp."""
+    return aco_cvrp_width(n) if env == "cvrp" else n
+
+
+def aco_depot_logp_grad(heatmap: Tensor, actions: Tensor, grad_ll: Tensor, *, env: str, grad_steps: Tensor | None = None,
+                        locs: Tensor | None = None, demand: Tensor | None = None, vehicle_capacity: Tensor | None = None,
+                        prize: Tensor | None = None, max_length: Tensor | None = None, multistart: bool = False,
+                        temperature: float = 1.0, row_split: int | None = None, table_in_scratch: bool | None = None,
+                        err: Tensor | None = None) -> Tensor:
+    """The gradient of the ants' log-likelihoods with respect to the heatmap on a depot graph in one launch
+    (rl4co_aco_depot_logp_grad; the header states the arithmetic). ``env``: "cvrp", "op", "pctsp" or "spctsp"; ``heatmap``
+    [B, n, n] fp32 (the depot is node 0; the logits the forward sampled from, not divided by the temperature), ``actions``
+    [rows, W] int64 as :func:`aco_cvrp` / :func:`aco_prize` write them (W = :func:`aco_depot_width`, rows = n_ants * B
+    ant-major, zero-filled after each row's length), ``grad_ll`` [rows] fp32 and optionally ``grad_steps`` [rows, W] fp32
+    -> ``grad_heatmap`` [B, n, n] fp32, every word written.
+
+    The instance: cvrp ``demand`` [B, n - 1] and ``vehicle_capacity`` [B] or [B, 1]; op ``locs`` [B, n, 2] and ``max_length``
+    [B, n]; pctsp / spctsp ``prize`` [B, n] (the prize the forward stepped with). ``multistart`` (cvrp): column 0 is a given
+    customer and contributes nothing. ``row_split``: workgroups per instance (None: :func:`aco_grad_row_split`); any value
+    gives the same bits. ``table_in_scratch``: keep the replay table in a global scratch instead of LDS (None: only above
+    :func:`aco_depot_grad_lds_entries`); the same bits. ``err`` as in :func:`aco_tsp`."""
+    if env not in _ACO_DEPOT_GRAD_ENVS:
+        raise NotImplementedError(f"aco_depot_logp_grad (rl4co_aco_depot_logp_grad) serves {sorted(_ACO_DEPOT_GRAD_ENVS)}, got "
+                                  f"env = {env!r}")
+    for name, t, dtype in (("heatmap", heatmap, torch.float32), ("actions", actions, torch.int64),
+                           ("grad_ll", grad_ll, torch.float32), ("grad_steps", grad_steps, torch.float32),
+                           ("locs", locs, torch.float32), ("demand", demand, torch.float32),
+                           ("vehicle_capacity", vehicle_capacity, torch.float32), ("prize", prize, torch.float32),
+                           ("max_length", max_length, torch.float32)):
+        if t is not None and t.dtype != dtype:
+            raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    if heatmap.dim() != 3 or heatmap.shape[1] != heatmap.shape[2]:
+        raise ValueError(f"heatmap must be [B, n, n], got {tuple(heatmap.shape)}")
+    b, n, _ = heatmap.shape
+    if not 2 <= n <= 1024:
+        raise NotImplementedError(f"aco_depot_logp_grad serves 2..1024 nodes (depot included), got n = {n}")
+    w = aco_depot_width(env, n)
+    if actions.dim() != 2 or actions.shape[1] != w or actions.shape[0] == 0 or actions.shape[0] % b:
+        raise ValueError(f"actions must be [n_ants * B, W] = [k * {b}, {w}], got {tuple(actions.shape)}")
+    rows = actions.shape[0]
+    n_ants = rows // b
+    if tuple(grad_ll.shape) != (rows,):
+        raise ValueError(f"grad_ll must be {(rows,)}, got {tuple(grad_ll.shape)}")
+    if grad_steps is not None and tuple(grad_steps.shape) != (rows, w):
+        raise ValueError(f"grad_steps must be {(rows, w)}, got {tuple(grad_steps.shape)}")
+    if vehicle_capacity is not None:
+        vehicle_capacity = vehicle_capacity.reshape(-1)
+    needs = {"cvrp": (("demand", demand, (b, n - 1)), ("vehicle_capacity", vehicle_capacity, (b,))),
+             "op": (("locs", locs, (b, n, 2)), ("max_length", max_length, (b, n)))}.get(env, (("prize", prize, (b, n)),))
+    for name, t, shape in needs:
+        if t is None or tuple(t.shape) != shape:
+            raise ValueError(f"env {env!r} takes {name} {shape}, got {None if t is None else tuple(t.shape)}")
+    if multistart and env != "cvrp":
+        raise NotImplementedError(f"multistart is served for cvrp only, got env = {env!r}")
+    if not temperature > 0:
+        raise ValueError(f"temperature must be positive, got {temperature}")
+    if row_split is not None and not 1 <= int(row_split) <= n:
+        raise ValueError(f"row_split must be in [1, n = {n}], got {row_split}")
+    _dev(heatmap, None, "heatmap"), _dev(actions, None, "actions"), _dev(grad_ll, None, "grad_ll")
+    if grad_steps is not None:
+        _dev(grad_steps, None, "grad_steps")
+    for name, t, _ in needs:
+        _dev(t, None, name)
+    given = {name: t for name, t, _ in needs}
+    dev = heatmap.device
+    if row_split is None:
+        row_split = aco_grad_row_split(b, n, torch.cuda.get_device_properties(dev).multi_processor_count)
+    fits = n_ants * n <= aco_depot_grad_lds_entries()
+    if table_in_scratch is None:
+        table_in_scratch = not fits
+    elif not table_in_scratch and not fits:
+        raise ValueError(f"n_ants * n = {n_ants * n} is above the LDS table's {aco_depot_grad_lds_entries()} entries")
+    scratch = None
+    if table_in_scratch:
+        per_wg = int(_lib.lib().rl4co_aco_depot_grad_scratch_bytes(n_ants, n))
+        scratch = torch.empty(b * int(row_split) * per_wg, dtype=torch.uint8, device=dev)
+    grad = torch.empty((b, n, n), dtype=torch.float32, device=dev)
+    own = err is None
+    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
+    a = _lib.AcoDepotGradArgs()
+    a.env, a.B, a.N, a.n_ants, a.row_split = _ACO_DEPOT_GRAD_ENVS[env], b, n, n_ants, int(row_split)
+    a.multistart, a.temperature, a.reserved0 = int(bool(multistart)), float(temperature), 0
+    a.heatmap, a.actions, a.grad_ll, a.grad_steps = _ptr(heatmap), _ptr(actions), _ptr(grad_ll), _ptr(grad_steps)
+    a.locs, a.demand, a.vehicle_capacity = _ptr(given.get("locs")), _ptr(given.get("demand")), _ptr(given.get("vehicle_capacity"))
+    a.prize, a.max_length = _ptr(given.get("prize")), _ptr(given.get("max_length"))
+    a.scratch, a.grad_heatmap, a.err = _ptr(scratch), _ptr(grad), _ptr(err)
+    st = _lib.lib().rl4co_aco_depot_logp_grad(C.byref(a), _stream())
+    _lib.check(st, "rl4co_aco_depot_logp_grad")
+    if own:
+        raise_if_error(err)
+    return grad
+
+
 def decoding_filter(top_k, top_p, n: int) -> tuple[int, float]:
     """The top-k / top-p arguments of utils/decoding.py:109-188 as the kernel takes them: ``top_k <= 0`` is off and is
     clamped to ``n`` (k >= n removes nothing: 0); ``top_p <= 0`` or ``>= 1`` is off (0.0); ``top_p > 1`` raises the

@@ -388,3 +388,115 @@ class DeepACOPolicy(nn.Module):
             _, ls_reward = aco.local_search(td_initial, env, rolled["actions"], decoding_kwargs)
             out["ls_reward"] = unbatchify(ls_reward)
         return out
+
+
+_TRAIN_ENVS = ("tsp", "cvrp", "op", "pctsp", "spctsp")
+
+
+class NonAutoregressivePolicy(nn.Module):
+    """models/common/constructive/nonautoregressive/policy.py: the constructive policy over a heatmap, the training
+    surface DeepACO's ``phase="train"`` delegates to. ``encoder`` is the caller's differentiable module returning
+    ``(heatmap [B, N, N], init_embeds)``; the decode is :func:`rl4co_amd.aco.heatmap_rollout` — one launch forward, one
+    backward — instead of the reference's step loop under autograd.
+
+    Served: ``phase="train"`` with sampling; ``tsp`` with multistart (``train_decode_type="multistart_sampling"`` or
+    ``multistart=True``, ``num_starts``), ``cvrp`` / ``op`` / ``pctsp`` / ``spctsp`` with multisample (``multisample=True``,
+    ``num_samples``), ``cvrp`` with multistart too. Returns ``ConstructivePolicy.forward``'s dict: flat ant-major [rows]
+    ``reward`` and ``log_likelihood``, ``actions`` [rows, W] (zero-filled after each row's length) and on request ``hidden``
+    (the heatmap) and ``init_embeds``. Everything else is refused with ``NotImplementedError`` BEFORE the encoder runs:
+    ``actions=``, ``return_entropy``, ``return_sum_log_likelihood=False``, ``top_k`` / ``top_p`` / ``tanh_clipping``,
+    ``mask_logits=False``, ``select_best``, unknown decoding keywords, CPU tensors, and ``phase="val"`` / ``"test"`` (greedy
+    decoding of a heatmap: DeepACO's inference is :class:`DeepACOPolicy`'s Ant System search)."""
+
+    def __init__(self, encoder: nn.Module, decoder=None, env_name: str = "tsp", temperature: float = 1.0,
+                 tanh_clipping: float = 0, mask_logits: bool = True, train_decode_type: str = "sampling",
+                 val_decode_type: str = "greedy", test_decode_type: str = "greedy"):
+        super().__init__()
+        if encoder is None:
+            raise ValueError("NonAutoregressivePolicy takes the caller's differentiable encoder")
+        if decoder is not None:
+            raise NotImplementedError("NonAutoregressivePolicy(decoder=...) is not served: the decode is the Ant System "
+                                      "kernels' (NonAutoregressiveDecoder's heatmap rows)")
+        if env_name not in _TRAIN_ENVS:
+            raise NotImplementedError(f"NonAutoregressivePolicy serves env_name in {_TRAIN_ENVS}, got {env_name!r}")
+        self.encoder = encoder
+        self.env_name = env_name
+        self.temperature = temperature
+        self.tanh_clipping = tanh_clipping
+        self.mask_logits = mask_logits
+        self.train_decode_type = train_decode_type
+        self.val_decode_type = val_decode_type
+        self.test_decode_type = test_decode_type
+
+    def forward(self, td, env=None, phase: str = "train", calc_reward: bool = True, return_actions: bool = True,
+                return_entropy: bool = False, return_hidden: bool = False, return_init_embeds: bool = False,
+                return_sum_log_likelihood: bool = True, actions=None, max_steps=1_000_000, **decoding_kwargs) -> dict:
+        name = "NonAutoregressivePolicy"
+        if phase != "train":
+            raise NotImplementedError(f"{name} serves phase='train' (the constructive training decode); phase={phase!r} is "
+                                      f"a greedy decode of the heatmap, which no kernel serves: DeepACO's inference is "
+                                      f"DeepACOPolicy's Ant System search (phase='val' / 'test' there)")
+        if actions is not None:
+            raise NotImplementedError(f"{name} does not serve actions= (the reference's 'evaluate' strategy); "
+                                      f"rl4co_amd.aco.heatmap_rollout(actions=...) evaluates given rows")
+        if return_entropy:
+            raise NotImplementedError(f"{name} does not serve return_entropy=True")
+        if not return_sum_log_likelihood:
+            raise NotImplementedError(f"{name} does not serve return_sum_log_likelihood=False; "
+                                      f"rl4co_amd.aco.heatmap_rollout returns the per-step log-probs")
+        kw = dict(decoding_kwargs)
+        decode_type = kw.pop("decode_type", None) or self.train_decode_type
+        if decode_type not in ("sampling", "multistart_sampling"):
+            raise NotImplementedError(f"{name} serves the decode types 'sampling' and 'multistart_sampling', got {decode_type!r}")
+        temperature = float(kw.pop("temperature", self.temperature))
+        if kw.pop("tanh_clipping", self.tanh_clipping):
+            raise NotImplementedError(f"{name} does not serve tanh_clipping")
+        if not kw.pop("mask_logits", self.mask_logits):
+            raise NotImplementedError(f"{name} does not serve mask_logits=False")
+        if kw.pop("top_k", 0) or kw.pop("top_p", 0.0):
+            raise NotImplementedError(f"{name} does not serve top_k / top_p filtering of the heatmap")
+        if kw.pop("select_best", False):
+            raise NotImplementedError(f"{name} does not serve select_best=True: training takes every ant's row")
+        kw.pop("store_all_logp", None)
+        multistart = bool(kw.pop("multistart", False)) or decode_type == "multistart_sampling"
+        multisample = bool(kw.pop("multisample", False))
+        num_starts, num_samples = kw.pop("num_starts", None), kw.pop("num_samples", None)
+        start_fn = kw.pop("select_start_nodes_fn", None)
+        if kw:
+            raise NotImplementedError(f"{name} does not serve the decoding keywords {sorted(kw)}")
+        if multistart == multisample:
+            raise NotImplementedError(f"{name} takes exactly one of multistart (decode type 'multistart_sampling' or "
+                                      f"multistart=True) and multisample=True")
+        if multistart and self.env_name not in ("tsp", "cvrp"):
+            raise NotImplementedError(f"{name} serves multistart for tsp and cvrp; {self.env_name!r} ants start at the depot "
+                                      f"(multisample=True, num_samples=...)")
+        if multisample and self.env_name == "tsp":
+            raise NotImplementedError(f"{name} serves tsp with multistart (num_starts=...): the ants' kernel starts every "
+                                      f"tour from a given node")
+        n_ants = num_starts if multistart else num_samples
+        if n_ants is None or int(n_ants) < 1:
+            raise NotImplementedError(f"{name} takes {'num_starts' if multistart else 'num_samples'} >= 1 (the ants per instance)")
+        n_ants = int(n_ants)
+        for key in ("locs",):
+            if not td[key].is_cuda:
+                raise NotImplementedError(f"{name} runs inside the MI355X kernels only: td[{key!r}] on {td[key].device}")
+        if env is None or isinstance(env, str):
+            from .envs import get_env
+
+            env = get_env(self.env_name if env is None else env)
+
+        hidden, init_embeds = self.encoder(td)
+        starts = None
+        if multistart:  # Sampling.pre_decoder_hook: called once
+            starts = start_fn(td, env, n_ants) if start_fn is not None else env.select_start_nodes(td, num_starts=n_ants)
+            starts = starts.to(device=hidden.device, dtype=torch.int64).reshape(-1)
+        rolled = heatmap_rollout(hidden, td["locs"], n_ants=n_ants, start_nodes=starts, temperature=temperature,
+                                 env_name=self.env_name, td=td)
+        out = {"reward": rolled["reward"], "log_likelihood": rolled["log_likelihood"]}
+        if return_actions:
+            out["actions"] = rolled["actions"]
+        if return_hidden:
+            out["hidden"] = hidden
+        if return_init_embeds:
+            out["init_embeds"] = init_embeds
+        return out

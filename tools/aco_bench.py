@@ -29,6 +29,9 @@ backward of the ants' log-likelihoods from a free heatmap at TSP-100 x 30 ants, 
 (512) the card's CU count; ``kernels`` (``heatmap_rollout``: two launches) against ``torch_per_step`` (the step loop in
 torch ops with autograd on the same card, what the reference executes), alternating (``main_train``). No threshold: both
 times and their ratio are reported. Writes profiles/aco_train_bench.json unless ``--out`` says otherwise.
+``--train --env cvrp|op|pctsp`` is the same protocol on a depot graph (csrc/aco_cvrp.hip / csrc/aco_prize.hip SAMPLE +
+csrc/aco_depot_grad.hip) with 100 customers, every ant starting at the depot (``main_train_depot``); all three rows are
+merged into profiles/aco_depot_train_bench.json unless ``--out`` says otherwise.
 """
 import argparse
 import json
@@ -125,7 +128,7 @@ def main():
     ap.add_argument("--ants", type=int, default=None, help="default 48 (--train: 30)")
     ap.add_argument("--iterations", type=int, default=10)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--env", choices=("tsp", "cvrp", "prize"), default="tsp")
+    ap.add_argument("--env", choices=("tsp", "cvrp", "prize", "op", "pctsp"), default="tsp", help="op / pctsp: with --train")
     ap.add_argument("--nls", action="store_true", help="time the neural-guided local search instead (TSP)")
     ap.add_argument("--train", action="store_true", help="time the training decode, forward plus backward, instead (TSP)")
     a = ap.parse_args()
@@ -133,7 +136,9 @@ def main():
         raise SystemExit("aco_bench needs the MI355X: a time taken anywhere else says nothing")
     dev = torch.device("cuda", 0)
     if a.train:  # its own defaults: an explicit --ants / --batch is taken as given
-        return main_train(a, dev)
+        return main_train(a, dev) if a.env == "tsp" else main_train_depot(a, dev)
+    if a.env in ("op", "pctsp"):
+        raise SystemExit("aco_bench --env op / pctsp goes with --train (the search of both is --env prize)")
     a.batch = 4096 if a.batch is None else a.batch
     a.ants = 48 if a.ants is None else a.ants
     if a.env == "cvrp":
@@ -450,6 +455,155 @@ def main_train(a, dev):
                             "around the step, synchronised; torch_per_step is this script's torch loop with autograd on the same "
                             "card (it draws other tours than the kernel); no threshold was fixed in advance",
                        rows=rows_out), f, indent=1)
+
+
+def depot_instances(env, batch, n, dev):
+    """Seeded instances in the generators' spirit (uniform locs; CVRP demands U{1..9} / 50; OP prizes by distance to the depot
+    and the per-node table of budget 4; PCTSP prizes U(0, 4 / C), penalties U(0, 3 / C))."""
+    g = torch.Generator().manual_seed(1234)
+    c = n - 1
+    locs = torch.rand(batch, n, 2, generator=g)
+    to_depot = (locs[:, 0:1] - locs).norm(p=2, dim=-1)
+    if env == "cvrp":
+        td = {"demand": torch.randint(1, 10, (batch, c), generator=g).float() / 50, "vehicle_capacity": torch.ones(batch, 1)}
+    elif env == "op":
+        prize = (1 + (to_depot / to_depot.max(-1, keepdim=True).values * 99).int()).float() / 100
+        prize[:, 0] = 0
+        td = {"prize": prize, "max_length": torch.full((batch, 1), 4.0) - to_depot - 1e-6}
+    else:
+        prize, penalty = torch.rand(batch, n, generator=g) * (4.0 / c), torch.rand(batch, n, generator=g) * (3.0 / c)
+        prize[:, 0] = 0
+        penalty[:, 0] = 0
+        td = {"real_prize": prize, "penalty": penalty}
+    td["locs"] = locs
+    return {k: v.to(dev) for k, v in td.items()}
+
+
+def torch_depot_train_step(env, heat, td, n_ants, temperature=1.0):
+    """The reference's training decode on a depot graph from torch ops with autograd, one decoding step at a time until every
+    row is done (ant-major rows, every ant starts at the depot): the environment's mask, gather the row, log-softmax,
+    multinomial, gather the log-prob. Returns (log_likelihood [rows], actions [rows, T])."""
+    b, n, _ = heat.shape
+    rows, dev = n_ants * b, heat.device
+    ar, inst = torch.arange(rows, device=dev), torch.arange(rows, device=dev) % b
+    locs = td["locs"][inst]
+    cur = torch.zeros(rows, dtype=torch.int64, device=dev)
+    visited = torch.zeros(rows, n, dtype=torch.bool, device=dev)
+    acc = torch.zeros(rows, device=dev)
+    done = torch.zeros(rows, dtype=torch.bool, device=dev)
+    if env == "cvrp":
+        demand = torch.cat((torch.zeros(b, 1, device=dev), td["demand"]), 1)[inst]
+        cap = td["vehicle_capacity"].reshape(-1)[inst]
+    steps, logps, t = [], [], 0
+    while not bool(done.all()):
+        if env == "cvrp":
+            bad = visited | (demand + acc[:, None] > cap[:, None] + 1e-5)
+            bad[:, 0] = (cur == 0) & ~bad[:, 1:].all(1)
+        elif env == "op":
+            reach = acc[:, None] + (locs - locs[ar, cur][:, None]).norm(p=2, dim=-1)
+            bad = visited | visited[:, 0:1] | (reach > td["max_length"][inst])
+            bad[:, 0] = False
+        else:
+            bad = visited | visited[:, 0:1]
+            bad[:, 0] = (acc < 1.0) & ~visited[:, 1:].all(1)
+        bad = torch.where(done[:, None], torch.arange(n, device=dev)[None, :] != 0, bad)  # a finished row stays at the depot
+        lp = torch.log_softmax(heat[inst, cur].masked_fill(bad, float("-inf")) / temperature, -1)
+        nxt = torch.multinomial(lp.detach().exp(), 1).squeeze(1)
+        logps.append(lp[ar, nxt])
+        if env == "cvrp":
+            acc = (acc + demand[ar, nxt]) * (nxt != 0)
+            visited = visited.clone()
+            visited[ar, nxt] = True
+            done = visited[:, 1:].all(1) & visited[:, 0]
+        else:
+            acc = acc + ((locs[ar, nxt] - locs[ar, cur]).norm(p=2, dim=-1) if env == "op" else td["real_prize"][inst, nxt])
+            visited = visited.clone()
+            visited[ar, nxt] = True
+            done = done | ((nxt == 0) & (t > 0))
+        cur = nxt
+        steps.append(nxt)
+        t += 1
+    return torch.stack(logps, 1).sum(1), torch.stack(steps, 1)
+
+
+def main_train_depot(a, dev):
+    """``--train --env cvrp|op|pctsp``: ``main_train``'s protocol on a depot graph. Both legs take their reward from the same
+    expression on their own rows (the tour length of [depot, row] closed; OP and PCTSP add their prize / penalty terms)."""
+    from rl4co_amd.aco import deepaco_loss, heatmap_rollout
+
+    env, n = a.env, a.num_loc + 1
+    ants = 30 if a.ants is None else a.ants
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    batches = (64, 512) if a.batch is None else (a.batch,)
+    rows_out = []
+    for batch in batches:
+        td = depot_instances(env, batch, n, dev)
+        locs = td["locs"]
+        dist = (locs[:, :, None] - locs[:, None, :]).norm(p=2, dim=-1)
+        heat = (-torch.log(dist + 1e9 * torch.eye(n, device=dev))).requires_grad_(True)
+        inst = torch.arange(ants * batch, device=dev) % batch
+        state = {}
+
+        def reward_of(actions):
+            idx = torch.cat((torch.zeros_like(actions[:, :1]), actions), 1)
+            pts = locs[inst[:, None], idx]
+            length = (pts.roll(-1, 1) - pts).norm(p=2, dim=-1).sum(1)
+            if env == "cvrp":
+                return -length
+            if env == "op":
+                return td["prize"][inst[:, None], actions].sum(1)
+            penalty = td["penalty"]
+            return penalty[inst[:, None], actions].sum(1) - (length + penalty[:, 1:].sum(1)[inst])
+
+        def finish(ll, reward):
+            loss = deepaco_loss({"reward": reward.view(ants, batch).t(), "log_likelihood": ll.view(ants, batch).t()})
+            heat.grad = None
+            loss.backward()
+            state["grad"] = heat.grad
+            return state["grad"]
+
+        def kernels():
+            out = heatmap_rollout(heat, locs, n_ants=ants, seed=1234, env_name=env, td=td)
+            state["kernel_steps"] = out["actions"].shape[1]
+            return finish(out["log_likelihood"], out["reward"])
+
+        def per_step():
+            ll, actions = torch_depot_train_step(env, heat, td, ants)
+            state["torch_steps"] = actions.shape[1]
+            return finish(ll, reward_of(actions))
+
+        legs = [Leg("kernels", kernels), Leg("torch_per_step", per_step)]
+        for it in range(a.reps + 1):  # one warm-up round; the legs alternate inside every round
+            for leg in legs:
+                leg.launch(keep=it >= 1)
+        results = []
+        for leg in legs:
+            t = sorted(leg.times)
+            if not bool(torch.isfinite(leg.tours).all()) or float(leg.tours.abs().max()) == 0.0:
+                raise SystemExit(f"aco_bench --train: leg {leg.kind} produced no usable gradient; no time is recorded")
+            results.append(dict(leg=leg.kind, env=env, case=f"{env}{n - 1}x{batch}", batch=batch,
+                                relation_to_cus=f"{batch} instances, {cus} CUs", reps=len(t), median_ms=t[len(t) // 2],
+                                min_ms=t[0], max_ms=t[-1], row_width=state["kernel_steps"], torch_steps=state["torch_steps"]))
+        ratio = results[1]["median_ms"] / results[0]["median_ms"]
+        for r in results:
+            r["torch_over_kernels_median"] = ratio
+            rows_out.append(r)
+            print(json.dumps(r), flush=True)
+    out = a.out or "profiles/aco_depot_train_bench.json"
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    kept = []
+    if os.path.exists(out):  # the other environments' rows stay
+        with open(out) as f:
+            kept = [r for r in json.load(f).get("rows", []) if r.get("env") != env]
+    with open(out, "w") as f:
+        json.dump(dict(device=torch.cuda.get_device_name(0), when=time.strftime("%Y-%m-%d"),
+                       case=f"{n - 1} customers, {ants} ants, batches {list(batches)}, free heatmap -log(distance), every ant "
+                            f"starts at the depot",
+                       what="training decode forward + deepaco_loss + backward to the heatmap (host work included), HIP events "
+                            "around the step, synchronised; torch_per_step is this script's torch loop with autograd on the same "
+                            "card (it draws other rows than the kernel, torch_steps of them against the kernel's fixed "
+                            "row_width); no threshold was fixed in advance",
+                       rows=kept + rows_out), f, indent=1)
 
 
 if __name__ == "__main__":
