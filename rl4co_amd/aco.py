@@ -30,12 +30,13 @@ row's length, the reward is ``env.get_reward`` on that W-wide row, ``final_actio
 Training: :func:`heatmap_rollout` is DeepACO's constructive training decode — for TSP the SAMPLE launch of
 ``rl4co_aco_tsp`` forward, ``rl4co_aco_tsp_logp_grad`` (csrc/aco_tsp_grad.hip) backward; with ``env_name`` "cvrp", "op",
 "pctsp" or "spctsp" the SAMPLE launch of ``rl4co_aco_cvrp`` / ``rl4co_aco_prize`` forward and
-``rl4co_aco_depot_logp_grad`` (csrc/aco_depot_grad.hip) backward; each pair joined by a ``torch.autograd.Function`` — and
+``rl4co_aco_depot_logp_grad`` (csrc/aco_depot_grad.hip) backward; every pair joined by the one ``torch.autograd.Function`` below — and
 :func:`deepaco_loss` the model's REINFORCE loss with the shared baseline (deepaco/model.py:79-91).
 ``rl4co_amd.NonAutoregressivePolicy`` (rl4co_amd/nargnn.py) is the reference's training surface over it."""
 from __future__ import annotations
 
 from functools import cached_property
+from typing import NamedTuple
 
 import torch
 from torch import Tensor
@@ -43,83 +44,58 @@ from torch import Tensor
 from . import _lib
 from . import kernels as K
 
+
+class _Serves(NamedTuple):
+    """What ``AntSystem`` serves per environment: the decoding keywords, why ``use_local_search`` is refused (None: it is
+    served) and which of multistart / multisample a run may ask for (two: exactly one of them)."""
+    kwargs: tuple[str, ...]
+    no_local_search: str | None
+    modes: tuple[str, ...]
+
+
 _SERVED_KWARGS = ("multistart", "num_starts", "select_best", "select_start_nodes_fn", "temperature")
-_SERVED_KWARGS_CVRP = _SERVED_KWARGS + ("multisample", "num_samples")
-_SERVED_KWARGS_PRIZE = ("multisample", "num_samples", "select_best", "temperature")
-_PRIZE_ENVS = ("op", "pctsp", "spctsp")  # rl4co_aco_prize; spctsp is pctsp with the stochastic prize in td["real_prize"]
+_PRIZE = _Serves(("multisample", "num_samples", "select_best", "temperature"),
+                 "the reference's destroy-and-repair local search is not part of the Ant System kernel", ("multisample",))
+_SERVES = {"tsp": _Serves(_SERVED_KWARGS, None, ("multistart",)),
+           "cvrp": _Serves(_SERVED_KWARGS + ("multisample", "num_samples"),
+                           "the reference's CVRP local search is the external HGS library", ("multistart", "multisample")),
+           "op": _PRIZE, "pctsp": _PRIZE, "spctsp": _PRIZE}  # spctsp is pctsp with the stochastic prize in td["real_prize"]
+_NUM_KEY = {"multistart": "num_starts", "multisample": "num_samples"}
+
+
+def _instance(env_name: str, td, dev) -> dict:
+    """The instance tensors of ``td`` under the bindings' keywords (``kernels.ACO_TD_KEYS``), fp32 on ``dev``."""
+    return {kw: td[key].detach().to(device=dev, dtype=torch.float32).contiguous() for kw, key in K.ACO_TD_KEYS[env_name]}
 
 
 class _AntLogLikelihood(torch.autograd.Function):
-    """The ants' per-step log-probs and their sum as functions of the heatmap: the forward is the SAMPLE launch of
-    ``rl4co_aco_tsp`` (pheromone of ones, alpha = beta = 1: ``rl4co_logf(1) == 0`` exactly, so its logits ARE the heatmap),
-    the backward is ``rl4co_aco_tsp_logp_grad``. Nothing is saved unless the heatmap requires a gradient; there is no
-    double backward."""
+    """The ants' per-step log-probs and their sum as functions of the heatmap: the forward is the SAMPLE launch of the
+    environment's search kernel (``kernels.aco_search``; pheromone of ones, alpha = beta = 1: ``rl4co_logf(1) == 0`` exactly,
+    so its logits ARE the heatmap), the backward is its log-likelihood gradient kernel (``kernels.aco_logp_grad``). ``data``:
+    ``locs`` and the instance tensors the bindings take by name; ``lengths`` is None for tsp. Nothing is saved unless the
+    heatmap requires a gradient; there is no double backward."""
 
     @staticmethod
-    def forward(ctx, heatmap, locs, start_nodes, forced, n_ants, temperature, seed, err):
-        out = K.aco_tsp(torch.ones_like(heatmap), n_ants=n_ants, phases=_lib.ACO_SAMPLE, log_heuristic=heatmap, locs=locs,
-                        start_nodes=start_nodes[None].contiguous(), forced_actions=forced, temperature=temperature,
-                        philox_seed=seed, philox_offset=0, err=err)
-        actions, logps, reward = out["actions"], out["logps"], out["reward"]
-        ctx.temperature, ctx.err = temperature, err
-        ctx.set_materialize_grads(False)
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(heatmap, actions)
-        ctx.mark_non_differentiable(actions, reward)
-        return logps, logps.sum(1), actions, reward
-
-    @staticmethod
-    def backward(ctx, grad_logps, grad_ll, _grad_actions, _grad_reward):
-        if torch.is_grad_enabled():
-            raise RuntimeError("heatmap_rollout has no double backward: rl4co_aco_tsp_logp_grad is not differentiable "
-                               "(create_graph=True is not served)")
-        heatmap, actions = ctx.saved_tensors
-        if grad_ll is None:
-            grad_ll = torch.zeros(actions.shape[0], dtype=torch.float32, device=heatmap.device)
-        grad_ll = grad_ll.to(torch.float32).contiguous()
-        if grad_logps is not None:
-            grad_logps = grad_logps.to(torch.float32).contiguous()
-        own = ctx.err is None
-        err = K.new_error_word(heatmap.device) if own else ctx.err
-        grad = K.aco_tsp_logp_grad(heatmap, actions, grad_ll, grad_steps=grad_logps, temperature=ctx.temperature, err=err)
-        if own:
-            _lib.raise_for_error_bits(int(err.item()))
-        return grad, None, None, None, None, None, None, None
-
-
-class _DepotAntLogLikelihood(torch.autograd.Function):
-    """:class:`_AntLogLikelihood` for the depot graphs: the forward is the SAMPLE launch of ``rl4co_aco_cvrp`` /
-    ``rl4co_aco_prize`` (pheromone of ones, alpha = beta = 1), the backward is ``rl4co_aco_depot_logp_grad``. ``data``: the
-    instance tensors the two bindings take by name. Nothing is saved unless the heatmap requires a gradient; there is no
-    double backward."""
-
-    @staticmethod
-    def forward(ctx, heatmap, env_name, locs, data, start_nodes, forced, n_ants, temperature, seed, err):
-        common = dict(n_ants=n_ants, phases=_lib.ACO_SAMPLE, log_heuristic=heatmap, locs=locs, forced_actions=forced,
-                      temperature=temperature, philox_seed=seed, philox_offset=0, err=err)
-        if env_name == "cvrp":
-            out = K.aco_cvrp(torch.ones_like(heatmap), start_nodes=None if start_nodes is None else start_nodes[None].contiguous(),
-                             **data, **common)
-        else:
-            out = K.aco_prize(torch.ones_like(heatmap), env=env_name, **data, **common)
-        actions, lengths, logps, reward = out["actions"], out["lengths"], out["logps"], out["reward"]
+    def forward(ctx, heatmap, env_name, data, start_nodes, forced, n_ants, temperature, seed, err):
+        kw = dict(data)
+        if K.aco_family(env_name).start_nodes:
+            kw["start_nodes"] = None if start_nodes is None else start_nodes[None].contiguous()
+        out = K.aco_search(env_name, torch.ones_like(heatmap), n_ants=n_ants, phases=_lib.ACO_SAMPLE, log_heuristic=heatmap,
+                           forced_actions=forced, temperature=temperature, philox_seed=seed, philox_offset=0, err=err, **kw)
+        actions, lengths, logps, reward = out["actions"], out.get("lengths"), out["logps"], out["reward"]
         ctx.set_materialize_grads(False)
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(heatmap, actions)
             ctx.temperature, ctx.err, ctx.env_name, ctx.multistart = temperature, err, env_name, start_nodes is not None
-            if env_name == "cvrp":
-                ctx.data = dict(demand=data["demand"], vehicle_capacity=data["vehicle_capacity"])
-            elif env_name == "op":
-                ctx.data = dict(locs=locs, max_length=data["max_length"])
-            else:
-                ctx.data = dict(prize=data["prize"])
-        ctx.mark_non_differentiable(actions, lengths, reward)
+            ctx.data = {key: data[key] for key, _ in K.aco_grad_family(env_name).needs[env_name]}
+        ctx.mark_non_differentiable(*(t for t in (actions, lengths, reward) if t is not None))
         return logps, logps.sum(1), actions, lengths, reward
 
     @staticmethod
     def backward(ctx, grad_logps, grad_ll, _grad_actions, _grad_lengths, _grad_reward):
+        fam = K.aco_grad_family(ctx.env_name)
         if torch.is_grad_enabled():
-            raise RuntimeError("heatmap_rollout has no double backward: rl4co_aco_depot_logp_grad is not differentiable "
+            raise RuntimeError(f"heatmap_rollout has no double backward: {fam.symbol} is not differentiable "
                                "(create_graph=True is not served)")
         heatmap, actions = ctx.saved_tensors
         if grad_ll is None:
@@ -129,61 +105,11 @@ class _DepotAntLogLikelihood(torch.autograd.Function):
             grad_logps = grad_logps.to(torch.float32).contiguous()
         own = ctx.err is None
         err = K.new_error_word(heatmap.device) if own else ctx.err
-        grad = K.aco_depot_logp_grad(heatmap, actions, grad_ll, env=ctx.env_name, grad_steps=grad_logps,
-                                     multistart=ctx.multistart, temperature=ctx.temperature, err=err, **ctx.data)
+        grad = K.aco_logp_grad(ctx.env_name, heatmap, actions, grad_ll, grad_steps=grad_logps, temperature=ctx.temperature,
+                               err=err, **ctx.data, **({"multistart": ctx.multistart} if fam.depot else {}))
         if own:
             _lib.raise_for_error_bits(int(err.item()))
-        return grad, None, None, None, None, None, None, None, None, None
-
-
-_DEPOT_TRAIN_ENVS = ("cvrp",) + _PRIZE_ENVS
-
-
-def _depot_rollout(heatmap, locs, td, env_name, n_ants, start_nodes, actions, temperature, seed, err) -> dict:
-    """:func:`heatmap_rollout` for ``env_name`` in cvrp / op / pctsp / spctsp."""
-    if td is None:
-        raise ValueError(f"heatmap_rollout(env_name={env_name!r}) takes td=: the instance's reset state (demand and "
-                         f"vehicle_capacity; prize and max_length; real_prize and penalty)")
-    keys = {"cvrp": ("demand", "vehicle_capacity"), "op": ("prize", "max_length")}.get(env_name, ("real_prize", "penalty"))
-    for key in keys:
-        if not td[key].is_cuda:
-            raise NotImplementedError(f"heatmap_rollout runs inside the MI355X kernels only: td[{key!r}] on {td[key].device}")
-    if heatmap.dim() != 3 or heatmap.shape[1] != heatmap.shape[2]:
-        raise ValueError(f"heatmap must be [B, n, n], got {tuple(heatmap.shape)}")
-    if start_nodes is not None and env_name != "cvrp":
-        raise NotImplementedError(f"start_nodes (multistart) is served for tsp and cvrp, not for {env_name!r}: every ant "
-                                  f"starts at the depot")
-    b, n, _ = heatmap.shape
-    n_ants = int(n_ants)
-    rows, w = n_ants * b, K.aco_depot_width(env_name, n)
-    dev = heatmap.device
-    heatmap = heatmap.to(torch.float32).contiguous()
-
-    def vec(t):
-        return t.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-    locs = vec(locs)
-    if env_name == "cvrp":
-        data = dict(demand=vec(td["demand"]), vehicle_capacity=vec(td["vehicle_capacity"]).reshape(-1))
-    elif env_name == "op":
-        data = dict(prize=vec(td["prize"]), max_length=vec(td["max_length"]))
-    else:  # real_prize: the deterministic prize, or the stochastic one under SPCTSPEnv (as AntSystem)
-        data = dict(prize=vec(td["real_prize"]), penalty=vec(td["penalty"]))
-    if actions is not None:
-        actions = actions.detach().to(device=dev, dtype=torch.int64).contiguous()
-        if tuple(actions.shape) != (rows, w):
-            raise ValueError(f"actions must be {(rows, w)}, got {tuple(actions.shape)}")
-        if start_nodes is not None:
-            start_nodes = actions[:, 0]
-    if start_nodes is not None:
-        start_nodes = start_nodes.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-        if start_nodes.shape[0] != rows:
-            raise ValueError(f"start_nodes must be [n_ants * B] = [{rows}], got {tuple(start_nodes.shape)}")
-    if seed is None:
-        seed = int(torch.randint(0, 2**62, (1,)).item())
-    logps, ll, acts, lengths, reward = _DepotAntLogLikelihood.apply(heatmap, env_name, locs, data, start_nodes, actions,
-                                                                    n_ants, float(temperature), int(seed), err)
-    return {"actions": acts, "lengths": lengths, "logps": logps, "log_likelihood": ll, "reward": reward}
+        return grad, None, None, None, None, None, None, None, None
 
 
 def heatmap_rollout(heatmap: Tensor, locs: Tensor, *, n_ants: int, start_nodes: Tensor | None = None,
@@ -210,34 +136,48 @@ def heatmap_rollout(heatmap: Tensor, locs: Tensor, *, n_ants: int, start_nodes: 
     for name, t in (("heatmap", heatmap), ("locs", locs)):
         if not t.is_cuda:
             raise NotImplementedError(f"heatmap_rollout runs inside the MI355X kernel (rl4co_aco_tsp) only: {name} on {t.device}")
-    if env_name in _DEPOT_TRAIN_ENVS:
-        return _depot_rollout(heatmap, locs, td, env_name, n_ants, start_nodes, actions, temperature, seed, err)
-    if env_name != "tsp":
+    if env_name not in K.ACO_TD_KEYS:
         raise NotImplementedError(f"heatmap_rollout serves tsp, cvrp, op, pctsp and spctsp, got env_name={env_name!r}")
+    fam = K.aco_family(env_name)
+    depot = fam.ragged  # node 0 is the depot
+    if depot and td is None:
+        raise ValueError(f"heatmap_rollout(env_name={env_name!r}) takes td=: the instance's reset state (demand and "
+                         f"vehicle_capacity; prize and max_length; real_prize and penalty)")
+    for _, key in K.ACO_TD_KEYS[env_name]:
+        if not td[key].is_cuda:
+            raise NotImplementedError(f"heatmap_rollout runs inside the MI355X kernels only: td[{key!r}] on {td[key].device}")
     if heatmap.dim() != 3 or heatmap.shape[1] != heatmap.shape[2]:
-        raise ValueError(f"heatmap must be [B, N, N], got {tuple(heatmap.shape)}")
+        raise ValueError(f"heatmap must be {'[B, n, n]' if depot else '[B, N, N]'}, got {tuple(heatmap.shape)}")
+    if start_nodes is not None and not fam.start_nodes:
+        raise NotImplementedError(f"start_nodes (multistart) is served for tsp and cvrp, not for {env_name!r}: every ant "
+                                  f"starts at the depot")
     b, n, _ = heatmap.shape
     n_ants = int(n_ants)
-    rows = n_ants * b
+    rows, w = n_ants * b, fam.width(n)
     dev = heatmap.device
     heatmap = heatmap.to(torch.float32).contiguous()
-    locs = locs.detach().to(device=dev, dtype=torch.float32).contiguous()
+    data = {"locs": locs.detach().to(device=dev, dtype=torch.float32).contiguous(), **_instance(env_name, td, dev)}
     if actions is not None:
         actions = actions.detach().to(device=dev, dtype=torch.int64).contiguous()
-        if tuple(actions.shape) != (rows, n):
-            raise ValueError(f"actions must be {(rows, n)}, got {tuple(actions.shape)}")
-        start_nodes = actions[:, 0]
-    elif start_nodes is None:
+        if tuple(actions.shape) != (rows, w):
+            raise ValueError(f"actions must be {(rows, w)}, got {tuple(actions.shape)}")
+        if start_nodes is not None or not depot:
+            start_nodes = actions[:, 0]
+    elif start_nodes is None and not depot:  # TSPEnv's own multistart choice; on a depot graph every ant starts at the depot
         start_nodes = (torch.arange(n_ants, device=dev) % n).repeat_interleave(b)
-    start_nodes = start_nodes.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-    if start_nodes.shape[0] != rows:
-        raise ValueError(f"start_nodes must be [n_ants * B] = [{rows}], got {tuple(start_nodes.shape)}")
+    if start_nodes is not None:
+        start_nodes = start_nodes.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        if start_nodes.shape[0] != rows:
+            raise ValueError(f"start_nodes must be [n_ants * B] = [{rows}], got {tuple(start_nodes.shape)}")
     if seed is None:
         seed = int(torch.randint(0, 2**62, (1,)).item())
-    # err goes through as it is: with None the forward launch (K.aco_tsp) and the backward launch each read their own word
-    logps, ll, acts, reward = _AntLogLikelihood.apply(heatmap, locs, start_nodes, actions, n_ants, float(temperature),
-                                                      int(seed), err)
-    return {"actions": acts, "logps": logps, "log_likelihood": ll, "reward": reward}
+    # err goes through as it is: with None the forward launch and the backward launch each read their own word
+    logps, ll, acts, lengths, reward = _AntLogLikelihood.apply(heatmap, env_name, data, start_nodes, actions, n_ants,
+                                                               float(temperature), int(seed), err)
+    out = {"actions": acts, "lengths": lengths, "logps": logps, "log_likelihood": ll, "reward": reward}
+    if not depot:
+        del out["lengths"]
+    return out
 
 
 def deepaco_loss(out: dict, train_with_local_search: bool = False, ls_reward_aug_W: float = 0.95) -> Tensor:
@@ -299,68 +239,31 @@ class AntSystem:
 
     # ---- what the kernel takes ---------------------------------------------------------------------------------------
     def _check(self, td, env, decoding_kwargs: dict) -> float:
-        if getattr(env, "name", None) == "cvrp":
-            return self._check_cvrp(td, decoding_kwargs)
-        if getattr(env, "name", None) in _PRIZE_ENVS:
-            return self._check_prize(td, env.name, decoding_kwargs)
-        if getattr(env, "name", None) != "tsp":
+        name = getattr(env, "name", None)
+        if name not in _SERVES:
             raise NotImplementedError(f"AntSystem serves the tsp, cvrp, op, pctsp and spctsp environments only (rl4co_aco_tsp, "
                                       f"rl4co_aco_cvrp, rl4co_aco_prize), got {getattr(env, 'name', env)!r}")
-        for key in decoding_kwargs:
-            if key not in _SERVED_KWARGS:
-                raise NotImplementedError(f"decoding_kwargs[{key!r}] is not served by the Ant System kernel")
-        if not decoding_kwargs.get("multistart", False):
-            raise NotImplementedError("decoding_kwargs['multistart'] must be True: every ant starts from a given node")
-        if decoding_kwargs.get("num_starts", self.n_ants) != self.n_ants:
-            raise NotImplementedError(f"decoding_kwargs['num_starts'] must equal n_ants = {self.n_ants}")
-        if decoding_kwargs.get("select_best", False):
-            raise NotImplementedError("decoding_kwargs['select_best'] must be False: the update needs every ant's tour")
-        for name, t in (("log_heuristic", self.log_heuristic), ("pheromone", self.pheromone), ("td['locs']", td["locs"])):
-            if not t.is_cuda:
-                raise NotImplementedError(f"AntSystem runs inside the MI355X kernel (rl4co_aco_tsp) only: {name} on {t.device}")
-        return float(decoding_kwargs.get("temperature", 1.0))
-
-    def _check_cvrp(self, td, decoding_kwargs: dict) -> float:
-        if self.use_local_search:
-            raise NotImplementedError("use_local_search is not served for cvrp: the reference's CVRP local search is the "
-                                      "external HGS library")
-        for key in decoding_kwargs:
-            if key not in _SERVED_KWARGS_CVRP:
-                raise NotImplementedError(f"decoding_kwargs[{key!r}] is not served by the Ant System kernel")
-        multistart = bool(decoding_kwargs.get("multistart", False))
-        if multistart == bool(decoding_kwargs.get("multisample", False)):
-            raise NotImplementedError("exactly one of decoding_kwargs['multistart'] and decoding_kwargs['multisample'] must "
-                                      "be True for cvrp")
-        key = "num_starts" if multistart else "num_samples"
-        if decoding_kwargs.get(key, self.n_ants) != self.n_ants:
-            raise NotImplementedError(f"decoding_kwargs[{key!r}] must equal n_ants = {self.n_ants}")
-        if decoding_kwargs.get("select_best", False):
-            raise NotImplementedError("decoding_kwargs['select_best'] must be False: the update needs every ant's tour")
-        for name, t in (("log_heuristic", self.log_heuristic), ("pheromone", self.pheromone), ("td['locs']", td["locs"])):
-            if not t.is_cuda:  # (before td['demand'] is touched)
-                raise NotImplementedError(f"AntSystem runs inside the MI355X kernel (rl4co_aco_cvrp) only: {name} on {t.device}")
-        return float(decoding_kwargs.get("temperature", 1.0))
-
-    def _check_prize(self, td, name: str, decoding_kwargs: dict) -> float:
-        if self.use_local_search:
-            raise NotImplementedError(f"use_local_search is not served for {name}: the reference's destroy-and-repair local "
-                                      f"search is not part of the Ant System kernel")
-        if decoding_kwargs.get("multistart", False):
+        serves = _SERVES[name]
+        if self.use_local_search and serves.no_local_search:
+            raise NotImplementedError(f"use_local_search is not served for {name}: {serves.no_local_search}")
+        if "multistart" not in serves.modes and decoding_kwargs.get("multistart", False):
             raise NotImplementedError(f"decoding_kwargs['multistart'] is not served for {name}: every ant starts at the depot "
                                       f"(multisample)")
         for key in decoding_kwargs:
-            if key not in _SERVED_KWARGS_PRIZE and key != "multistart":
+            if key not in serves.kwargs and key != "multistart":
                 raise NotImplementedError(f"decoding_kwargs[{key!r}] is not served by the Ant System kernel for {name}")
-        if not decoding_kwargs.get("multisample", False):
-            raise NotImplementedError(f"decoding_kwargs['multisample'] must be True for {name}")
-        if decoding_kwargs.get("num_samples", self.n_ants) != self.n_ants:
-            raise NotImplementedError(f"decoding_kwargs['num_samples'] must equal n_ants = {self.n_ants}")
+        on = [mode for mode in serves.modes if decoding_kwargs.get(mode, False)]
+        if len(on) != 1:
+            asked = " and ".join(f"decoding_kwargs[{mode!r}]" for mode in serves.modes)
+            raise NotImplementedError(f"{'exactly one of ' if len(serves.modes) > 1 else ''}{asked} must be True for {name}")
+        if decoding_kwargs.get(_NUM_KEY[on[0]], self.n_ants) != self.n_ants:
+            raise NotImplementedError(f"decoding_kwargs[{_NUM_KEY[on[0]]!r}] must equal n_ants = {self.n_ants}")
         if decoding_kwargs.get("select_best", False):
             raise NotImplementedError("decoding_kwargs['select_best'] must be False: the update needs every ant's tour")
         for what, t in (("log_heuristic", self.log_heuristic), ("pheromone", self.pheromone), ("td['locs']", td["locs"])):
-            if not t.is_cuda:  # (before td['prize'], td['max_length'], td['real_prize'] or td['penalty'] is touched)
-                raise NotImplementedError(f"AntSystem runs inside the MI355X kernel (rl4co_aco_prize) only, env {name!r}: "
-                                          f"{what} on {t.device}")
+            if not t.is_cuda:  # (before any other key of td is touched)
+                raise NotImplementedError(f"AntSystem runs inside the MI355X kernel ({K.aco_family(name).symbol}) only: "
+                                          f"{what} on {t.device} (env {name!r})")
         return float(decoding_kwargs.get("temperature", 1.0))
 
     def _tensors(self, td):
@@ -396,9 +299,8 @@ class AntSystem:
     # ---- AntSystem.run (antsystem.py:87-118) -----------------------------------------------------------------------------
     def run(self, td_initial, env, n_iterations: int, decoding_kwargs: dict, disable_tqdm: bool = True):
         temperature = self._check(td_initial, env, decoding_kwargs)
-        if env.name == "cvrp" or env.name in _PRIZE_ENVS:
-            sampling = self._sampling_cvrp if env.name == "cvrp" else self._sampling_prize
-            out = sampling(td_initial, env, decoding_kwargs, temperature, n_iterations)
+        if K.aco_family(env.name).ragged:
+            out = self._sampling(td_initial, env, decoding_kwargs, temperature, n_iterations)
             for i in range(n_iterations):
                 self.final_reward_cache[i] = out["final_reward_cache"][i].clone()
             self.last_iterations = {"actions": out["iter_actions"], "reward": out["iter_reward"], "lengths": out["iter_lengths"]}
@@ -432,11 +334,8 @@ class AntSystem:
     def _one_step(self, td, env, decoding_kwargs: dict):
         """One iteration: sample, optional local search, update. Returns (actions [rows, N], reward [rows]), ant-major."""
         temperature = self._check(td, env, decoding_kwargs)
-        if env.name == "cvrp":  # actions [rows, W], zero-filled after each row's length
-            out = self._sampling_cvrp(td, env, decoding_kwargs, temperature, 1)
-            return out["actions"], out["reward"]
-        if env.name in _PRIZE_ENVS:  # actions [rows, n], zero-filled after each row's length
-            out = self._sampling_prize(td, env, decoding_kwargs, temperature, 1)
+        if K.aco_family(env.name).ragged:  # actions [rows, W], zero-filled after each row's length
+            out = self._sampling(td, env, decoding_kwargs, temperature, 1)
             return out["actions"], out["reward"]
         heu, locs = self._tensors(td)
         starts = self._start_nodes(td, env, decoding_kwargs)[None].contiguous()
@@ -462,21 +361,19 @@ class AntSystem:
         self._take_record(out)
         return actions, reward
 
-    # ---- CVRP: sampling and update of ``n_iterations`` iterations in one launch (rl4co_aco_cvrp) -----------------------------
-    def _sampling_cvrp(self, td, env, decoding_kwargs: dict, temperature: float, n_iterations: int) -> dict:
+    # ---- depot graphs: sampling and update of ``n_iterations`` iterations in one launch (rl4co_aco_cvrp, rl4co_aco_prize) ------
+    def _sampling(self, td, env, decoding_kwargs: dict, temperature: float, n_iterations: int) -> dict:
         heu, locs = self._tensors(td)
         dev = heu.device
-        demand = td["demand"].detach().to(device=dev, dtype=torch.float32).contiguous()
-        capacity = td["vehicle_capacity"].detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        starts = None
+        data = _instance(env.name, td, dev)
         if decoding_kwargs.get("multistart", False):  # Sampling.pre_decoder_hook: called once per iteration
-            starts = torch.stack([self._start_nodes(td, env, decoding_kwargs) for _ in range(n_iterations)], 0).contiguous()
+            data["start_nodes"] = torch.stack([self._start_nodes(td, env, decoding_kwargs) for _ in range(n_iterations)],
+                                              0).contiguous()
         seed, offset = self._next_seed()
         err = K.new_error_word(dev)
-        record = self._padded_record(K.aco_cvrp_width(heu.shape[1]))
-        out = K.aco_cvrp(self.pheromone, iterations=n_iterations, log_heuristic=heu, locs=locs, demand=demand,
-                         vehicle_capacity=capacity, start_nodes=starts, philox_seed=seed, philox_offset=offset,
-                         record_iterations=True, err=err, **record, **self._common(temperature))
+        record = self._padded_record(K.aco_family(env.name).width(heu.shape[1]))
+        out = K.aco_search(env.name, self.pheromone, iterations=n_iterations, log_heuristic=heu, locs=locs, philox_seed=seed,
+                           philox_offset=offset, record_iterations=True, err=err, **data, **record, **self._common(temperature))
         self._take_ragged_record(out, err, record["has_best"])
         return out
 
@@ -501,27 +398,6 @@ class AntSystem:
         for i, it in enumerate(replaced):  # antsystem.py:238-245: the entry has the width of its iteration's batch
             if it >= 0:
                 self.final_actions[i] = out["final_actions"][i, : widths[it]].clone()
-
-    # ---- OP / PCTSP: sampling and update of ``n_iterations`` iterations in one launch (rl4co_aco_prize) -----------------------
-    def _sampling_prize(self, td, env, decoding_kwargs: dict, temperature: float, n_iterations: int) -> dict:
-        heu, locs = self._tensors(td)
-        dev = heu.device
-
-        def vec(key):
-            return td[key].detach().to(device=dev, dtype=torch.float32).contiguous()
-
-        if env.name == "op":
-            data = dict(prize=vec("prize"), max_length=vec("max_length"))
-        else:  # real_prize: the deterministic prize, or the stochastic one under SPCTSPEnv (the env's reset picked it)
-            data = dict(prize=vec("real_prize"), penalty=vec("penalty"))
-        seed, offset = self._next_seed()
-        err = K.new_error_word(dev)
-        record = self._padded_record(heu.shape[1])
-        out = K.aco_prize(self.pheromone, env=env.name, iterations=n_iterations, log_heuristic=heu, locs=locs,
-                          philox_seed=seed, philox_offset=offset, record_iterations=True, err=err, **data, **record,
-                          **self._common(temperature))
-        self._take_ragged_record(out, err, record["has_best"])
-        return out
 
     # ---- AntSystem.local_search (antsystem.py:173-230), without the host round trip --------------------------------------
     def local_search(self, td, env, actions: Tensor, decoding_kwargs: dict):

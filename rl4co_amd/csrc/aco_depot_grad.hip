@@ -51,12 +51,12 @@
 // tools/aco_bench.py --train's end-to-end time.
 #include <hip/hip_runtime.h>
 
+#include "ant_grad.h"
 #include "ant_rules.h"
-#include "ant_system.h"
 
 namespace {
 
-using namespace rl4co::aco;  // ant_system.h: the constants, check_indices, log_softmax_max / _lse, launch; ant_rules.h
+using namespace rl4co::aco;  // ant_system.h: the constants, check_indices, log_softmax_max / _lse, launch; ant_grad.h; ant_rules.h
 
 constexpr int kTableLdsEntries = 8192;
 constexpr uint16_t kNoPos = 0xffff;
@@ -78,8 +78,9 @@ __global__ void __launch_bounds__(kThreads) aco_depot_grad_kernel(const rl4co_ac
   constexpr bool kCvrp = ENV == RL4CO_ENV_CVRP, kOp = ENV == RL4CO_ENV_OP;
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int S = a.row_split, b = (int)(blockIdx.x / (unsigned)S), s = (int)(blockIdx.x - (unsigned)b * (unsigned)S);
-  const int B = a.B, N = a.N, A = a.n_ants;
+  const int S = a.row_split, B = a.B, N = a.N, A = a.n_ants;
+  int b, s;
+  grad_split(S, b, s);
   const int C = N - 1, W = row_width(ENV, N), NS = node_stride(N), K = (N + 63) >> 6;
   const int64_t AN = (int64_t)A * N;
   float* v0 = reinterpret_cast<float*>(smem + kScratchBytes);  // CVRP: demand (word c is demand[c - 1], word 0 demand[0])
@@ -204,8 +205,7 @@ __global__ void __launch_bounds__(kThreads) aco_depot_grad_kernel(const rl4co_ac
     if (!ok && tid == 0) atomicOr(a.err, (int)bits);
   }
   if (!ok) {  // the instance's gradient is all zeros: this workgroup's rows
-    for (int i = s + S * w; i < N; i += S * kWaves)
-      for (int n = lane; n < N; n += 64) gout[(int64_t)i * N + n] = 0.0f;
+    grad_zero_rows(gout, N, s, S, w, lane);
     return;
   }
 
@@ -337,12 +337,9 @@ __global__ void __launch_bounds__(kThreads) aco_depot_grad_kernel(const rl4co_ac
 
 template <int ENV, bool LDS>
 int launch_grad(const rl4co_aco_depot_grad_args& a, int bytes, hipStream_t s) {
-  const int K = (a.N + 63) >> 6, grid = a.B * a.row_split;
-  if (K <= 1) return launch<aco_depot_grad_kernel<ENV, 1, LDS>>(a, bytes, s, grid);
-  if (K <= 2) return launch<aco_depot_grad_kernel<ENV, 2, LDS>>(a, bytes, s, grid);
-  if (K <= 4) return launch<aco_depot_grad_kernel<ENV, 4, LDS>>(a, bytes, s, grid);
-  if (K <= 8) return launch<aco_depot_grad_kernel<ENV, 8, LDS>>(a, bytes, s, grid);
-  return launch<aco_depot_grad_kernel<ENV, 16, LDS>>(a, bytes, s, grid);
+  return grad_ladder(a.N, [&](auto kmax) {
+    return launch<aco_depot_grad_kernel<ENV, decltype(kmax)::value, LDS>>(a, bytes, s, a.B * a.row_split);
+  });
 }
 
 template <int ENV>

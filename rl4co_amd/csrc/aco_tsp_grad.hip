@@ -36,11 +36,11 @@
 // end-to-end time.
 #include <hip/hip_runtime.h>
 
-#include "ant_system.h"
+#include "ant_grad.h"
 
 namespace {
 
-using namespace rl4co::aco;  // ant_system.h: the constants, check_indices, log_softmax_max / _lse, launch
+using namespace rl4co::aco;  // ant_system.h: the constants, check_indices, log_softmax_max / _lse, launch; ant_grad.h
 
 constexpr int kPosLdsEntries = 16384;
 constexpr uint16_t kNoPos = 0xffff;
@@ -50,8 +50,9 @@ __global__ void __launch_bounds__(kThreads) aco_tsp_grad_kernel(const rl4co_aco_
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int S = a.row_split, b = (int)(blockIdx.x / (unsigned)S), s = (int)(blockIdx.x - (unsigned)b * (unsigned)S);
-  const int B = a.B, N = a.N, A = a.n_ants;
+  const int S = a.row_split, B = a.B, N = a.N, A = a.n_ants;
+  int b, s;
+  grad_split(S, b, s);
   const int64_t AN = (int64_t)A * N;
   uint16_t* pos = LDS ? reinterpret_cast<uint16_t*>(smem + kScratchBytes) : a.pos_scratch + (int64_t)blockIdx.x * AN;
   float* gout = a.grad_heatmap + (int64_t)b * N * N;
@@ -75,8 +76,7 @@ __global__ void __launch_bounds__(kThreads) aco_tsp_grad_kernel(const rl4co_aco_
     if (!ok && tid == 0) atomicOr(a.err, RL4CO_EBIT_INVALID_TOUR);
   }
   if (!ok) {  // the instance's gradient is all zeros: this workgroup's rows
-    for (int i = s + S * w; i < N; i += S * kWaves)
-      for (int n = lane; n < N; n += 64) gout[(int64_t)i * N + n] = 0.0f;
+    grad_zero_rows(gout, N, s, S, w, lane);
     return;
   }
 
@@ -139,12 +139,9 @@ __global__ void __launch_bounds__(kThreads) aco_tsp_grad_kernel(const rl4co_aco_
 
 template <bool LDS>
 int launch_grad(const rl4co_aco_tsp_grad_args& a, int bytes, hipStream_t s) {
-  const int K = (a.N + 63) >> 6, grid = a.B * a.row_split;
-  if (K <= 1) return launch<aco_tsp_grad_kernel<1, LDS>>(a, bytes, s, grid);
-  if (K <= 2) return launch<aco_tsp_grad_kernel<2, LDS>>(a, bytes, s, grid);
-  if (K <= 4) return launch<aco_tsp_grad_kernel<4, LDS>>(a, bytes, s, grid);
-  if (K <= 8) return launch<aco_tsp_grad_kernel<8, LDS>>(a, bytes, s, grid);
-  return launch<aco_tsp_grad_kernel<16, LDS>>(a, bytes, s, grid);
+  return grad_ladder(a.N, [&](auto kmax) {
+    return launch<aco_tsp_grad_kernel<decltype(kmax)::value, LDS>>(a, bytes, s, a.B * a.row_split);
+  });
 }
 
 }  // namespace

@@ -7,6 +7,7 @@ There is no CPU path: a non-CUDA tensor is an error.
 from __future__ import annotations
 
 import ctypes as C
+from typing import Callable, NamedTuple
 
 import torch
 from torch import Tensor
@@ -803,9 +804,204 @@ def nargnn_depot_heatmap(locs: Tensor, feats: Tensor, neighbors: Tensor, edge_co
     return heatmap, node_embed
 
 
+# ---- the Ant System: one table of families, one launch path for the search, one for the backward ---------------------------
+_ACO_PRIZE_ENVS = {"op": _lib.ENV_OP, "pctsp": _lib.ENV_PCTSP, "spctsp": _lib.ENV_PCTSP}  # spctsp: the caller's prize is the stochastic one
+_ACO_DEPOT_GRAD_ENVS = {"cvrp": _lib.ENV_CVRP, **_ACO_PRIZE_ENVS}
+
+
+def aco_cvrp_width(n: int) -> int:
+    """W = max(C + 1, 2 C - 1), C = n - 1: the longest action row the reference's CVRP sampling loop can produce."""
+    return max(n, 2 * n - 3)
+
+
+def aco_depot_width(env: str, n: int) -> int:
+    """The width of a sampled row: :func:`aco_cvrp_width` for cvrp, ``n`` for op / pctsp / spctsp."""
+    return aco_cvrp_width(n) if env == "cvrp" else n
+
+
+class AcoTensor(NamedTuple):
+    """One fp32 instance tensor of a search binding. ``sample``: the SAMPLE phase needs it — always, never, or under these
+    ``env`` values. ``flat``: taken as ``reshape(-1)`` ([B] or [B, 1])."""
+    key: str
+    shape: Callable[[int, int], tuple]  # of (b, n)
+    text: str  # the shape as a message states it
+    sample: bool | tuple[str, ...] = False
+    flat: bool = False
+
+
+class AcoFamily(NamedTuple):
+    """One Ant System search kernel. The struct's field names are the binding's keywords and the returned dict's keys."""
+    name: str  # the public binding
+    symbol: str
+    args: type
+    envs: dict  # environment name -> RL4CO_ENV_*
+    width: Callable[[int], int]  # of a sampled row
+    lds_nodes: Callable[[int], int]  # of RL4CO_ENV_*: the *_lds_nodes query
+    instance: tuple[AcoTensor, ...]
+    ragged: bool  # depot graph: lengths / iter_lengths / final_iteration / T / iteration_base, zero-filled outputs
+    start_nodes: bool
+    scalars: tuple[str, ...]  # scalar struct fields beyond the shared ones
+    cpu_refused: tuple[str, ...]  # tensors a NotImplementedError names before anything else is looked at (tsp: none)
+
+
+_LOCS = AcoTensor("locs", lambda b, n: (b, n, 2), "[B, n, 2]")
+ACO_FAMILIES = (
+    AcoFamily("aco_tsp", "rl4co_aco_tsp", _lib.AcoTspArgs, {"tsp": _lib.ENV_TSP}, lambda n: n,
+              lambda env: _lib.lib().rl4co_aco_tsp_lds_nodes(), (_LOCS,), False, True, (), ()),
+    AcoFamily("aco_cvrp", "rl4co_aco_cvrp", _lib.AcoCvrpArgs, {"cvrp": _lib.ENV_CVRP}, aco_cvrp_width,
+              lambda env: _lib.lib().rl4co_aco_cvrp_lds_nodes(),
+              (_LOCS, AcoTensor("demand", lambda b, n: (b, n - 1), "[B, n - 1]", True),
+               AcoTensor("vehicle_capacity", lambda b, n: (b,), "[B]", True, flat=True)),
+              True, True, ("T", "iteration_base"), ("pheromone", "log_heuristic", "locs", "demand")),
+    AcoFamily("aco_prize", "rl4co_aco_prize", _lib.AcoPrizeArgs, _ACO_PRIZE_ENVS, lambda n: n,
+              lambda env: _lib.lib().rl4co_aco_prize_lds_nodes(env),
+              (_LOCS._replace(sample=True), AcoTensor("prize", lambda b, n: (b, n), "[B, n]", True),
+               AcoTensor("penalty", lambda b, n: (b, n), "[B, n]", ("pctsp", "spctsp")),
+               AcoTensor("max_length", lambda b, n: (b, n), "[B, n]", ("op",))),
+              True, False, ("T", "iteration_base", "env", "n_workgroups"),
+              ("pheromone", "log_heuristic", "locs", "prize", "penalty", "max_length")),
+)
+# the environment's reset state -> the bindings' instance keywords: ((keyword, td key), ...); real_prize: the deterministic
+# prize, or the stochastic one under SPCTSPEnv (the env's reset picked it)
+ACO_TD_KEYS = {"tsp": (), "cvrp": (("demand", "demand"), ("vehicle_capacity", "vehicle_capacity")),
+               "op": (("prize", "prize"), ("max_length", "max_length")),
+               "pctsp": (("prize", "real_prize"), ("penalty", "penalty")),
+               "spctsp": (("prize", "real_prize"), ("penalty", "penalty"))}
+
+
+def aco_family(env: str) -> AcoFamily:
+    return next(fam for fam in ACO_FAMILIES if env in fam.envs)
+
+
+def aco_search(env: str, pheromone: Tensor, **kw) -> dict:
+    """:func:`aco_tsp`, :func:`aco_cvrp` or :func:`aco_prize`, whichever serves ``env``."""
+    fam = aco_family(env)
+    return globals()[fam.name](pheromone, **kw, **({"env": env} if "env" in fam.scalars else {}))
+
+
+def _aco_launch(symbol: str, a, values: dict, err: Tensor | None, dev) -> None:
+    """Fill the struct ``a`` field by field from ``values`` (tensors as pointers, a pointer without a value NULL), launch and
+    check. With ``err`` the sticky bits are OR-ed into the caller's word; without, the launch's own word is read back."""
+    own = err is None
+    values["err"] = new_error_word(dev) if own else _dev(err, torch.int32, "err")
+    for name, ctype in a._fields_:
+        setattr(a, name, _ptr(values.get(name)) if ctype is C.c_void_p else values[name])
+    st = getattr(_lib.lib(), symbol)(C.byref(a), _stream())
+    _lib.check(st, symbol)
+    if own:
+        raise_if_error(values["err"])
+
+
+def _aco_search(fam: AcoFamily, pheromone, *, n_ants, phases, iterations, log_heuristic, alpha, beta, decay, Q, temperature,
+                ln_noise, philox_seed, philox_offset, philox_seed_dev, forced_actions, actions, reward, final_reward,
+                final_actions, has_best, all_logps, record_iterations, err, env, start_nodes=None, final_iteration=None,
+                iteration_base=0, n_workgroups=0, **given) -> dict:
+    """The one body of the three search bindings; ``given``: the family's instance tensors by keyword."""
+    who, d = fam.name, "n" if fam.ragged else "N"
+    if env not in fam.envs:
+        raise NotImplementedError(f"{who} ({fam.symbol}) serves {sorted(fam.envs)}, got env = {env!r}")
+    for name in fam.cpu_refused:
+        t = {"pheromone": pheromone, "log_heuristic": log_heuristic, **given}[name]
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError(f"{who} runs inside the MI355X kernel ({fam.symbol}) only: {name} on {t.device}")
+    pheromone = _dev(pheromone, torch.float32, "pheromone")
+    if pheromone.dim() != 3 or pheromone.shape[1] != pheromone.shape[2]:
+        raise ValueError(f"pheromone must be [B, {d}, {d}], got {tuple(pheromone.shape)}")
+    b, n, _ = pheromone.shape
+    if not 2 <= n <= 1024:
+        raise NotImplementedError(f"{who} serves 2..1024 nodes{' (depot included)' if fam.ragged else ''}, got {d} = {n}")
+    n_ants, iterations = int(n_ants), int(iterations)
+    rows, w = n_ants * b, fam.width(n)
+    dev = pheromone.device
+    sample, update = bool(phases & _lib.ACO_SAMPLE), bool(phases & _lib.ACO_UPDATE)
+    new = torch.zeros if fam.ragged else torch.empty  # a ragged row is zero-filled after its length
+
+    def shaped(t, dtype, shape, name):
+        if t is None:
+            return None
+        t = _dev(t, dtype, name)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    log_heuristic = shaped(log_heuristic, torch.float32, (b, n, n), "log_heuristic")
+    for it in fam.instance:
+        t = given[it.key]
+        given[it.key] = shaped(t.reshape(-1) if it.flat and t is not None else t, torch.float32, it.shape(b, n), it.key)
+    if fam.start_nodes:
+        start_nodes = shaped(start_nodes, torch.int64, (iterations, rows), "start_nodes")
+    ln_noise = shaped(ln_noise, torch.float32, (iterations, w if fam.ragged else n - 1, rows, n), "ln_noise")
+    forced_actions = shaped(forced_actions, torch.int64, (rows, w), "forced_actions")
+    t = w
+    if sample:
+        if actions is not None or reward is not None:
+            raise ValueError("actions / reward are outputs of the SAMPLE phase")
+        needs = [it for it in fam.instance if it.sample is True or (it.sample and env in it.sample)]
+        if any(given[it.key] is None for it in needs):
+            texts = [f"{it.key} {it.text}" for it in needs]
+            raise ValueError("the SAMPLE phase takes " + ", ".join(texts[:-1]) + " and " + texts[-1])
+        actions = new((rows, w), dtype=torch.int64, device=dev)
+        reward = torch.zeros(rows, dtype=torch.float32, device=dev)
+    elif actions is None or reward is None:
+        raise ValueError(f"the UPDATE phase alone takes actions [rows, {'T' if fam.ragged else 'N'}] and reward [rows]")
+    elif fam.ragged:
+        t = actions.shape[-1]
+        if t < 2:
+            raise ValueError(f"actions must be [rows, T] with T >= 2, got {tuple(actions.shape)}")
+    actions = shaped(actions, torch.int64, (rows, t), "actions")
+    reward = shaped(reward, torch.float32, (rows,), "reward")
+    out = {"actions": actions, "reward": reward}
+    if sample:
+        if fam.ragged:
+            out["lengths"] = torch.zeros(rows, dtype=torch.int32, device=dev)
+        out["logps"] = new((rows, w), dtype=torch.float32, device=dev)
+        if all_logps:
+            out["all_logps"] = new((rows, w, n), dtype=torch.float32, device=dev)
+        if record_iterations:
+            out["iter_actions"] = new((iterations, rows, w), dtype=torch.int64, device=dev)
+            if fam.ragged:
+                out["iter_lengths"] = torch.zeros((iterations, rows), dtype=torch.int32, device=dev)
+            out["iter_reward"] = torch.zeros((iterations, rows), dtype=torch.float32, device=dev)
+    if update:
+        if (final_reward is None) != (final_actions is None):
+            raise ValueError("final_reward and final_actions come together")
+        if final_reward is None:
+            if has_best:
+                raise ValueError("has_best needs final_reward and final_actions")
+            final_reward = torch.zeros(b, dtype=torch.float32, device=dev)
+            final_actions = torch.zeros((b, t), dtype=torch.int64, device=dev)
+        out["final_reward"] = shaped(final_reward, torch.float32, (b,), "final_reward")
+        out["final_actions"] = shaped(final_actions, torch.int64, (b, t), "final_actions")
+        if fam.ragged:
+            if final_iteration is None:
+                final_iteration = torch.full((b,), -1, dtype=torch.int32, device=dev)
+            out["final_iteration"] = shaped(final_iteration, torch.int32, (b,), "final_iteration")
+        out["final_reward_cache"] = torch.zeros((iterations, b), dtype=torch.float32, device=dev)
+    scratch = torch.empty((b, n, n), dtype=torch.float32, device=dev) if n > int(fam.lds_nodes(fam.envs[env])) else None
+    extra = dict(T=t, iteration_base=int(iteration_base), env=fam.envs[env], n_workgroups=int(n_workgroups))
+    values = dict(out, B=b, N=n, n_ants=n_ants, iterations=iterations, phases=int(phases), has_best=int(bool(has_best)),
+                  alpha=alpha, beta=beta, decay=decay, Q=Q, temperature=temperature, reserved0=0,
+                  philox_seed=int(philox_seed) & (2**64 - 1), philox_offset=int(philox_offset) & (2**64 - 1),
+                  philox_seed_dev=philox_seed_dev, log_heuristic=log_heuristic, pheromone=pheromone, start_nodes=start_nodes,
+                  ln_noise=ln_noise, forced_actions=forced_actions, logits_scratch=scratch, **given,
+                  **{key: extra[key] for key in fam.scalars})
+    _aco_launch(fam.symbol, fam.args(), values, err, dev)
+    return out
+
+
 def aco_lds_nodes() -> int:
     """Largest node count at which the Ant System kernel keeps logits and pheromone in LDS (a host query)."""
     return int(_lib.lib().rl4co_aco_tsp_lds_nodes())
+
+
+def aco_cvrp_lds_nodes() -> int:
+    """Largest node count (depot included) at which the CVRP Ant System kernel keeps logits and pheromone in LDS."""
+    return int(_lib.lib().rl4co_aco_cvrp_lds_nodes())
+
+
+def aco_prize_lds_nodes(env: str) -> int:
+    """Largest node count (depot included) at which the OP / PCTSP Ant System kernel keeps logits and pheromone in LDS."""
+    return int(_lib.lib().rl4co_aco_prize_lds_nodes(_ACO_PRIZE_ENVS[env]))
 
 
 def aco_tsp(pheromone: Tensor, *, n_ants: int, phases: int = _lib.ACO_SAMPLE | _lib.ACO_UPDATE, iterations: int = 1,
@@ -827,156 +1023,7 @@ def aco_tsp(pheromone: Tensor, *, n_ants: int, phases: int = _lib.ACO_SAMPLE | _
     actions, reward, logps, final_reward, final_actions, final_reward_cache [iterations, B] and, on request, all_logps
     [rows, N, N], iter_actions [iterations, rows, N], iter_reward [iterations, rows]. With ``err`` the sticky bits are
     OR-ed into the caller's word and nothing is synchronised; without it the word is read back and a set bit raises."""
-    pheromone = _dev(pheromone, torch.float32, "pheromone")
-    if pheromone.dim() != 3 or pheromone.shape[1] != pheromone.shape[2]:
-        raise ValueError(f"pheromone must be [B, N, N], got {tuple(pheromone.shape)}")
-    b, n, _ = pheromone.shape
-    if not 2 <= n <= 1024:
-        raise NotImplementedError(f"aco_tsp serves 2..1024 nodes, got N = {n}")
-    n_ants, iterations = int(n_ants), int(iterations)
-    rows = n_ants * b
-    dev = pheromone.device
-    sample, update = bool(phases & _lib.ACO_SAMPLE), bool(phases & _lib.ACO_UPDATE)
-
-    def shaped(t, dtype, shape, name):
-        if t is None:
-            return None
-        t = _dev(t, dtype, name)
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
-        return t
-
-    log_heuristic = shaped(log_heuristic, torch.float32, (b, n, n), "log_heuristic")
-    locs = shaped(locs, torch.float32, (b, n, 2), "locs")
-    start_nodes = shaped(start_nodes, torch.int64, (iterations, rows), "start_nodes")
-    ln_noise = shaped(ln_noise, torch.float32, (iterations, n - 1, rows, n), "ln_noise")
-    forced_actions = shaped(forced_actions, torch.int64, (rows, n), "forced_actions")
-    if sample:
-        if actions is not None or reward is not None:
-            raise ValueError("actions / reward are outputs of the SAMPLE phase")
-        actions = torch.empty((rows, n), dtype=torch.int64, device=dev)
-        reward = torch.zeros(rows, dtype=torch.float32, device=dev)
-    elif actions is None or reward is None:
-        raise ValueError("the UPDATE phase alone takes actions [rows, N] and reward [rows]")
-    actions = shaped(actions, torch.int64, (rows, n), "actions")
-    reward = shaped(reward, torch.float32, (rows,), "reward")
-    out = {"actions": actions, "reward": reward}
-    if sample:
-        out["logps"] = torch.empty((rows, n), dtype=torch.float32, device=dev)
-        if all_logps:
-            out["all_logps"] = torch.empty((rows, n, n), dtype=torch.float32, device=dev)
-        if record_iterations:
-            out["iter_actions"] = torch.empty((iterations, rows, n), dtype=torch.int64, device=dev)
-            out["iter_reward"] = torch.zeros((iterations, rows), dtype=torch.float32, device=dev)
-    if update:
-        if (final_reward is None) != (final_actions is None):
-            raise ValueError("final_reward and final_actions come together")
-        if final_reward is None:
-            if has_best:
-                raise ValueError("has_best needs final_reward and final_actions")
-            final_reward = torch.zeros(b, dtype=torch.float32, device=dev)
-            final_actions = torch.zeros((b, n), dtype=torch.int64, device=dev)
-        out["final_reward"] = shaped(final_reward, torch.float32, (b,), "final_reward")
-        out["final_actions"] = shaped(final_actions, torch.int64, (b, n), "final_actions")
-        out["final_reward_cache"] = torch.zeros((iterations, b), dtype=torch.float32, device=dev)
-    scratch = torch.empty((b, n, n), dtype=torch.float32, device=dev) if n > aco_lds_nodes() else None
-    own = err is None
-    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
-    a = _lib.AcoTspArgs()
-    a.B, a.N, a.n_ants, a.iterations, a.phases, a.has_best = b, n, n_ants, iterations, int(phases), int(bool(has_best))
-    a.alpha, a.beta, a.decay, a.Q, a.temperature, a.reserved0 = alpha, beta, decay, Q, temperature, 0
-    a.philox_seed, a.philox_offset = int(philox_seed) & (2**64 - 1), int(philox_offset) & (2**64 - 1)
-    a.philox_seed_dev = _ptr(philox_seed_dev)
-    a.log_heuristic, a.pheromone, a.locs, a.start_nodes = _ptr(log_heuristic), _ptr(pheromone), _ptr(locs), _ptr(start_nodes)
-    a.ln_noise, a.forced_actions, a.logits_scratch = _ptr(ln_noise), _ptr(forced_actions), _ptr(scratch)
-    a.actions, a.reward, a.logps, a.all_logps = _ptr(actions), _ptr(reward), _ptr(out.get("logps")), _ptr(out.get("all_logps"))
-    a.iter_actions, a.iter_reward = _ptr(out.get("iter_actions")), _ptr(out.get("iter_reward"))
-    a.final_reward, a.final_actions = _ptr(out.get("final_reward")), _ptr(out.get("final_actions"))
-    a.final_reward_cache, a.err = _ptr(out.get("final_reward_cache")), _ptr(err)
-    st = _lib.lib().rl4co_aco_tsp(C.byref(a), _stream())
-    _lib.check(st, "rl4co_aco_tsp")
-    if own:
-        raise_if_error(err)
-    return out
-
-
-def aco_grad_lds_entries() -> int:
-    """Largest ``n_ants * N`` whose inverse-permutation table the log-likelihood backward keeps in LDS (a host query)."""
-    return int(_lib.lib().rl4co_aco_tsp_grad_lds_entries())
-
-
-def aco_grad_row_split(b: int, n: int, cus: int) -> int:
-    """Workgroups per instance of :func:`aco_tsp_logp_grad` when the caller names none: about two workgroups per CU, at
-    least sixteen heatmap rows per workgroup (each repeats the table build). An estimate, not a measured optimum."""
-    return max(1, min(n // 16, (2 * cus) // b))
-
-
-def aco_tsp_logp_grad(heatmap: Tensor, actions: Tensor, grad_ll: Tensor, *, grad_steps: Tensor | None = None,
-                      temperature: float = 1.0, row_split: int | None = None, pos_in_scratch: bool | None = None,
-                      err: Tensor | None = None) -> Tensor:
-    """The gradient of the ants' log-likelihoods with respect to the heatmap in one launch (rl4co_aco_tsp_logp_grad; the
-    header states the arithmetic): ``heatmap`` [B, N, N] fp32 (the logits the forward sampled from, not divided by the
-    temperature), ``actions`` [rows, N] int64 with rows = n_ants * B ant-major, ``grad_ll`` [rows] fp32 and optionally
-    ``grad_steps`` [rows, N] fp32 (column 0 ignored) -> ``grad_heatmap`` [B, N, N] fp32, every word written.
-
-    ``row_split``: workgroups per instance (None: :func:`aco_grad_row_split`); any value gives the same bits.
-    ``pos_in_scratch``: keep the inverse-permutation table in a global scratch instead of LDS (None: only above
-    :func:`aco_grad_lds_entries`). ``err`` as in :func:`aco_tsp`."""
-    for name, t, dtype in (("heatmap", heatmap, torch.float32), ("actions", actions, torch.int64),
-                           ("grad_ll", grad_ll, torch.float32), ("grad_steps", grad_steps, torch.float32)):
-        if t is not None and t.dtype != dtype:
-            raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
-    if heatmap.dim() != 3 or heatmap.shape[1] != heatmap.shape[2]:
-        raise ValueError(f"heatmap must be [B, N, N], got {tuple(heatmap.shape)}")
-    b, n, _ = heatmap.shape
-    if not 2 <= n <= 1024:
-        raise NotImplementedError(f"aco_tsp_logp_grad serves 2..1024 nodes, got N = {n}")
-    if actions.dim() != 2 or actions.shape[1] != n or actions.shape[0] == 0 or actions.shape[0] % b:
-        raise ValueError(f"actions must be [n_ants * B, N] = [k * {b}, {n}], got {tuple(actions.shape)}")
-    rows = actions.shape[0]
-    n_ants = rows // b
-    if tuple(grad_ll.shape) != (rows,):
-        raise ValueError(f"grad_ll must be {(rows,)}, got {tuple(grad_ll.shape)}")
-    if grad_steps is not None and tuple(grad_steps.shape) != (rows, n):
-        raise ValueError(f"grad_steps must be {(rows, n)}, got {tuple(grad_steps.shape)}")
-    if not temperature > 0:
-        raise ValueError(f"temperature must be positive, got {temperature}")
-    if row_split is not None and not 1 <= int(row_split) <= n:
-        raise ValueError(f"row_split must be in [1, N = {n}], got {row_split}")
-    _dev(heatmap, None, "heatmap"), _dev(actions, None, "actions"), _dev(grad_ll, None, "grad_ll")
-    if grad_steps is not None:
-        _dev(grad_steps, None, "grad_steps")
-    dev = heatmap.device
-    if row_split is None:
-        row_split = aco_grad_row_split(b, n, torch.cuda.get_device_properties(dev).multi_processor_count)
-    fits = n_ants * n <= aco_grad_lds_entries()
-    if pos_in_scratch is None:
-        pos_in_scratch = not fits
-    elif not pos_in_scratch and not fits:
-        raise ValueError(f"n_ants * N = {n_ants * n} is above the LDS table's {aco_grad_lds_entries()} entries")
-    scratch = torch.empty((b * int(row_split), n_ants, n), dtype=torch.int16, device=dev) if pos_in_scratch else None
-    grad = torch.empty((b, n, n), dtype=torch.float32, device=dev)
-    own = err is None
-    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
-    a = _lib.AcoTspGradArgs()
-    a.B, a.N, a.n_ants, a.row_split, a.temperature, a.reserved0 = b, n, n_ants, int(row_split), float(temperature), 0
-    a.heatmap, a.actions, a.grad_ll, a.grad_steps = _ptr(heatmap), _ptr(actions), _ptr(grad_ll), _ptr(grad_steps)
-    a.pos_scratch, a.grad_heatmap, a.err = _ptr(scratch), _ptr(grad), _ptr(err)
-    st = _lib.lib().rl4co_aco_tsp_logp_grad(C.byref(a), _stream())
-    _lib.check(st, "rl4co_aco_tsp_logp_grad")
-    if own:
-        raise_if_error(err)
-    return grad
-
-
-def aco_cvrp_lds_nodes() -> int:
-    """Largest node count (depot included) at which the CVRP Ant System kernel keeps logits and pheromone in LDS."""
-    return int(_lib.lib().rl4co_aco_cvrp_lds_nodes())
-
-
-def aco_cvrp_width(n: int) -> int:
-    """W = max(C + 1, 2 C - 1), C = n - 1: the longest action row the reference's CVRP sampling loop can produce."""
-    return max(n, 2 * n - 3)
+    return _aco_search(ACO_FAMILIES[0], env="tsp", **locals())  # (locals(): the arguments as they came)
 
 
 def aco_cvrp(pheromone: Tensor, *, n_ants: int, phases: int = _lib.ACO_SAMPLE | _lib.ACO_UPDATE, iterations: int = 1,
@@ -1002,108 +1049,7 @@ def aco_cvrp(pheromone: Tensor, *, n_ants: int, phases: int = _lib.ACO_SAMPLE | 
     launch wrote: actions, lengths, reward, logps, final_reward, final_actions, final_iteration, final_reward_cache
     [iterations, B] and, on request, all_logps [rows, W, n], iter_actions [iterations, rows, W], iter_lengths and
     iter_reward [iterations, rows]. ``err`` as in :func:`aco_tsp`."""
-    for name, t in (("pheromone", pheromone), ("log_heuristic", log_heuristic), ("locs", locs), ("demand", demand)):
-        if t is not None and not t.is_cuda:
-            raise NotImplementedError(f"aco_cvrp runs inside the MI355X kernel (rl4co_aco_cvrp) only: {name} on {t.device}")
-    pheromone = _dev(pheromone, torch.float32, "pheromone")
-    if pheromone.dim() != 3 or pheromone.shape[1] != pheromone.shape[2]:
-        raise ValueError(f"pheromone must be [B, n, n], got {tuple(pheromone.shape)}")
-    b, n, _ = pheromone.shape
-    if not 2 <= n <= 1024:
-        raise NotImplementedError(f"aco_cvrp serves 2..1024 nodes (depot included), got n = {n}")
-    n_ants, iterations = int(n_ants), int(iterations)
-    rows, w = n_ants * b, aco_cvrp_width(n)
-    dev = pheromone.device
-    sample, update = bool(phases & _lib.ACO_SAMPLE), bool(phases & _lib.ACO_UPDATE)
-
-    def shaped(t, dtype, shape, name):
-        if t is None:
-            return None
-        t = _dev(t, dtype, name)
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
-        return t
-
-    log_heuristic = shaped(log_heuristic, torch.float32, (b, n, n), "log_heuristic")
-    locs = shaped(locs, torch.float32, (b, n, 2), "locs")
-    demand = shaped(demand, torch.float32, (b, n - 1), "demand")
-    if vehicle_capacity is not None:
-        vehicle_capacity = shaped(vehicle_capacity.reshape(-1), torch.float32, (b,), "vehicle_capacity")
-    start_nodes = shaped(start_nodes, torch.int64, (iterations, rows), "start_nodes")
-    ln_noise = shaped(ln_noise, torch.float32, (iterations, w, rows, n), "ln_noise")
-    forced_actions = shaped(forced_actions, torch.int64, (rows, w), "forced_actions")
-    if sample:
-        if actions is not None or reward is not None:
-            raise ValueError("actions / reward are outputs of the SAMPLE phase")
-        if demand is None or vehicle_capacity is None:
-            raise ValueError("the SAMPLE phase takes demand [B, n - 1] and vehicle_capacity [B]")
-        actions = torch.zeros((rows, w), dtype=torch.int64, device=dev)
-        reward = torch.zeros(rows, dtype=torch.float32, device=dev)
-        t = w
-    elif actions is None or reward is None:
-        raise ValueError("the UPDATE phase alone takes actions [rows, T] and reward [rows]")
-    else:
-        t = actions.shape[-1]
-        if t < 2:
-            raise ValueError(f"actions must be [rows, T] with T >= 2, got {tuple(actions.shape)}")
-    actions = shaped(actions, torch.int64, (rows, t), "actions")
-    reward = shaped(reward, torch.float32, (rows,), "reward")
-    out = {"actions": actions, "reward": reward}
-    if sample:
-        out["lengths"] = torch.zeros(rows, dtype=torch.int32, device=dev)
-        out["logps"] = torch.zeros((rows, w), dtype=torch.float32, device=dev)
-        if all_logps:
-            out["all_logps"] = torch.zeros((rows, w, n), dtype=torch.float32, device=dev)
-        if record_iterations:
-            out["iter_actions"] = torch.zeros((iterations, rows, w), dtype=torch.int64, device=dev)
-            out["iter_lengths"] = torch.zeros((iterations, rows), dtype=torch.int32, device=dev)
-            out["iter_reward"] = torch.zeros((iterations, rows), dtype=torch.float32, device=dev)
-    if update:
-        if (final_reward is None) != (final_actions is None):
-            raise ValueError("final_reward and final_actions come together")
-        if final_reward is None:
-            if has_best:
-                raise ValueError("has_best needs final_reward and final_actions")
-            final_reward = torch.zeros(b, dtype=torch.float32, device=dev)
-            final_actions = torch.zeros((b, t), dtype=torch.int64, device=dev)
-        if final_iteration is None:
-            final_iteration = torch.full((b,), -1, dtype=torch.int32, device=dev)
-        out["final_reward"] = shaped(final_reward, torch.float32, (b,), "final_reward")
-        out["final_actions"] = shaped(final_actions, torch.int64, (b, t), "final_actions")
-        out["final_iteration"] = shaped(final_iteration, torch.int32, (b,), "final_iteration")
-        out["final_reward_cache"] = torch.zeros((iterations, b), dtype=torch.float32, device=dev)
-    scratch = torch.empty((b, n, n), dtype=torch.float32, device=dev) if n > aco_cvrp_lds_nodes() else None
-    own = err is None
-    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
-    a = _lib.AcoCvrpArgs()
-    a.B, a.N, a.n_ants, a.iterations, a.phases, a.has_best = b, n, n_ants, iterations, int(phases), int(bool(has_best))
-    a.T, a.iteration_base = t, int(iteration_base)
-    a.alpha, a.beta, a.decay, a.Q, a.temperature, a.reserved0 = alpha, beta, decay, Q, temperature, 0
-    a.philox_seed, a.philox_offset = int(philox_seed) & (2**64 - 1), int(philox_offset) & (2**64 - 1)
-    a.philox_seed_dev = _ptr(philox_seed_dev)
-    a.log_heuristic, a.pheromone, a.locs = _ptr(log_heuristic), _ptr(pheromone), _ptr(locs)
-    a.demand, a.vehicle_capacity, a.start_nodes = _ptr(demand), _ptr(vehicle_capacity), _ptr(start_nodes)
-    a.ln_noise, a.forced_actions, a.logits_scratch = _ptr(ln_noise), _ptr(forced_actions), _ptr(scratch)
-    a.actions, a.lengths, a.reward = _ptr(actions), _ptr(out.get("lengths")), _ptr(reward)
-    a.logps, a.all_logps = _ptr(out.get("logps")), _ptr(out.get("all_logps"))
-    a.iter_actions, a.iter_lengths = _ptr(out.get("iter_actions")), _ptr(out.get("iter_lengths"))
-    a.iter_reward = _ptr(out.get("iter_reward"))
-    a.final_reward, a.final_actions = _ptr(out.get("final_reward")), _ptr(out.get("final_actions"))
-    a.final_iteration, a.final_reward_cache = _ptr(out.get("final_iteration")), _ptr(out.get("final_reward_cache"))
-    a.err = _ptr(err)
-    st = _lib.lib().rl4co_aco_cvrp(C.byref(a), _stream())
-    _lib.check(st, "rl4co_aco_cvrp")
-    if own:
-        raise_if_error(err)
-    return out
-
-
-_ACO_PRIZE_ENVS = {"op": _lib.ENV_OP, "pctsp": _lib.ENV_PCTSP, "spctsp": _lib.ENV_PCTSP}  # spctsp: the caller's prize is the stochastic one
-
-
-def aco_prize_lds_nodes(env: str) -> int:
-    """Largest node count (depot included) at which the OP / PCTSP Ant System kernel keeps logits and pheromone in LDS."""
-    return int(_lib.lib().rl4co_aco_prize_lds_nodes(_ACO_PRIZE_ENVS[env]))
+    return _aco_search(ACO_FAMILIES[1], env="cvrp", **locals())
 
 
 def aco_prize(pheromone: Tensor, *, env: str, n_ants: int, phases: int = _lib.ACO_SAMPLE | _lib.ACO_UPDATE,
@@ -1127,107 +1073,27 @@ def aco_prize(pheromone: Tensor, *, env: str, n_ants: int, phases: int = _lib.AC
     ``reward`` [rows]. The reward is the environment's ``get_reward`` on the W-wide row. ``n_workgroups``: 0 for one
     workgroup per instance, else that many workgroups striding over the instances (the same results). The record
     arguments, the returned dict and ``err`` are :func:`aco_cvrp`'s."""
-    if env not in _ACO_PRIZE_ENVS:
-        raise NotImplementedError(f"aco_prize (rl4co_aco_prize) serves {sorted(_ACO_PRIZE_ENVS)}, got env = {env!r}")
-    for name, t in (("pheromone", pheromone), ("log_heuristic", log_heuristic), ("locs", locs), ("prize", prize),
-                    ("penalty", penalty), ("max_length", max_length)):
-        if t is not None and not t.is_cuda:
-            raise NotImplementedError(f"aco_prize runs inside the MI355X kernel (rl4co_aco_prize) only: {name} on {t.device}")
-    pheromone = _dev(pheromone, torch.float32, "pheromone")
-    if pheromone.dim() != 3 or pheromone.shape[1] != pheromone.shape[2]:
-        raise ValueError(f"pheromone must be [B, n, n], got {tuple(pheromone.shape)}")
-    b, n, _ = pheromone.shape
-    if not 2 <= n <= 1024:
-        raise NotImplementedError(f"aco_prize serves 2..1024 nodes (depot included), got n = {n}")
-    n_ants, iterations = int(n_ants), int(iterations)
-    rows, w = n_ants * b, n
-    dev = pheromone.device
-    sample, update = bool(phases & _lib.ACO_SAMPLE), bool(phases & _lib.ACO_UPDATE)
-    is_op = env == "op"
-
-    def shaped(t, dtype, shape, name):
-        if t is None:
-            return None
-        t = _dev(t, dtype, name)
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
-        return t
-
-    log_heuristic = shaped(log_heuristic, torch.float32, (b, n, n), "log_heuristic")
-    locs = shaped(locs, torch.float32, (b, n, 2), "locs")
-    prize = shaped(prize, torch.float32, (b, n), "prize")
-    penalty = shaped(penalty, torch.float32, (b, n), "penalty")
-    max_length = shaped(max_length, torch.float32, (b, n), "max_length")
-    ln_noise = shaped(ln_noise, torch.float32, (iterations, w, rows, n), "ln_noise")
-    forced_actions = shaped(forced_actions, torch.int64, (rows, w), "forced_actions")
-    if sample:
-        if actions is not None or reward is not None:
-            raise ValueError("actions / reward are outputs of the SAMPLE phase")
-        if locs is None or prize is None or (max_length if is_op else penalty) is None:
-            raise ValueError("the SAMPLE phase takes locs [B, n, 2], prize [B, n] and "
-                             + ("max_length [B, n]" if is_op else "penalty [B, n]"))
-        actions = torch.zeros((rows, w), dtype=torch.int64, device=dev)
-        reward = torch.zeros(rows, dtype=torch.float32, device=dev)
-        t = w
-    elif actions is None or reward is None:
-        raise ValueError("the UPDATE phase alone takes actions [rows, T] and reward [rows]")
-    else:
-        t = actions.shape[-1]
-        if t < 2:
-            raise ValueError(f"actions must be [rows, T] with T >= 2, got {tuple(actions.shape)}")
-    actions = shaped(actions, torch.int64, (rows, t), "actions")
-    reward = shaped(reward, torch.float32, (rows,), "reward")
-    out = {"actions": actions, "reward": reward}
-    if sample:
-        out["lengths"] = torch.zeros(rows, dtype=torch.int32, device=dev)
-        out["logps"] = torch.zeros((rows, w), dtype=torch.float32, device=dev)
-        if all_logps:
-            out["all_logps"] = torch.zeros((rows, w, n), dtype=torch.float32, device=dev)
-        if record_iterations:
-            out["iter_actions"] = torch.zeros((iterations, rows, w), dtype=torch.int64, device=dev)
-            out["iter_lengths"] = torch.zeros((iterations, rows), dtype=torch.int32, device=dev)
-            out["iter_reward"] = torch.zeros((iterations, rows), dtype=torch.float32, device=dev)
-    if update:
-        if (final_reward is None) != (final_actions is None):
-            raise ValueError("final_reward and final_actions come together")
-        if final_reward is None:
-            if has_best:
-                raise ValueError("has_best needs final_reward and final_actions")
-            final_reward = torch.zeros(b, dtype=torch.float32, device=dev)
-            final_actions = torch.zeros((b, t), dtype=torch.int64, device=dev)
-        if final_iteration is None:
-            final_iteration = torch.full((b,), -1, dtype=torch.int32, device=dev)
-        out["final_reward"] = shaped(final_reward, torch.float32, (b,), "final_reward")
-        out["final_actions"] = shaped(final_actions, torch.int64, (b, t), "final_actions")
-        out["final_iteration"] = shaped(final_iteration, torch.int32, (b,), "final_iteration")
-        out["final_reward_cache"] = torch.zeros((iterations, b), dtype=torch.float32, device=dev)
-    scratch = torch.empty((b, n, n), dtype=torch.float32, device=dev) if n > aco_prize_lds_nodes(env) else None
-    own = err is None
-    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
-    a = _lib.AcoPrizeArgs()
-    a.B, a.N, a.n_ants, a.iterations, a.phases, a.has_best = b, n, n_ants, iterations, int(phases), int(bool(has_best))
-    a.T, a.iteration_base, a.env, a.n_workgroups = t, int(iteration_base), _ACO_PRIZE_ENVS[env], int(n_workgroups)
-    a.alpha, a.beta, a.decay, a.Q, a.temperature, a.reserved0 = alpha, beta, decay, Q, temperature, 0
-    a.philox_seed, a.philox_offset = int(philox_seed) & (2**64 - 1), int(philox_offset) & (2**64 - 1)
-    a.philox_seed_dev = _ptr(philox_seed_dev)
-    a.log_heuristic, a.pheromone, a.locs = _ptr(log_heuristic), _ptr(pheromone), _ptr(locs)
-    a.prize, a.penalty, a.max_length = _ptr(prize), _ptr(penalty), _ptr(max_length)
-    a.ln_noise, a.forced_actions, a.logits_scratch = _ptr(ln_noise), _ptr(forced_actions), _ptr(scratch)
-    a.actions, a.lengths, a.reward = _ptr(actions), _ptr(out.get("lengths")), _ptr(reward)
-    a.logps, a.all_logps = _ptr(out.get("logps")), _ptr(out.get("all_logps"))
-    a.iter_actions, a.iter_lengths = _ptr(out.get("iter_actions")), _ptr(out.get("iter_lengths"))
-    a.iter_reward = _ptr(out.get("iter_reward"))
-    a.final_reward, a.final_actions = _ptr(out.get("final_reward")), _ptr(out.get("final_actions"))
-    a.final_iteration, a.final_reward_cache = _ptr(out.get("final_iteration")), _ptr(out.get("final_reward_cache"))
-    a.err = _ptr(err)
-    st = _lib.lib().rl4co_aco_prize(C.byref(a), _stream())
-    _lib.check(st, "rl4co_aco_prize")
-    if own:
-        raise_if_error(err)
-    return out
+    return _aco_search(ACO_FAMILIES[2], **locals())
 
 
-_ACO_DEPOT_GRAD_ENVS = {"cvrp": _lib.ENV_CVRP, **_ACO_PRIZE_ENVS}
+class AcoGradFamily(NamedTuple):
+    """One backward kernel of the ants' log-likelihoods. ``needs``: environment -> the instance tensors it takes as
+    ``(keyword, shape of (b, n))``; ``scratch``: the struct's pointer for the table kept outside LDS, and what to allocate
+    for ``parts`` workgroups."""
+    name: str
+    symbol: str
+    args: type
+    envs: dict
+    depot: bool  # node 0 is the depot: the binding takes ``env`` and instance tensors
+    width: Callable[[str, int], int]
+    lds_entries: Callable[[], int]
+    scratch: tuple[str, Callable]  # (struct field, (parts, n_ants, n, device) -> Tensor)
+    needs: dict
+
+
+def aco_grad_lds_entries() -> int:
+    """Largest ``n_ants * N`` whose inverse-permutation table the log-likelihood backward keeps in LDS (a host query)."""
+    return int(_lib.lib().rl4co_aco_tsp_grad_lds_entries())
 
 
 def aco_depot_grad_lds_entries() -> int:
@@ -1235,9 +1101,111 @@ def aco_depot_grad_lds_entries() -> int:
     return int(_lib.lib().rl4co_aco_depot_grad_lds_entries())
 
 
-def aco_depot_width(env: str, n: int) -> int:
-    """The width of a sampled row: :func:`aco_cvrp_width` for cvrp, ``n`` for op / pctsp / spctsp."""
-    return aco_cvrp_width(n) if env == "cvrp" else n
+def aco_grad_row_split(b: int, n: int, cus: int) -> int:
+    """Workgroups per instance of :func:`aco_tsp_logp_grad` when the caller names none: about two workgroups per CU, at
+    least sixteen heatmap rows per workgroup (each repeats the table build). An estimate, not a measured optimum."""
+    return max(1, min(n // 16, (2 * cus) // b))
+
+
+_PRIZE_NEEDS = (("prize", lambda b, n: (b, n)),)
+ACO_GRAD_FAMILIES = (
+    AcoGradFamily("aco_tsp_logp_grad", "rl4co_aco_tsp_logp_grad", _lib.AcoTspGradArgs, {"tsp": _lib.ENV_TSP},
+                  False, lambda env, n: n, aco_grad_lds_entries,
+                  ("pos_scratch",
+                   lambda parts, ants, n, dev: torch.empty((parts, ants, n), dtype=torch.int16, device=dev)), {"tsp": ()}),
+    AcoGradFamily("aco_depot_logp_grad", "rl4co_aco_depot_logp_grad", _lib.AcoDepotGradArgs, _ACO_DEPOT_GRAD_ENVS,
+                  True, aco_depot_width, aco_depot_grad_lds_entries,
+                  ("scratch", lambda parts, ants, n, dev: torch.empty(
+                      parts * int(_lib.lib().rl4co_aco_depot_grad_scratch_bytes(ants, n)), dtype=torch.uint8, device=dev)),
+                  {"cvrp": (("demand", lambda b, n: (b, n - 1)), ("vehicle_capacity", lambda b, n: (b,))),
+                   "op": (("locs", lambda b, n: (b, n, 2)), ("max_length", lambda b, n: (b, n))),
+                   "pctsp": _PRIZE_NEEDS, "spctsp": _PRIZE_NEEDS}),
+)
+
+
+def aco_grad_family(env: str) -> AcoGradFamily:
+    return next(fam for fam in ACO_GRAD_FAMILIES if env in fam.envs)
+
+
+def aco_logp_grad(env: str, heatmap: Tensor, actions: Tensor, grad_ll: Tensor, **kw) -> Tensor:
+    """:func:`aco_tsp_logp_grad` or :func:`aco_depot_logp_grad`, whichever serves ``env``."""
+    fam = aco_grad_family(env)
+    return globals()[fam.name](heatmap, actions, grad_ll, **kw, **({"env": env} if fam.depot else {}))
+
+
+def _aco_logp_grad(fam: AcoGradFamily, heatmap, actions, grad_ll, *, env, grad_steps, temperature, row_split, in_scratch, err,
+                   multistart=False, **given) -> Tensor:
+    """The one body of the two gradient bindings; ``given``: the instance tensors by keyword."""
+    who, depot = fam.name, fam.depot
+    d, wd = ("n", "W") if depot else ("N", "N")
+    if env not in fam.envs:
+        raise NotImplementedError(f"{who} ({fam.symbol}) serves {sorted(fam.envs)}, got env = {env!r}")
+    for name, t, dtype in (("heatmap", heatmap, torch.float32), ("actions", actions, torch.int64),
+                           ("grad_ll", grad_ll, torch.float32), ("grad_steps", grad_steps, torch.float32),
+                           *((name, t, torch.float32) for name, t in given.items())):
+        if t is not None and t.dtype != dtype:
+            raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    if heatmap.dim() != 3 or heatmap.shape[1] != heatmap.shape[2]:
+        raise ValueError(f"heatmap must be [B, {d}, {d}], got {tuple(heatmap.shape)}")
+    b, n, _ = heatmap.shape
+    if not 2 <= n <= 1024:
+        raise NotImplementedError(f"{who} serves 2..1024 nodes{' (depot included)' if depot else ''}, got {d} = {n}")
+    w = fam.width(env, n)
+    if actions.dim() != 2 or actions.shape[1] != w or actions.shape[0] == 0 or actions.shape[0] % b:
+        raise ValueError(f"actions must be [n_ants * B, {wd}] = [k * {b}, {w}], got {tuple(actions.shape)}")
+    rows = actions.shape[0]
+    n_ants = rows // b
+    if tuple(grad_ll.shape) != (rows,):
+        raise ValueError(f"grad_ll must be {(rows,)}, got {tuple(grad_ll.shape)}")
+    if grad_steps is not None and tuple(grad_steps.shape) != (rows, w):
+        raise ValueError(f"grad_steps must be {(rows, w)}, got {tuple(grad_steps.shape)}")
+    if given.get("vehicle_capacity") is not None:
+        given["vehicle_capacity"] = given["vehicle_capacity"].reshape(-1)
+    needs = {name: given[name] for name, _ in fam.needs[env]}
+    for name, shape in fam.needs[env]:
+        if needs[name] is None or tuple(needs[name].shape) != shape(b, n):
+            raise ValueError(f"env {env!r} takes {name} {shape(b, n)}, got "
+                             f"{None if needs[name] is None else tuple(needs[name].shape)}")
+    if multistart and env != "cvrp":
+        raise NotImplementedError(f"multistart is served for cvrp only, got env = {env!r}")
+    if not temperature > 0:
+        raise ValueError(f"temperature must be positive, got {temperature}")
+    if row_split is not None and not 1 <= int(row_split) <= n:
+        raise ValueError(f"row_split must be in [1, {d} = {n}], got {row_split}")
+    for name, t in (("heatmap", heatmap), ("actions", actions), ("grad_ll", grad_ll), ("grad_steps", grad_steps), *needs.items()):
+        if t is not None:
+            _dev(t, None, name)
+    dev = heatmap.device
+    if row_split is None:
+        row_split = aco_grad_row_split(b, n, torch.cuda.get_device_properties(dev).multi_processor_count)
+    fits = n_ants * n <= fam.lds_entries()
+    field, alloc = fam.scratch
+    if in_scratch is None:
+        in_scratch = not fits
+    elif not in_scratch and not fits:
+        raise ValueError(f"n_ants * {d} = {n_ants * n} is above the LDS table's {fam.lds_entries()} entries")
+    grad = torch.empty((b, n, n), dtype=torch.float32, device=dev)
+    values = dict(needs, env=fam.envs[env], B=b, N=n, n_ants=n_ants, row_split=int(row_split), multistart=int(bool(multistart)),
+                  temperature=float(temperature), reserved0=0, heatmap=heatmap, actions=actions, grad_ll=grad_ll,
+                  grad_steps=grad_steps, grad_heatmap=grad)
+    values[field] = alloc(b * int(row_split), n_ants, n, dev) if in_scratch else None
+    _aco_launch(fam.symbol, fam.args(), values, err, dev)
+    return grad
+
+
+def aco_tsp_logp_grad(heatmap: Tensor, actions: Tensor, grad_ll: Tensor, *, grad_steps: Tensor | None = None,
+                      temperature: float = 1.0, row_split: int | None = None, pos_in_scratch: bool | None = None,
+                      err: Tensor | None = None) -> Tensor:
+    """The gradient of the ants' log-likelihoods with respect to the heatmap in one launch (rl4co_aco_tsp_logp_grad; the
+    header states the arithmetic): ``heatmap`` [B, N, N] fp32 (the logits the forward sampled from, not divided by the
+    temperature), ``actions`` [rows, N] int64 with rows = n_ants * B ant-major, ``grad_ll`` [rows] fp32 and optionally
+    ``grad_steps`` [rows, N] fp32 (column 0 ignored) -> ``grad_heatmap`` [B, N, N] fp32, every word written.
+
+    ``row_split``: workgroups per instance (None: :func:`aco_grad_row_split`); any value gives the same bits.
+    ``pos_in_scratch``: keep the inverse-permutation table in a global scratch instead of LDS (None: only above
+    :func:`aco_grad_lds_entries`). ``err`` as in :func:`aco_tsp`."""
+    return _aco_logp_grad(ACO_GRAD_FAMILIES[0], heatmap, actions, grad_ll, env="tsp", grad_steps=grad_steps,
+                          temperature=temperature, row_split=row_split, in_scratch=pos_in_scratch, err=err)
 
 
 def aco_depot_logp_grad(heatmap: Tensor, actions: Tensor, grad_ll: Tensor, *, env: str, grad_steps: Tensor | None = None,
@@ -1257,76 +1225,10 @@ def aco_depot_logp_grad(heatmap: Tensor, actions: Tensor, grad_ll: Tensor, *, en
     customer and contributes nothing. ``row_split``: workgroups per instance (None: :func:`aco_grad_row_split`); any value
     gives the same bits. ``table_in_scratch``: keep the replay table in a global scratch instead of LDS (None: only above
     :func:`aco_depot_grad_lds_entries`); the same bits. ``err`` as in :func:`aco_tsp`."""
-    if env not in _ACO_DEPOT_GRAD_ENVS:
-        raise NotImplementedError(f"aco_depot_logp_grad (rl4co_aco_depot_logp_grad) serves {sorted(_ACO_DEPOT_GRAD_ENVS)}, got "
-                                  f"env = {env!r}")
-    for name, t, dtype in (("heatmap", heatmap, torch.float32), ("actions", actions, torch.int64),
-                           ("grad_ll", grad_ll, torch.float32), ("grad_steps", grad_steps, torch.float32),
-                           ("locs", locs, torch.float32), ("demand", demand, torch.float32),
-                           ("vehicle_capacity", vehicle_capacity, torch.float32), ("prize", prize, torch.float32),
-                           ("max_length", max_length, torch.float32)):
-        if t is not None and t.dtype != dtype:
-            raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
-    if heatmap.dim() != 3 or heatmap.shape[1] != heatmap.shape[2]:
-        raise ValueError(f"heatmap must be [B, n, n], got {tuple(heatmap.shape)}")
-    b, n, _ = heatmap.shape
-    if not 2 <= n <= 1024:
-        raise NotImplementedError(f"aco_depot_logp_grad serves 2..1024 nodes (depot included), got n = {n}")
-    w = aco_depot_width(env, n)
-    if actions.dim() != 2 or actions.shape[1] != w or actions.shape[0] == 0 or actions.shape[0] % b:
-        raise ValueError(f"actions must be [n_ants * B, W] = [k * {b}, {w}], got {tuple(actions.shape)}")
-    rows = actions.shape[0]
-    n_ants = rows // b
-    if tuple(grad_ll.shape) != (rows,):
-        raise ValueError(f"grad_ll must be {(rows,)}, got {tuple(grad_ll.shape)}")
-    if grad_steps is not None and tuple(grad_steps.shape) != (rows, w):
-        raise ValueError(f"grad_steps must be {(rows, w)}, got {tuple(grad_steps.shape)}")
-    if vehicle_capacity is not None:
-        vehicle_capacity = vehicle_capacity.reshape(-1)
-    needs = {"cvrp": (("demand", demand, (b, n - 1)), ("vehicle_capacity", vehicle_capacity, (b,))),
-             "op": (("locs", locs, (b, n, 2)), ("max_length", max_length, (b, n)))}.get(env, (("prize", prize, (b, n)),))
-    for name, t, shape in needs:
-        if t is None or tuple(t.shape) != shape:
-            raise ValueError(f"env {env!r} takes {name} {shape}, got {None if t is None else tuple(t.shape)}")
-    if multistart and env != "cvrp":
-        raise NotImplementedError(f"multistart is served for cvrp only, got env = {env!r}")
-    if not temperature > 0:
-        raise ValueError(f"temperature must be positive, got {temperature}")
-    if row_split is not None and not 1 <= int(row_split) <= n:
-        raise ValueError(f"row_split must be in [1, n = {n}], got {row_split}")
-    _dev(heatmap, None, "heatmap"), _dev(actions, None, "actions"), _dev(grad_ll, None, "grad_ll")
-    if grad_steps is not None:
-        _dev(grad_steps, None, "grad_steps")
-    for name, t, _ in needs:
-        _dev(t, None, name)
-    given = {name: t for name, t, _ in needs}
-    dev = heatmap.device
-    if row_split is None:
-        row_split = aco_grad_row_split(b, n, torch.cuda.get_device_properties(dev).multi_processor_count)
-    fits = n_ants * n <= aco_depot_grad_lds_entries()
-    if table_in_scratch is None:
-        table_in_scratch = not fits
-    elif not table_in_scratch and not fits:
-        raise ValueError(f"n_ants * n = {n_ants * n} is above the LDS table's {aco_depot_grad_lds_entries()} entries")
-    scratch = None
-    if table_in_scratch:
-        per_wg = int(_lib.lib().rl4co_aco_depot_grad_scratch_bytes(n_ants, n))
-        scratch = torch.empty(b * int(row_split) * per_wg, dtype=torch.uint8, device=dev)
-    grad = torch.empty((b, n, n), dtype=torch.float32, device=dev)
-    own = err is None
-    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
-    a = _lib.AcoDepotGradArgs()
-    a.env, a.B, a.N, a.n_ants, a.row_split = _ACO_DEPOT_GRAD_ENVS[env], b, n, n_ants, int(row_split)
-    a.multistart, a.temperature, a.reserved0 = int(bool(multistart)), float(temperature), 0
-    a.heatmap, a.actions, a.grad_ll, a.grad_steps = _ptr(heatmap), _ptr(actions), _ptr(grad_ll), _ptr(grad_steps)
-    a.locs, a.demand, a.vehicle_capacity = _ptr(given.get("locs")), _ptr(given.get("demand")), _ptr(given.get("vehicle_capacity"))
-    a.prize, a.max_length = _ptr(given.get("prize")), _ptr(given.get("max_length"))
-    a.scratch, a.grad_heatmap, a.err = _ptr(scratch), _ptr(grad), _ptr(err)
-    st = _lib.lib().rl4co_aco_depot_logp_grad(C.byref(a), _stream())
-    _lib.check(st, "rl4co_aco_depot_logp_grad")
-    if own:
-        raise_if_error(err)
-    return grad
+    return _aco_logp_grad(ACO_GRAD_FAMILIES[1], heatmap, actions, grad_ll, env=env, grad_steps=grad_steps, locs=locs,
+                          demand=demand, vehicle_capacity=vehicle_capacity, prize=prize, max_length=max_length,
+                          multistart=multistart, temperature=temperature, row_split=row_split, in_scratch=table_in_scratch,
+                          err=err)
 
 
 def decoding_filter(top_k, top_p, n: int) -> tuple[int, float]:

@@ -3,8 +3,9 @@
 
     python tools/asm_identity.py emit OUT_DIR [TREE]      # TREE: a checkout of this repository (default: this one)
     python tools/asm_identity.py compare DIR_A DIR_B      # one line per file; exit status 1 if any file differs
+    ... --files a.hip b.hip                               # either command: these files of csrc/ (default: FILES)
 
-``emit`` compiles each file of FILES device-only to assembly with ``build.COMPILE_FLAGS`` and the include path of
+``emit`` compiles each file device-only to assembly with ``build.COMPILE_FLAGS`` and the include path of
 ``build._compile``. ``compare`` splits each assembly text by kernel symbol (every ``.amdhsa_kernel NAME``), takes a
 kernel's text from its label ``NAME:`` to the ``.end_amdhsa_kernel`` of its descriptor (the ``.amdhsa_*`` resource lines
 included) and asks that both sides define the same symbols with byte-identical text. The order of the kernels in the file
@@ -25,12 +26,12 @@ FILES = ["am_decode.hip", "am_decode_ms.hip", "am_decode_ms_f16.hip", "am_decode
          "am_teacher_mma.hip", "am_teacher_mma_f16.hip"]
 
 
-def emit(out: Path, tree: Path) -> None:
+def emit(out: Path, tree: Path, files=FILES) -> None:
     out.mkdir(parents=True, exist_ok=True)
     procs = [(name, subprocess.Popen(
         [B._hipcc(), *B.COMPILE_FLAGS, f"-I{tree / 'include'}", "--cuda-device-only", "-S",
          str(tree / "rl4co_amd" / "csrc" / name), "-o", str(out / (name + ".s"))], stderr=subprocess.PIPE, text=True))
-        for name in FILES]
+        for name in files]
     for name, p in procs:
         err = p.communicate()[1]
         if p.returncode != 0:
@@ -52,9 +53,9 @@ def kernels(text: str) -> dict:
     return out
 
 
-def compare(a: Path, b: Path) -> int:
+def compare(a: Path, b: Path, files=FILES) -> int:
     bad = 0
-    for name in FILES:
+    for name in files:
         ka, kb = kernels((a / (name + ".s")).read_text()), kernels((b / (name + ".s")).read_text())
         only = sorted(set(ka) ^ set(kb))
         differ = sorted(k for k in set(ka) & set(kb) if ka[k] != kb[k])
@@ -69,9 +70,14 @@ def compare(a: Path, b: Path) -> int:
 
 
 if __name__ == "__main__":
-    if len(sys.argv) >= 3 and sys.argv[1] == "emit":
-        emit(Path(sys.argv[2]), Path(sys.argv[3]).resolve() if len(sys.argv) > 3 else ROOT)
-    elif len(sys.argv) == 4 and sys.argv[1] == "compare":
-        sys.exit(compare(Path(sys.argv[2]), Path(sys.argv[3])))
+    argv, files = sys.argv[1:], FILES
+    if "--files" in argv:
+        argv, files = argv[:argv.index("--files")], argv[argv.index("--files") + 1:]
+    if not files:
+        raise SystemExit(__doc__)
+    if len(argv) in (2, 3) and argv[0] == "emit":
+        emit(Path(argv[1]), Path(argv[2]).resolve() if len(argv) > 2 else ROOT, files)
+    elif len(argv) == 3 and argv[0] == "compare":
+        sys.exit(compare(Path(argv[1]), Path(argv[2]), files))
     else:
         raise SystemExit(__doc__)
