@@ -952,7 +952,7 @@ int rl4co_tsp_nls_lds_nodes(void);
  *   heatmap[b][u][v] = log(h + small_value) at the K neighbours of u, fill_value everywhere else (diagonal included).
  * silu(y) = y / (1 + exp(-y)); the batch norms are eval-mode, folded by the host into a per-channel scale and shift
  * (y * scale + shift). The 64-long dot products run on v_mfma_f32_16x16x4_f32 (the hardware's summation order).
- * Three tiers by where the state lives (nargnn.hip header): up to rl4co_nargnn_lds_nodes(K) nodes the edge state and the
+ * Three tiers by where the state lives (nargnn_shared.h header): up to rl4co_nargnn_lds_nodes(K) nodes the edge state and the
  * two gathered node planes stay in LDS; above, the edge state lives in `scratch`; above 300 nodes every plane does.
  * `scratch` holds n_workgroups * rl4co_nargnn_scratch_bytes(N, K) bytes, 16-byte aligned.
  * A neighbour index outside [0, N) sets RL4CO_EBIT_TOUR_INDEX; that instance's outputs are left untouched.
@@ -990,7 +990,7 @@ typedef struct rl4co_nargnn_args {
 } rl4co_nargnn_args;
 
 int rl4co_nargnn_heatmap(const rl4co_nargnn_args* args, void* stream);
-/* Largest N at which rl4co_nargnn_heatmap keeps the edge state of K out-edges per node in LDS (nargnn.hip header). */
+/* Largest N at which rl4co_nargnn_heatmap keeps the edge state of K out-edges per node in LDS (nargnn_shared.h header). */
 int rl4co_nargnn_lds_nodes(int K);
 /* Bytes of `scratch` one workgroup needs at this shape (0 < result; the tier is the kernel's own choice). */
 int64_t rl4co_nargnn_scratch_bytes(int N, int K);
@@ -1050,7 +1050,7 @@ typedef struct rl4co_nargnn_depot_args {
 } rl4co_nargnn_depot_args;
 
 int rl4co_nargnn_depot_heatmap(const rl4co_nargnn_depot_args* args, void* stream);
-/* Largest N at which rl4co_nargnn_depot_heatmap keeps the (N - 1)(K + 2) edge rows in LDS (nargnn_depot.hip header). */
+/* Largest N at which rl4co_nargnn_depot_heatmap keeps the (N - 1)(K + 2) edge rows in LDS (nargnn_shared.h header). */
 int rl4co_nargnn_depot_lds_nodes(int K);
 /* Bytes of `scratch` one workgroup needs at this shape (0 outside the supported range). */
 int64_t rl4co_nargnn_depot_scratch_bytes(int N, int K);

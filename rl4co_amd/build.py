@@ -28,7 +28,7 @@ SOURCES = ["api.hip", "entry16.hip", "env_step.hip", "tour_length.hip", "tsp_two
            "am_train_ops_f16.hip", "am_train_attn_f16.hip", "am_attn_flash_f16.hip", "am_cross_attn_f16.hip",
            "am_decode_ms_f16.hip", "am_teacher_mma_f16.hip"]
 HEADERS = ["common.h", "rl4co_math.h", "topkp.h", "elem16.h", "enc_f32.h", "decode_wave.h", "env_table.h", "tsp_two_opt_search.h",
-           "lds_tour_reward.h", "ant_system.h", "ant_rules.h", "ant_grad.h", "nargnn_tile.h"]
+           "lds_tour_reward.h", "ant_system.h", "ant_rules.h", "ant_grad.h", "nargnn_shared.h"]
 # *_f16.hip wrappers include their bf16 namesake: its text is part of their hash
 INCLUDED = {name: [name.replace("_f16.hip", ".hip")] for name in SOURCES if name.endswith("_f16.hip")}
 COMPILE_FLAGS = [

@@ -1,7 +1,7 @@
 // nargnn_depot.hip — DeepACO's heatmap encoder for the depot graphs of CVRP, OP and PCTSP (the reference's NARGNNEncoder in
 // inference with VRP / OP / PCTSPInitEmbedding and CVRPEdgeEmbedding, env_embeddings/edge.py:119-176) as one launch for
-// gfx950, fp32 throughout. The scheme is nargnn.hip's: one workgroup of eight waves per INSTANCE, persistent over the
-// layers, grid-stride over the instances, the 64-long dot products on nargnn_tile.h's MFMA tiles.
+// gfx950, fp32 throughout. The scheme, the MFMA tiles, the tiers and their LDS budget are nargnn_shared.h's, shared with
+// nargnn.hip; what follows is the depot graph's own.
 //
 // The graph is not regular. Node 0 is the depot, nodes 1 .. C = N - 1 the customers. Edge rows, R = C (K + 2) of them:
 //   customer u owns the K + 1 contiguous rows (u - 1)(K + 1) ..: its K customer neighbours neighbors[u - 1][0 .. K-1], then
@@ -31,47 +31,42 @@
 //   receives C stores, column 0 one from every customer's depot row, and no entry is written by two rows as long as a
 //   neighbour list holds no 0 and no repeat.
 //
-// Where the state lives (rows of kRS = 68 floats):
-//   tier 0  N <= rl4co_nargnn_depot_lds_nodes(K): x2, x4 and the edge state in LDS; x, x1, x3, part in `scratch`
-//   tier 1  N <= 300: x2, x4 in LDS; the edge state and x, x1, x3, part in `scratch`
-//   tier 2  up to 1024 nodes: everything in `scratch`
-// `scratch` is sized by the grid, not by B; a workgroup's slice is its own, so workgroup barriers order it.
-// LDS budget (bytes, all dynamic; the launcher checks that the compiler added no static LDS beyond kStaticLds):
-//   head 64 (the bad-index flag) + 272 (2 N + C (K + 2)) in tier 0 | 272 * 2 N in tier 1 | nothing more in tier 2.
-//   tier 0 at K = 10: N <= 43; at K = 20: N <= 25.
-// scratch rows per workgroup: 3 N + 8 (part) + C (K + 2) in tiers 1 and 2 + 2 N in tier 2.
+// The tiers are nargnn_shared.h's with R edge rows and eight extra scratch rows (`part`, behind x, x1, x3):
+//   tier 0 (N <= rl4co_nargnn_depot_lds_nodes(K)) at K = 10: N <= 43; at K = 20: N <= 25.
 // A neighbour index outside [1, N) raises RL4CO_EBIT_TOUR_INDEX and the instance is left untouched: the lists are checked
 // before anything is read through them. 0 is refused as well: it would repeat the depot edge, and two rows would write one
 // heatmap entry.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
-#include "nargnn_tile.h"
+#include "nargnn_shared.h"
 
 namespace {
 
-using namespace rl4co::nargnn;  // kD, kRS, f32x4, sigmoidf, siluf, load_wfrags, gemm_tile, node_gemm
-
-constexpr int kThreads = 512;
-constexpr int kWaves = kThreads / 64;
-constexpr int kCuLds = 160 * 1024;
-constexpr int kStaticLds = 64;
-constexpr int kHeadBytes = 64;
-constexpr int kNodeLdsMax = 300;  // tier 1: 64 + 2 * 300 * 272 + 64 <= 160 KiB
+using namespace rl4co::nargnn;
 
 __host__ __device__ constexpr int64_t edge_rows(int N, int K) { return (int64_t)(N - 1) * (K + 2); }
-__host__ __device__ constexpr int64_t lds_bytes(int tier, int N, int K) {
-  const int64_t rows = tier == 0 ? 2 * (int64_t)N + edge_rows(N, K) : (tier == 1 ? 2 * (int64_t)N : 0);
-  return kHeadBytes + rows * kRS * 4;
-}
-__host__ __device__ constexpr int64_t scratch_floats(int tier, int N, int K) {
-  const int64_t rows = 3 * (int64_t)N + kWaves + (tier >= 1 ? edge_rows(N, K) : 0) + (tier == 2 ? 2 * (int64_t)N : 0);
-  return rows * kRS;
-}
-inline int tier_of(int N, int K) {
-  if (lds_bytes(0, N, K) + kStaticLds <= kCuLds) return 0;
-  return N <= kNodeLdsMax ? 1 : 2;
-}
+
+// The edge rows: customer ci's K + 1 rows (k == K: its depot edge) below D0, the depot's row to customer ci + 1 from D0 on.
+struct Rows {
+  const int32_t* nbr;
+  int D0, K1, K;
+  // is row e a customer's? then (ci, k) are its customer and place, otherwise ci is the customer the depot's row goes to
+  __device__ __forceinline__ bool customer_row(int e, int& ci, int& k) const {
+    if (e < D0) {
+      ci = e / K1, k = e - ci * K1;
+      return true;
+    }
+    ci = e - D0;
+    return false;
+  }
+  // row e is (u -> v)
+  __device__ __forceinline__ Edge operator()(int e) const {
+    int ci, k;
+    if (customer_row(e, ci, k)) return {ci + 1, k < K ? nbr[ci * K + k] : 0};
+    return {0, ci + 1};
+  }
+};
 
 template <int TIER>
 __global__ void __launch_bounds__(kThreads) nargnn_depot_kernel(const rl4co_nargnn_depot_args a) {
@@ -85,26 +80,8 @@ __global__ void __launch_bounds__(kThreads) nargnn_depot_kernel(const rl4co_narg
   const int N = a.N, K = a.K, F = a.F, C = N - 1, K1 = K + 1, CK = C * K;
   const int D0 = C * K1, R = D0 + C;  // the depot's first row, all rows
 
-  float* gs = a.scratch + (int64_t)blockIdx.x * scratch_floats(TIER, N, K);
-  float* X = gs;
-  float* X1 = gs + N * kRS;
-  float* X3 = gs + 2 * N * kRS;
-  float* PART = gs + 3 * N * kRS;
-  float* after = PART + kWaves * kRS;
-  float *X2, *X4, *E;
-  if constexpr (TIER == 0) {
-    X2 = lds;
-    X4 = lds + N * kRS;
-    E = lds + 2 * N * kRS;
-  } else if constexpr (TIER == 1) {
-    X2 = lds;
-    X4 = lds + N * kRS;
-    E = after;
-  } else {
-    E = after;
-    X2 = E + (int64_t)R * kRS;
-    X4 = X2 + N * kRS;
-  }
+  const Planes p = planes<TIER>(a.scratch + (int64_t)blockIdx.x * scratch_floats(TIER, N, edge_rows(N, K), kWaves), lds, N, R, kWaves);
+  float *X = p.X, *X1 = p.X1, *X3 = p.X3, *PART = p.extra, *X2 = p.X2, *X4 = p.X4, *E = p.E;
 
   // the wave's customers (and depot rows) in B1 and its edge rows everywhere else, for every layer
   const int cpw = (C + kWaves - 1) / kWaves;
@@ -114,20 +91,8 @@ __global__ void __launch_bounds__(kThreads) nargnn_depot_kernel(const rl4co_narg
 
   for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
     const int32_t* nbr = a.neighbors + (int64_t)b * CK;
-
-    // ---- the neighbour lists: range check before anything is read through them ------------------------------------------
-    if (tid == 0) *bad_flag = 0u;
-    __syncthreads();
-    bool bad = false;
-    for (int e = tid; e < CK; e += kThreads) {
-      const int v = nbr[e];
-      bad |= v < 1 || v >= N;
-    }
-    if (bad) *bad_flag = 1u;
-    __syncthreads();
-    const bool refused = *bad_flag != 0u;  // (uniform: one LDS word)
-    __syncthreads();                       // the word is reset at the top of the next instance
-    if (refused) {
+    const Rows uv{nbr, D0, K1, K};
+    if (neighbors_refused(bad_flag, nbr, CK, 1, N, tid)) {  // 0 would repeat the depot edge
       if (tid == 0) atomicOr(a.err, RL4CO_EBIT_TOUR_INDEX);
       continue;
     }
@@ -158,13 +123,8 @@ __global__ void __launch_bounds__(kThreads) nargnn_depot_kernel(const rl4co_narg
       const float* cost = a.edge_cost + (int64_t)b * CK;
       const float* dcost = a.depot_cost + (int64_t)b * C;
       for (int e = e0; e < e1; ++e) {
-        float d;
-        if (e < D0) {
-          const int ci = e / K1, k = e - ci * K1;
-          d = k < K ? cost[ci * K + k] : dcost[ci];
-        } else {
-          d = dcost[e - D0];
-        }
+        int ci, k;
+        const float d = uv.customer_row(e, ci, k) && k < K ? cost[ci * K + k] : dcost[ci];
         E[e * kRS + lane] = siluf(d * we + be);
       }
     }
@@ -175,16 +135,7 @@ __global__ void __launch_bounds__(kThreads) nargnn_depot_kernel(const rl4co_narg
       const float* BN = a.bn + (int64_t)l * 4 * kD;
       __syncthreads();  // 1: x of every node is this layer's; the layer before has finished with x1 .. x4 and part
 
-      // ---- A. x1 .. x4 of every node ---------------------------------------------------------------------------------
-      {
-        const int m = w & 3, tile0 = w >> 2;  // (wave-uniform)
-        const float* Wm = LW + m * kD * kD;
-        const float* bm = LB + m * kD;
-        if (m == 0) node_gemm(X1, X, Wm, bm, N, tile0, lane);
-        else if (m == 1) node_gemm(X2, X, Wm, bm, N, tile0, lane);
-        else if (m == 2) node_gemm(X3, X, Wm, bm, N, tile0, lane);
-        else node_gemm(X4, X, Wm, bm, N, tile0, lane);
-      }
+      node_gemms(X1, X2, X3, X4, X, LW, LB, N, w, lane);
       __syncthreads();  // 2
 
       // ---- B1. the node sums: the wave's customers, then its share of the depot's rows (lane = channel) --------------------
@@ -216,69 +167,9 @@ __global__ void __launch_bounds__(kThreads) nargnn_depot_kernel(const rl4co_narg
         const float y = (X1[lane] + s / (float)C) * vsc + vsh;
         X[lane] += siluf(y);
       }
-      {
-        f32x4 wf[4][4];
-        load_wfrags(wf, LW + 4 * kD * kD, lane);
-        float bcol[4], sc[4], sh[4];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-          bcol[ct] = LB[4 * kD + 16 * ct + c];
-          sc[ct] = BN[2 * kD + 16 * ct + c];
-          sh[ct] = BN[3 * kD + 16 * ct + c];
-        }
-        for (int t0 = e0; t0 < e1; t0 += 16) {
-          const int row = min(t0 + c, e1 - 1);  // rows past the wave's last repeat it and are not stored
-          f32x4 acc[4];
-          gemm_tile(acc, wf, E + row * kRS + 4 * g);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int e = t0 + 4 * g + r;
-            if (e < e1) {
-              int u, v;
-              if (e < D0) {
-                const int ci = e / K1, k = e - ci * K1;
-                u = ci + 1;
-                v = k < K ? nbr[ci * K + k] : 0;
-              } else {
-                u = 0;
-                v = e - D0 + 1;
-              }
-#pragma unroll
-              for (int ct = 0; ct < 4; ++ct) {
-                const int col = 16 * ct + c;
-                float y = ((acc[ct][r] + bcol[ct]) + X3[u * kRS + col]) + X4[v * kRS + col];
-                y = y * sc[ct] + sh[ct];
-                E[e * kRS + col] += siluf(y);
-              }
-            }
-          }
-        }
-      }
+      edge_update(E, X3, X4, LW, LB, BN, e0, e1, lane, c, g, uv);
     }
-
-    // ---- the heatmap MLP on the own rows: layer by layer in place, wave-local ----------------------------------------------
-    for (int h = 0; h + 1 < a.H; ++h) {
-      rl4co::lds_barrier_wave();  // rows written in one lane layout are read in another, by this wave only
-      f32x4 wf[4][4];
-      load_wfrags(wf, a.mlp_w + (int64_t)h * kD * kD, lane);
-      float bcol[4];
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) bcol[ct] = a.mlp_b ? a.mlp_b[h * kD + 16 * ct + c] : 0.0f;
-      for (int t0 = e0; t0 < e1; t0 += 16) {
-        const int row = min(t0 + c, e1 - 1);
-        f32x4 acc[4];
-        gemm_tile(acc, wf, E + row * kRS + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int e = t0 + 4 * g + r;
-          if (e < e1) {
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) E[e * kRS + 16 * ct + c] = siluf(acc[ct][r] + bcol[ct]);
-          }
-        }
-      }
-    }
-    rl4co::lds_barrier_wave();
+    mlp_rows(E, a.mlp_w, a.mlp_b, a.H, e0, e1, lane, c, g);
 
     // ---- the fill, then the output layer and the scatter of the own rows -------------------------------------------------------
     {
@@ -286,84 +177,33 @@ __global__ void __launch_bounds__(kThreads) nargnn_depot_kernel(const rl4co_narg
       for (int j = tid; j < N * N; j += kThreads) hm[j] = a.fill_value;
       // a heatmap row is filled by many waves and scattered into by others: the barrier waits for every fill store
       __syncthreads();
-      const float wo = a.out_w[lane];
-      const float bo = a.out_b ? a.out_b[0] : 0.0f;
-      for (int e = e0; e < e1; ++e) {
-        const float p = rl4co::bfly_sum<1, 64>(E[e * kRS + lane] * wo);
-        if (lane == 0) {
-          int u, v;
-          if (e < D0) {
-            const int ci = e / K1, k = e - ci * K1;
-            u = ci + 1;
-            v = k < K ? nbr[ci * K + k] : 0;
-          } else {
-            u = 0;
-            v = e - D0 + 1;
-          }
-          hm[u * N + v] = logf(sigmoidf(p + bo) + a.small_value);
-        }
-      }
+      output_rows(hm, E, a.out_w, a.out_b, a.small_value, N, e0, e1, lane, uv);
     }
   }
 }
 
-template <int TIER>
-int launch(const rl4co_nargnn_depot_args& a, hipStream_t stream) {
-  const int lds = (int)lds_bytes(TIER, a.N, a.K);
-  hipFuncAttributes fa;
-  RL4CO_HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(nargnn_depot_kernel<TIER>)));
-  RL4CO_REQUIRE((int64_t)fa.sharedSizeBytes <= kStaticLds);  // the budget of rl4co_nargnn_depot_lds_nodes holds
-  if (lds > 64 * 1024) {
-    RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(nargnn_depot_kernel<TIER>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  }
-  hipLaunchKernelGGL((nargnn_depot_kernel<TIER>), dim3(a.n_workgroups), dim3(kThreads), lds, stream, a);
-  RL4CO_HIP_TRY(hipGetLastError());
-  return RL4CO_OK;
-}
-
 }  // namespace
 
-extern "C" int rl4co_nargnn_depot_lds_nodes(int K) {
-  if (K < 1) return 0;
-  int n = 1024;
-  while (n > 0 && lds_bytes(0, n, K) + kStaticLds > kCuLds) --n;
-  return n;
-}
+extern "C" int rl4co_nargnn_depot_lds_nodes(int K) { return lds_nodes(K, edge_rows); }
 
 extern "C" int64_t rl4co_nargnn_depot_scratch_bytes(int N, int K) {
   if (N < 3 || N > 1024 || K < 1 || K > 256 || K > N - 2) return 0;
-  return scratch_floats(tier_of(N, K), N, K) * 4;
+  return scratch_floats(tier_of(N, edge_rows(N, K)), N, edge_rows(N, K), kWaves) * 4;
 }
 
 extern "C" int rl4co_nargnn_depot_heatmap(const rl4co_nargnn_depot_args* args, void* stream) {
-  static_assert(lds_bytes(1, kNodeLdsMax, 1) + kStaticLds <= kCuLds, "the node planes of tier 1 fit the LDS");
+  static_assert(lds_bytes(1, kNodeLdsMax, edge_rows(kNodeLdsMax, 1)) + kStaticLds <= kCuLds, "the node planes of tier 1 fit the LDS");
   static_assert(edge_rows(1024, 256) * kRS < (int64_t)1 << 31, "row offsets fit an int");
   RL4CO_REQUIRE(args != nullptr);
   const rl4co_nargnn_depot_args& a = *args;
-  RL4CO_REQUIRE(a.D == kD);
-  RL4CO_REQUIRE(a.B >= 1);
+  if (const int rc = require_model(a)) return rc;
   RL4CO_REQUIRE(a.N >= 3 && a.N <= 1024);
   RL4CO_REQUIRE(a.K >= 1 && a.K <= 256 && a.K <= a.N - 2);
   RL4CO_REQUIRE(a.F == 1 || a.F == 2);
-  RL4CO_REQUIRE(a.L >= 0 && a.L <= (1 << 20));
-  RL4CO_REQUIRE(a.H >= 1 && a.H <= (1 << 20));
-  RL4CO_REQUIRE(a.n_workgroups >= 1 && a.n_workgroups <= a.B);
+  if (const int rc = require_depth_and_grid(a)) return rc;
   RL4CO_REQUIRE(a.locs != nullptr && a.feats != nullptr && a.neighbors != nullptr && a.edge_cost != nullptr && a.depot_cost != nullptr);
   RL4CO_REQUIRE(a.init_w != nullptr && a.init_b != nullptr && a.depot_w != nullptr && a.depot_b != nullptr);
   RL4CO_REQUIRE(a.edge_w != nullptr && a.edge_b != nullptr);
-  RL4CO_REQUIRE(a.L == 0 || (a.lin_w != nullptr && a.lin_b != nullptr && a.bn != nullptr));
-  RL4CO_REQUIRE(a.H == 1 || a.mlp_w != nullptr);
-  RL4CO_REQUIRE(a.out_w != nullptr);
-  RL4CO_REQUIRE(((reinterpret_cast<uintptr_t>(a.lin_w) | reinterpret_cast<uintptr_t>(a.mlp_w)) & 15) == 0);  // 16-byte fragments
-  RL4CO_REQUIRE(a.scratch != nullptr);
-  RL4CO_REQUIRE((reinterpret_cast<uintptr_t>(a.scratch) & 15) == 0);
-  RL4CO_REQUIRE(a.scratch_bytes >= (int64_t)a.n_workgroups * rl4co_nargnn_depot_scratch_bytes(a.N, a.K));
-  RL4CO_REQUIRE(a.heatmap != nullptr && a.node_embed != nullptr && a.err != nullptr);
-  hipStream_t s = rl4co::as_stream(stream);
-  switch (tier_of(a.N, a.K)) {
-    case 0: return launch<0>(a, s);
-    case 1: return launch<1>(a, s);
-    default: return launch<2>(a, s);
-  }
+  if (const int rc = require_buffers(a, rl4co_nargnn_depot_scratch_bytes(a.N, a.K))) return rc;
+  return launch_tier<nargnn_depot_kernel<0>, nargnn_depot_kernel<1>, nargnn_depot_kernel<2>>(a, edge_rows(a.N, a.K), stream);
 }

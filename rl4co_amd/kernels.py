@@ -622,6 +622,55 @@ def nargnn_lds_nodes(k: int) -> int:
 
 
 _NARGNN_SCRATCH_CAP = 1 << 30  # bytes of scratch a launch may take before the grid is made smaller than the card
+_NARGNN_PARAMS = ("init_w", "init_b", "edge_w", "edge_b", "lin_w", "lin_b", "bn", "mlp_w", "mlp_b", "out_w", "out_b")
+
+
+def _nargnn_launch(symbol: str, a, sizes: tuple, inputs: dict, params: dict, extra: dict, scalars: dict, *, small_value,
+                   fill_value, n_workgroups, err):
+    """The one body behind :func:`nargnn_heatmap` and :func:`nargnn_depot_heatmap`, from the parameter shapes to the
+    launch of ``<symbol>_heatmap``. ``sizes``: (B, N, K, D) as the caller checked them; ``inputs``: the instance tensors as
+    name -> (tensor, dtype) in the struct's order; ``params``: the eleven parameter keywords both bindings take;
+    ``extra``: the graph's own parameters as name -> (tensor, shape), which stand behind ``init_b``; ``scalars``: the
+    struct's own scalar fields."""
+    b, n, k, d = sizes
+    init_w, init_b, edge_w, edge_b, lin_w, lin_b, bn, mlp_w, mlp_b, out_w, out_b = (params[key] for key in _NARGNN_PARAMS)
+    layers = 0 if lin_w is None else lin_w.shape[0]
+    if layers and (lin_b is None or bn is None):
+        raise ValueError("lin_w needs lin_b and bn")
+    hidden = 0 if mlp_w is None else mlp_w.shape[0]
+    want = {"init_b": (init_b, (d,)), **extra, "edge_b": (edge_b, (d,)), "lin_w": (lin_w, (layers, 5, d, d)),
+            "lin_b": (lin_b if layers else None, (layers, 5, d)), "bn": (bn if layers else None, (layers, 2, 2, d)),
+            "mlp_w": (mlp_w, (hidden, d, d)), "mlp_b": (mlp_b, (hidden, d)), "out_b": (out_b, (1,))}
+    for name, (t, shape) in want.items():
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    if mlp_b is not None and hidden == 0:
+        mlp_b = None
+    edge_w, out_w = edge_w.reshape(-1), out_w.reshape(-1)
+    if edge_w.numel() != d or out_w.numel() != d:
+        raise ValueError(f"edge_w and out_w must hold {d} values, got {edge_w.numel()} and {out_w.numel()}")
+    values = {name: _dev(t, dtype, name) for name, (t, dtype) in inputs.items()}
+    named = dict(init_w=init_w, init_b=init_b, **{name: t for name, (t, _) in extra.items()}, edge_w=edge_w, edge_b=edge_b,
+                 lin_w=lin_w if layers else None, lin_b=lin_b if layers else None, bn=bn if layers else None,
+                 mlp_w=mlp_w if hidden else None, mlp_b=mlp_b, out_w=out_w, out_b=out_b)
+    values.update({key: (None if t is None else _dev(t, torch.float32, key)) for key, t in named.items()})
+    dev = values["locs"].device
+    if fill_value is None:
+        fill_value = float(torch.log(torch.tensor(small_value, dtype=torch.float32)))
+    per_wg = int(getattr(_lib.lib(), symbol + "_scratch_bytes")(n, k))
+    if n_workgroups is None:  # one workgroup per CU (eight waves above 128 VGPRs: a second one does not fit), within the cap
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        n_workgroups = min(b, cus, max(1, _NARGNN_SCRATCH_CAP // per_wg))
+    if not 1 <= n_workgroups <= b:
+        raise ValueError(f"n_workgroups must be in [1, B = {b}], got {n_workgroups}")
+    scratch = torch.empty(n_workgroups * per_wg // 4, dtype=torch.float32, device=dev)
+    heatmap = torch.empty((b, n, n), dtype=torch.float32, device=dev)
+    node_embed = torch.empty((b, n, d), dtype=torch.float32, device=dev)
+    values.update(B=b, N=n, K=k, D=d, L=layers, H=hidden + 1, n_workgroups=int(n_workgroups), **scalars,
+                  small_value=float(small_value), fill_value=float(fill_value), scratch=scratch,
+                  scratch_bytes=scratch.numel() * 4, heatmap=heatmap, node_embed=node_embed)
+    _aco_launch(symbol + "_heatmap", a, values, err, dev)
+    return heatmap, node_embed
 
 
 def nargnn_heatmap(locs: Tensor, neighbors: Tensor, edge_cost: Tensor, *, init_w: Tensor, init_b: Tensor, edge_w: Tensor,
@@ -654,55 +703,13 @@ def nargnn_heatmap(locs: Tensor, neighbors: Tensor, edge_cost: Tensor, *, init_w
     if b < 1 or not 2 <= n <= 1024 or not 1 <= k <= min(n - 1, 256):
         raise NotImplementedError(f"nargnn_heatmap serves B >= 1, 2 <= N <= 1024 and 1 <= K <= min(N - 1, 256), got "
                                   f"B = {b}, N = {n}, K = {k}")
-    layers = 0 if lin_w is None else lin_w.shape[0]
-    if layers and (lin_b is None or bn is None):
-        raise ValueError("lin_w needs lin_b and bn")
-    hidden = 0 if mlp_w is None else mlp_w.shape[0]
-    want = {"init_b": (init_b, (d,)), "edge_b": (edge_b, (d,)), "lin_w": (lin_w, (layers, 5, d, d)),
-            "lin_b": (lin_b if layers else None, (layers, 5, d)), "bn": (bn if layers else None, (layers, 2, 2, d)),
-            "mlp_w": (mlp_w, (hidden, d, d)), "mlp_b": (mlp_b, (hidden, d)), "out_b": (out_b, (1,))}
-    for name, (t, shape) in want.items():
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
-    if mlp_b is not None and hidden == 0:
-        mlp_b = None
-    edge_w, out_w = edge_w.reshape(-1), out_w.reshape(-1)
-    if edge_w.numel() != d or out_w.numel() != d:
-        raise ValueError(f"edge_w and out_w must hold {d} values, got {edge_w.numel()} and {out_w.numel()}")
-    locs = _dev(locs, torch.float32, "locs")
-    neighbors = _dev(neighbors, torch.int32, "neighbors")
-    edge_cost = _dev(edge_cost, torch.float32, "edge_cost")
-    named = dict(init_w=init_w, init_b=init_b, edge_w=edge_w, edge_b=edge_b, lin_w=lin_w if layers else None,
-                 lin_b=lin_b if layers else None, bn=bn if layers else None, mlp_w=mlp_w if hidden else None, mlp_b=mlp_b,
-                 out_w=out_w, out_b=out_b)
-    named = {key: (None if t is None else _dev(t, torch.float32, key)) for key, t in named.items()}
-    dev = locs.device
-    if fill_value is None:
-        fill_value = float(torch.log(torch.tensor(small_value, dtype=torch.float32)))
-    per_wg = int(_lib.lib().rl4co_nargnn_scratch_bytes(n, k))
-    if n_workgroups is None:  # one workgroup per CU (eight waves of 155 VGPRs: a second one does not fit), within the cap
-        cus = torch.cuda.get_device_properties(dev).multi_processor_count
-        n_workgroups = min(b, cus, max(1, _NARGNN_SCRATCH_CAP // per_wg))
-    if not 1 <= n_workgroups <= b:
-        raise ValueError(f"n_workgroups must be in [1, B = {b}], got {n_workgroups}")
-    scratch = torch.empty(n_workgroups * per_wg // 4, dtype=torch.float32, device=dev)
-    heatmap = torch.empty((b, n, n), dtype=torch.float32, device=dev)
-    node_embed = torch.empty((b, n, d), dtype=torch.float32, device=dev)
-    own = err is None
-    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
-    a = _lib.NargnnArgs()
-    a.B, a.N, a.K, a.D, a.L, a.H, a.n_workgroups, a.reserved0 = b, n, k, d, layers, hidden + 1, int(n_workgroups), 0
-    a.small_value, a.fill_value = float(small_value), float(fill_value)
-    a.locs, a.neighbors, a.edge_cost = _ptr(locs), _ptr(neighbors), _ptr(edge_cost)
-    for key, t in named.items():
-        setattr(a, key, _ptr(t))
-    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * 4
-    a.heatmap, a.node_embed, a.err = _ptr(heatmap), _ptr(node_embed), _ptr(err)
-    st = _lib.lib().rl4co_nargnn_heatmap(C.byref(a), _stream())
-    _lib.check(st, "rl4co_nargnn_heatmap")
-    if own:
-        raise_if_error(err)
-    return heatmap, node_embed
+    params = dict(init_w=init_w, init_b=init_b, edge_w=edge_w, edge_b=edge_b, lin_w=lin_w, lin_b=lin_b, bn=bn, mlp_w=mlp_w,
+                  mlp_b=mlp_b, out_w=out_w, out_b=out_b)
+    return _nargnn_launch("rl4co_nargnn", _lib.NargnnArgs(), (b, n, k, d),
+                          dict(locs=(locs, torch.float32), neighbors=(neighbors, torch.int32),
+                               edge_cost=(edge_cost, torch.float32)), params, {},
+                          dict(reserved0=0), small_value=small_value, fill_value=fill_value, n_workgroups=n_workgroups,
+                          err=err)
 
 
 def nargnn_depot_lds_nodes(k: int) -> int:
@@ -749,59 +756,13 @@ def nargnn_depot_heatmap(locs: Tensor, feats: Tensor, neighbors: Tensor, edge_co
     if b < 1 or not 3 <= n <= 1024 or not 1 <= k <= min(n - 2, 256):
         raise NotImplementedError(f"nargnn_depot_heatmap serves B >= 1, 3 <= N <= 1024 and 1 <= K <= min(N - 2, 256), got "
                                   f"B = {b}, N = {n}, K = {k}")
-    layers = 0 if lin_w is None else lin_w.shape[0]
-    if layers and (lin_b is None or bn is None):
-        raise ValueError("lin_w needs lin_b and bn")
-    hidden = 0 if mlp_w is None else mlp_w.shape[0]
-    want = {"init_b": (init_b, (d,)), "depot_w": (depot_w, (d, 2)), "depot_b": (depot_b, (d,)), "edge_b": (edge_b, (d,)),
-            "lin_w": (lin_w, (layers, 5, d, d)), "lin_b": (lin_b if layers else None, (layers, 5, d)),
-            "bn": (bn if layers else None, (layers, 2, 2, d)), "mlp_w": (mlp_w, (hidden, d, d)),
-            "mlp_b": (mlp_b, (hidden, d)), "out_b": (out_b, (1,))}
-    for name, (t, shape) in want.items():
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
-    if mlp_b is not None and hidden == 0:
-        mlp_b = None
-    edge_w, out_w = edge_w.reshape(-1), out_w.reshape(-1)
-    if edge_w.numel() != d or out_w.numel() != d:
-        raise ValueError(f"edge_w and out_w must hold {d} values, got {edge_w.numel()} and {out_w.numel()}")
-    locs = _dev(locs, torch.float32, "locs")
-    feats = _dev(feats, torch.float32, "feats")
-    neighbors = _dev(neighbors, torch.int32, "neighbors")
-    edge_cost = _dev(edge_cost, torch.float32, "edge_cost")
-    depot_cost = _dev(depot_cost, torch.float32, "depot_cost")
-    named = dict(init_w=init_w, init_b=init_b, depot_w=depot_w, depot_b=depot_b, edge_w=edge_w, edge_b=edge_b,
-                 lin_w=lin_w if layers else None, lin_b=lin_b if layers else None, bn=bn if layers else None,
-                 mlp_w=mlp_w if hidden else None, mlp_b=mlp_b, out_w=out_w, out_b=out_b)
-    named = {key: (None if t is None else _dev(t, torch.float32, key)) for key, t in named.items()}
-    dev = locs.device
-    if fill_value is None:
-        fill_value = float(torch.log(torch.tensor(small_value, dtype=torch.float32)))
-    per_wg = int(_lib.lib().rl4co_nargnn_depot_scratch_bytes(n, k))
-    if n_workgroups is None:  # one workgroup per CU (eight waves above 128 VGPRs: a second one does not fit), within the cap
-        cus = torch.cuda.get_device_properties(dev).multi_processor_count
-        n_workgroups = min(b, cus, max(1, _NARGNN_SCRATCH_CAP // per_wg))
-    if not 1 <= n_workgroups <= b:
-        raise ValueError(f"n_workgroups must be in [1, B = {b}], got {n_workgroups}")
-    scratch = torch.empty(n_workgroups * per_wg // 4, dtype=torch.float32, device=dev)
-    heatmap = torch.empty((b, n, n), dtype=torch.float32, device=dev)
-    node_embed = torch.empty((b, n, d), dtype=torch.float32, device=dev)
-    own = err is None
-    err = new_error_word(dev) if own else _dev(err, torch.int32, "err")
-    a = _lib.NargnnDepotArgs()
-    a.B, a.N, a.K, a.F, a.D, a.L, a.H, a.n_workgroups = b, n, k, f, d, layers, hidden + 1, int(n_workgroups)
-    a.small_value, a.fill_value = float(small_value), float(fill_value)
-    a.locs, a.feats, a.neighbors, a.edge_cost, a.depot_cost = (_ptr(locs), _ptr(feats), _ptr(neighbors), _ptr(edge_cost),
-                                                               _ptr(depot_cost))
-    for key, t in named.items():
-        setattr(a, key, _ptr(t))
-    a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel() * 4
-    a.heatmap, a.node_embed, a.err = _ptr(heatmap), _ptr(node_embed), _ptr(err)
-    st = _lib.lib().rl4co_nargnn_depot_heatmap(C.byref(a), _stream())
-    _lib.check(st, "rl4co_nargnn_depot_heatmap")
-    if own:
-        raise_if_error(err)
-    return heatmap, node_embed
+    params = dict(init_w=init_w, init_b=init_b, edge_w=edge_w, edge_b=edge_b, lin_w=lin_w, lin_b=lin_b, bn=bn, mlp_w=mlp_w,
+                  mlp_b=mlp_b, out_w=out_w, out_b=out_b)
+    return _nargnn_launch("rl4co_nargnn_depot", _lib.NargnnDepotArgs(), (b, n, k, d),
+                          dict(locs=(locs, torch.float32), feats=(feats, torch.float32), neighbors=(neighbors, torch.int32),
+                               edge_cost=(edge_cost, torch.float32), depot_cost=(depot_cost, torch.float32)),
+                          params, dict(depot_w=(depot_w, (d, 2)), depot_b=(depot_b, (d,))),
+                          dict(F=f), small_value=small_value, fill_value=fill_value, n_workgroups=n_workgroups, err=err)
 
 
 # ---- the Ant System: one table of families, one launch path for the search, one for the backward ---------------------------
