@@ -57,8 +57,10 @@ extern "C" {
  *  24: rl4co_aco_tsp_logp_grad / rl4co_aco_tsp_grad_lds_entries (the backward of the ants' log-likelihoods with respect
  *      to the heatmap, DeepACO's training path, rl4co_aco_tsp_grad_args).
  *  25: rl4co_aco_depot_logp_grad / rl4co_aco_depot_grad_lds_entries / rl4co_aco_depot_grad_scratch_bytes (the same backward
- *      for the depot graphs of CVRP, OP and PCTSP, rl4co_aco_depot_grad_args). */
-#define RL4CO_ABI_VERSION 25
+ *      for the depot graphs of CVRP, OP and PCTSP, rl4co_aco_depot_grad_args).
+ *  26: rl4co_nargnn_train_forward / rl4co_nargnn_train_backward / rl4co_nargnn_train_workspace_bytes (the heatmap
+ *      encoder's GNN stack in train mode and its backward, rl4co_nargnn_train_args). */
+#define RL4CO_ABI_VERSION 26
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -1054,6 +1056,66 @@ int rl4co_nargnn_depot_heatmap(const rl4co_nargnn_depot_args* args, void* stream
 int rl4co_nargnn_depot_lds_nodes(int K);
 /* Bytes of `scratch` one workgroup needs at this shape (0 outside the supported range). */
 int64_t rl4co_nargnn_depot_scratch_bytes(int N, int K);
+
+/* --------------------------------------------------------------------------
+ * The GNN stack of the TSP heatmap encoder in TRAIN mode and its backward (gnn.py:45-61 over the regular graph, batch
+ * norms on BATCH statistics), fp32, nargnn_train.hip. Rows: n_v = B N node rows, n_e = B N K edge rows, all dense
+ * [rows, D], D = 64; edge row e belongs to node i = e / K and points at node j = (i / N) N + neighbors[e].
+ *   per layer, s = sigmoid(w0):
+ *     pre_v[i] = v_lin1(x0)[i] + (1 / K) sum_k s[i,k] * v_lin2(x0)[j];   pre_e[e] = e_lin(w0)[e] + v_lin3(x0)[i] + v_lin4(x0)[j]
+ *     per channel over ALL rows: mu, biased var, r = 1 / sqrt(var + eps); x = x0 + silu(gamma (pre_v - mu) r + beta), w alike
+ * rl4co_nargnn_train_forward writes x_out, w_out, stats[l] = (mu_v, r_v, var_v, mu_e, r_e, var_e) and the saves in
+ * `workspace`; rl4co_nargnn_train_backward, given the SAME workspace, inputs and parameters and the gradients of x_out and
+ * w_out, writes the gradients of x_in, w_in and of every parameter. Every batch-wide reduction crosses a launch boundary
+ * (per-workgroup partials, a finalize launch that combines them in a fixed order); there is no grid barrier and no
+ * floating-point atomic: every output is bit-identical run to run. The variance is combined from per-workgroup
+ * (count, mean, M2) by Chan's formula. The scatter to target nodes runs over the incoming-edge CSR: csr_ptr[j] ..
+ * csr_ptr[j + 1] are the positions in csr_src of the edge rows e (ascending) that point at global node j.
+ * A neighbour index outside [0, N) or a CSR that is not exactly that of `neighbors` sets RL4CO_EBIT_TOUR_INDEX, decided by
+ * the first launch of either call before anything is read through them; the call's outputs are then left unwritten.
+ * workspace floats, nv = 64 B N, ne = 64 B N K, P_v = min(ceil(B N / 64), 1024), P_e = min(ceil(B N K / 64), 1024):
+ *   64 + max(L - 1, 0) (nv + ne) + L (2 nv + ne) + 5 nv + 2 ne + 192 (P_v + P_e) + 4160 (4 P_v + P_e) + 512
+ * (the layers' x0 and w0 behind the first, pre_v, x2 and pre_e per layer; the node planes, the running gradients and gu_e;
+ * the statistics partials; the weight-gradient partials; the backward's means).
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_nargnn_train_args {
+  int32_t B;                  /* instances, >= 1                                              */
+  int32_t N;                  /* nodes, 2 .. 1024; B N >= 2                                   */
+  int32_t K;                  /* out-edges per node, 1 .. min(N - 1, 64)                      */
+  int32_t D;                  /* embedding width: 64                                          */
+  int32_t L;                  /* GNN layers, >= 1                                             */
+  int32_t reserved0;          /* 0                                                            */
+  float eps;                  /* the batch norms' eps                                         */
+  int32_t reserved1;          /* 0                                                            */
+  const int32_t* neighbors;   /* [B,N,K]                                                      */
+  const int32_t* csr_ptr;     /* [B N + 1]                                                    */
+  const int32_t* csr_src;     /* [B N K]                                                      */
+  const float* x_in;          /* [B N, D]                                                     */
+  const float* w_in;          /* [B N K, D]                                                   */
+  const float* lin_w;         /* [L,5,D,D]: v_lin1 .. v_lin4, e_lin                           */
+  const float* lin_b;         /* [L,5,D]                                                      */
+  const float* bn_w;          /* [L,2,D]: gamma of (v_bn, e_bn)                               */
+  const float* bn_b;          /* [L,2,D]: beta                                                */
+  float* workspace;           /* rl4co_nargnn_train_workspace_bytes(B, N, K, L) bytes         */
+  int64_t workspace_bytes;
+  float* x_out;               /* [B N, D]       forward out                                   */
+  float* w_out;               /* [B N K, D]     forward out                                   */
+  float* stats;               /* [L,6,D]        forward out, backward in                      */
+  const float* grad_x_out;    /* [B N, D]       backward in                                   */
+  const float* grad_w_out;    /* [B N K, D]     backward in                                   */
+  float* grad_x_in;           /* [B N, D]       backward out                                  */
+  float* grad_w_in;           /* [B N K, D]     backward out                                  */
+  float* grad_lin_w;          /* [L,5,D,D]      backward out                                  */
+  float* grad_lin_b;          /* [L,5,D]        backward out                                  */
+  float* grad_bn_w;           /* [L,2,D]        backward out                                  */
+  float* grad_bn_b;           /* [L,2,D]        backward out                                  */
+  int32_t* err;               /* sticky error bits                                            */
+} rl4co_nargnn_train_args;
+
+int rl4co_nargnn_train_forward(const rl4co_nargnn_train_args* args, void* stream);
+int rl4co_nargnn_train_backward(const rl4co_nargnn_train_args* args, void* stream);
+/* Bytes of `workspace` at this shape by the formula above (0 outside the supported range). */
+int64_t rl4co_nargnn_train_workspace_bytes(int B, int N, int K, int L);
 
 /* --------------------------------------------------------------------------
  * a11-a13  fused encoder + decoder-cache fold on the matrix cores (inference rollouts).

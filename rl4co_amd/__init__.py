@@ -7,7 +7,8 @@ See DESIGN.md for the path, the boundary and what is out of scope.
 """
 __version__ = "0.1.0"
 
-__all__ = ["AntSystem", "DeepACOPolicy", "NARGNNDepotEncoder", "NARGNNEncoder", "NonAutoregressivePolicy"]
+__all__ = ["AntSystem", "DeepACOPolicy", "NARGNNDepotEncoder", "NARGNNEncoder", "NonAutoregressivePolicy",
+           "TrainableNARGNNEncoder"]
 
 
 def __getattr__(name):
@@ -16,7 +17,7 @@ def __getattr__(name):
 
         return AntSystem
     # rl4co_amd.nargnn: DeepACO's heatmap encoders on rl4co_nargnn_heatmap / rl4co_nargnn_depot_heatmap
-    if name in ("NARGNNEncoder", "NARGNNDepotEncoder", "DeepACOPolicy", "NonAutoregressivePolicy"):
+    if name in ("NARGNNEncoder", "NARGNNDepotEncoder", "DeepACOPolicy", "NonAutoregressivePolicy", "TrainableNARGNNEncoder"):
         from . import nargnn
 
         return getattr(nargnn, name)

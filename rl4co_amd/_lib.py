@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 25  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 26  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -151,6 +151,19 @@ class NargnnDepotArgs(C.Structure):
         ("init_w", _vp), ("init_b", _vp), ("depot_w", _vp), ("depot_b", _vp), ("edge_w", _vp), ("edge_b", _vp),
         ("lin_w", _vp), ("lin_b", _vp), ("bn", _vp), ("mlp_w", _vp), ("mlp_b", _vp), ("out_w", _vp), ("out_b", _vp),
         ("scratch", _vp), ("scratch_bytes", _i64), ("heatmap", _vp), ("node_embed", _vp), ("err", _vp),
+    ]
+
+
+class NargnnTrainArgs(C.Structure):
+    """Mirror of ``struct rl4co_nargnn_train_args`` (field order and types must match the header)."""
+
+    _fields_ = [
+        ("B", _i32), ("N", _i32), ("K", _i32), ("D", _i32), ("L", _i32), ("reserved0", _i32), ("eps", _f32), ("reserved1", _i32),
+        ("neighbors", _vp), ("csr_ptr", _vp), ("csr_src", _vp), ("x_in", _vp), ("w_in", _vp),
+        ("lin_w", _vp), ("lin_b", _vp), ("bn_w", _vp), ("bn_b", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+        ("x_out", _vp), ("w_out", _vp), ("stats", _vp), ("grad_x_out", _vp), ("grad_w_out", _vp),
+        ("grad_x_in", _vp), ("grad_w_in", _vp), ("grad_lin_w", _vp), ("grad_lin_b", _vp), ("grad_bn_w", _vp),
+        ("grad_bn_b", _vp), ("err", _vp),
     ]
 
 
@@ -340,6 +353,9 @@ SYMBOLS = {
     "rl4co_nargnn_depot_heatmap": (C.c_int, [C.POINTER(NargnnDepotArgs), _vp]),
     "rl4co_nargnn_depot_lds_nodes": (C.c_int, [C.c_int]),
     "rl4co_nargnn_depot_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "rl4co_nargnn_train_forward": (C.c_int, [C.POINTER(NargnnTrainArgs), _vp]),
+    "rl4co_nargnn_train_backward": (C.c_int, [C.POINTER(NargnnTrainArgs), _vp]),
+    "rl4co_nargnn_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "rl4co_select_start_nodes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "rl4co_augment_dihedral8_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_augment_symmetric_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp]),

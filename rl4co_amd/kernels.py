@@ -765,6 +765,118 @@ def nargnn_depot_heatmap(locs: Tensor, feats: Tensor, neighbors: Tensor, edge_co
                           dict(F=f), small_value=small_value, fill_value=fill_value, n_workgroups=n_workgroups, err=err)
 
 
+# ---- the heatmap encoder's GNN stack in train mode (csrc/nargnn_train.hip) ------------------------------------------------------
+def nargnn_train_workspace_bytes(b: int, n: int, k: int, layers: int) -> int:
+    """Bytes of workspace the train-mode GNN stack needs at this shape (the formula is in include/rl4co_amd.h); 0 outside the
+    served range."""
+    return int(_lib.lib().rl4co_nargnn_train_workspace_bytes(int(b), int(n), int(k), int(layers)))
+
+
+def incoming_csr(neighbors: Tensor) -> tuple[Tensor, Tensor]:
+    """The reverse adjacency of ``neighbors`` [B, N, K] over the flat rows: ``(csr_ptr [B N + 1] int32, csr_src [B N K]
+    int32)``; positions ``csr_ptr[j] .. csr_ptr[j + 1]`` of ``csr_src`` hold, ascending, the edge rows e = (b N + i) K + k
+    that point at the global node j = b N + neighbors[b, i, k]. A stable sort of the targets keeps the rows ascending."""
+    b, n, k = neighbors.shape
+    target = (neighbors.to(torch.int64) + torch.arange(b, device=neighbors.device).view(b, 1, 1) * n).reshape(-1)
+    src = torch.sort(target, stable=True).indices.to(torch.int32)
+    # (out-of-range targets are clamped for the count alone: the kernel's check refuses such lists)
+    counts = torch.bincount(target.clamp(0, b * n - 1), minlength=b * n)
+    ptr = torch.zeros(b * n + 1, dtype=torch.int64, device=neighbors.device)
+    ptr[1:] = counts.cumsum(0)
+    return ptr.to(torch.int32), src.contiguous()
+
+
+def _nargnn_train_args(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps):
+    b, n, k = neighbors.shape
+    d = x_in.shape[-1]
+    if d != 64:
+        raise NotImplementedError(f"nargnn_train serves embed_dim = 64 only, got {d}")
+    if b < 1 or not 2 <= n <= 1024 or not 1 <= k <= min(n - 1, 64):
+        raise NotImplementedError(f"nargnn_train serves B >= 1, 2 <= N <= 1024 and 1 <= K <= min(N - 1, 64), got "
+                                  f"B = {b}, N = {n}, K = {k}")
+    layers = 0 if lin_w is None else lin_w.shape[0]
+    if layers < 1:
+        raise ValueError("nargnn_train takes at least one layer (without layers the stack is the identity)")
+    want = dict(x_in=(x_in, (b, n, d)), w_in=(w_in, (b, n, k, d)), lin_w=(lin_w, (layers, 5, d, d)), lin_b=(lin_b, (layers, 5, d)),
+                bn_w=(bn_w, (layers, 2, d)), bn_b=(bn_b, (layers, 2, d)))
+    for name, (t, shape) in want.items():
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    if tuple(csr_ptr.shape) != (b * n + 1,) or tuple(csr_src.shape) != (b * n * k,):
+        raise ValueError(f"csr_ptr must be [{b * n + 1}] and csr_src [{b * n * k}], got {tuple(csr_ptr.shape)} and "
+                         f"{tuple(csr_src.shape)}")
+    for name, (t, _) in want.items():
+        _dev(t, torch.float32, name)
+    for name, t in (("neighbors", neighbors), ("csr_ptr", csr_ptr), ("csr_src", csr_src)):
+        _dev(t, torch.int32, name)
+    a = _lib.NargnnTrainArgs()
+    a.B, a.N, a.K, a.D, a.L, a.reserved0, a.eps, a.reserved1 = b, n, k, d, layers, 0, float(eps), 0
+    values = dict(neighbors=neighbors, csr_ptr=csr_ptr, csr_src=csr_src, x_in=x_in, w_in=w_in, lin_w=lin_w, lin_b=lin_b, bn_w=bn_w,
+                  bn_b=bn_b)
+    return a, values, (b, n, k, d, layers)
+
+
+def _nargnn_train_launch(symbol: str, a, values: dict, err: Tensor | None, dev) -> None:
+    for name, ctype in a._fields_:
+        if ctype is C.c_void_p and name != "err":
+            setattr(a, name, _ptr(values.get(name)))
+    own = err is None
+    word = new_error_word(dev) if own else _dev(err, torch.int32, "err")
+    a.err = _ptr(word)
+    _lib.check(getattr(_lib.lib(), symbol)(C.byref(a), _stream()), symbol)
+    if own:
+        raise_if_error(word)
+
+
+def nargnn_train_forward(neighbors: Tensor, csr_ptr: Tensor, csr_src: Tensor, x_in: Tensor, w_in: Tensor, *, lin_w: Tensor,
+                         lin_b: Tensor, bn_w: Tensor, bn_b: Tensor, eps: float = 1e-5, err: Tensor | None = None):
+    """The L-layer GNN stack of the TSP heatmap encoder on BATCH statistics (rl4co_nargnn_train_forward), fp32.
+
+    ``neighbors`` [B, N, K] int32, ``(csr_ptr, csr_src)`` from :func:`incoming_csr`, ``x_in`` [B, N, 64] and ``w_in``
+    [B, N, K, 64] (the activated embeddings), ``lin_w`` [L, 5, 64, 64], ``lin_b`` [L, 5, 64], ``bn_w`` / ``bn_b`` [L, 2, 64]
+    (gamma / beta of v_bn, e_bn). Returns ``(x_out, w_out, stats [L, 6, 64], workspace)``; ``stats[l]`` = (mu_v, r_v, var_v,
+    mu_e, r_e, var_e), the variances biased. ``workspace`` holds what :func:`nargnn_train_backward` reads. Without ``err``
+    the error word is read back and a bad neighbour list or CSR raises; the outputs are then not returned."""
+    a, values, (b, n, k, d, layers) = _nargnn_train_args(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps)
+    dev = x_in.device
+    nbytes = nargnn_train_workspace_bytes(b, n, k, layers)
+    if nbytes <= 0:
+        raise NotImplementedError(f"nargnn_train does not serve B = {b}, N = {n}, K = {k}, L = {layers} (B N K <= 2^24)")
+    workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    x_out = torch.empty((b, n, d), dtype=torch.float32, device=dev)
+    w_out = torch.empty((b, n, k, d), dtype=torch.float32, device=dev)
+    stats = torch.empty((layers, 6, d), dtype=torch.float32, device=dev)
+    a.workspace_bytes = nbytes
+    values.update(workspace=workspace, x_out=x_out, w_out=w_out, stats=stats)
+    _nargnn_train_launch("rl4co_nargnn_train_forward", a, values, err, dev)
+    return x_out, w_out, stats, workspace
+
+
+def nargnn_train_backward(neighbors: Tensor, csr_ptr: Tensor, csr_src: Tensor, x_in: Tensor, w_in: Tensor, *, lin_w: Tensor,
+                          lin_b: Tensor, bn_w: Tensor, bn_b: Tensor, stats: Tensor, workspace: Tensor, grad_x_out: Tensor,
+                          grad_w_out: Tensor, eps: float = 1e-5, err: Tensor | None = None) -> dict:
+    """The backward of :func:`nargnn_train_forward` (rl4co_nargnn_train_backward) given its inputs, ``stats`` and
+    ``workspace`` and the gradients of its two outputs. Returns the gradients by name: ``x_in``, ``w_in``, ``lin_w``,
+    ``lin_b``, ``bn_w``, ``bn_b``."""
+    a, values, (b, n, k, d, layers) = _nargnn_train_args(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps)
+    dev = x_in.device
+    for name, t, shape in (("grad_x_out", grad_x_out, (b, n, d)), ("grad_w_out", grad_w_out, (b, n, k, d)),
+                           ("stats", stats, (layers, 6, d))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+        _dev(t, torch.float32, name)
+    nbytes = nargnn_train_workspace_bytes(b, n, k, layers)
+    if _dev(workspace, torch.float32, "workspace").numel() * 4 < nbytes or nbytes <= 0:
+        raise ValueError(f"workspace must hold {nbytes} bytes, got {workspace.numel() * 4}")
+    grads = dict(x_in=torch.empty_like(x_in), w_in=torch.empty_like(w_in), lin_w=torch.empty_like(lin_w),
+                 lin_b=torch.empty_like(lin_b), bn_w=torch.empty_like(bn_w), bn_b=torch.empty_like(bn_b))
+    a.workspace_bytes = workspace.numel() * 4
+    values.update(workspace=workspace, stats=stats, grad_x_out=grad_x_out, grad_w_out=grad_w_out,
+                  **{"grad_" + key: t for key, t in grads.items()})
+    _nargnn_train_launch("rl4co_nargnn_train_backward", a, values, err, dev)
+    return grads
+
+
 # ---- the Ant System: one table of families, one launch path for the search, one for the backward ---------------------------
 _ACO_PRIZE_ENVS = {"op": _lib.ENV_OP, "pctsp": _lib.ENV_PCTSP, "spctsp": _lib.ENV_PCTSP}  # spctsp: the caller's prize is the stochastic one
 _ACO_DEPOT_GRAD_ENVS = {"cvrp": _lib.ENV_CVRP, **_ACO_PRIZE_ENVS}
