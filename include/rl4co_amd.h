@@ -59,8 +59,10 @@ extern "C" {
  *  25: rl4co_aco_depot_logp_grad / rl4co_aco_depot_grad_lds_entries / rl4co_aco_depot_grad_scratch_bytes (the same backward
  *      for the depot graphs of CVRP, OP and PCTSP, rl4co_aco_depot_grad_args).
  *  26: rl4co_nargnn_train_forward / rl4co_nargnn_train_backward / rl4co_nargnn_train_workspace_bytes (the heatmap
- *      encoder's GNN stack in train mode and its backward, rl4co_nargnn_train_args). */
-#define RL4CO_ABI_VERSION 26
+ *      encoder's GNN stack in train mode and its backward, rl4co_nargnn_train_args).
+ *  27: rl4co_nargnn_depot_train_forward / rl4co_nargnn_depot_train_backward / rl4co_nargnn_depot_train_workspace_bytes
+ *      (the same stack on the depot graphs of CVRP, OP and PCTSP, rl4co_nargnn_depot_train_args). */
+#define RL4CO_ABI_VERSION 27
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -1116,6 +1118,70 @@ int rl4co_nargnn_train_forward(const rl4co_nargnn_train_args* args, void* stream
 int rl4co_nargnn_train_backward(const rl4co_nargnn_train_args* args, void* stream);
 /* Bytes of `workspace` at this shape by the formula above (0 outside the supported range). */
 int64_t rl4co_nargnn_train_workspace_bytes(int B, int N, int K, int L);
+
+/* --------------------------------------------------------------------------
+ * The same stack, train mode and backward, on the DEPOT graph of CVRP, OP and PCTSP (CVRPEdgeEmbedding: every customer's K
+ * nearest customers plus the depot, the depot to every customer), fp32, nargnn_train.hip: the kernels of
+ * rl4co_nargnn_train_* instantiated for a second graph. Node 0 of an instance is the depot, C = N - 1 are customers.
+ * Rows: n_v = B N node rows, n_e = B E edge rows, E = C (K + 2), per instance in the reference's own order:
+ *   [0, C K)             the kNN rows by source: row (i - 1) K + k is i -> neighbors[i - 1, k], a customer in 1 .. N - 1
+ *   [C K, C K + C)       row C K + (i - 1) is i -> 0
+ *   [C K + C, C (K + 2)) row C K + C + (i - 1) is 0 -> i
+ * Source and target of a row are closed forms of (row, neighbors); no edge list is stored. deg(i), the out-degree, is
+ * K + 1 for a customer (its K rows and its i -> 0 row) and C for the depot.
+ *   per layer, s = sigmoid(w0), e: i -> j:
+ *     pre_v[i] = v_lin1(x0)[i] + (1 / deg(i)) sum_{e out of i} s[e] * v_lin2(x0)[j];
+ *     pre_e[e] = e_lin(w0)[e] + v_lin3(x0)[i] + v_lin4(x0)[j]
+ *     per channel over ALL rows: mu, biased var, r = 1 / sqrt(var + eps); x = x0 + silu(gamma (pre_v - mu) r + beta), w alike
+ * Forward, backward, statistics, determinism and the workspace are rl4co_nargnn_train_*'s, with E in place of N K:
+ *   nv = 64 B N, ne = 64 B E, P_v = min(ceil(B N / 64), 1024), P_e = min(ceil(B E / 64), 1024), the same formula.
+ * The depot's sums (its mean, its gradient sums: C terms) are eight interleaved partial sums, term t into partial t mod 8,
+ * combined ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)); every other node's sums run in row order.
+ * The CSR runs over all n_e rows: csr_ptr[j] .. csr_ptr[j + 1] are the positions in csr_src of the edge rows (ascending)
+ * whose target is global node j; the depot's in-degree is C, a customer's at least 1. A neighbour index outside [1, N)
+ * (the depot is nobody's kNN neighbour) or a CSR that is not exactly that of the rows' closed-form targets sets
+ * RL4CO_EBIT_TOUR_INDEX in the first launch of either call; the whole call is then refused (batch statistics tie the
+ * instances together) and its outputs are left unwritten.
+ * Served: B >= 1, 3 <= N <= 1024, 1 <= K <= min(N - 2, 64), L >= 1, B C (K + 2) <= 2^24.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_nargnn_depot_train_args {
+  int32_t B;                  /* instances, >= 1                                              */
+  int32_t N;                  /* nodes with the depot, 3 .. 1024                              */
+  int32_t K;                  /* kNN rows per customer, 1 .. min(N - 2, 64)                   */
+  int32_t D;                  /* embedding width: 64                                          */
+  int32_t L;                  /* GNN layers, >= 1                                             */
+  int32_t reserved0;          /* 0                                                            */
+  float eps;                  /* the batch norms' eps                                         */
+  int32_t reserved1;          /* 0                                                            */
+  const int32_t* neighbors;   /* [B,N-1,K], values in 1 .. N - 1                              */
+  const int32_t* csr_ptr;     /* [B N + 1]                                                    */
+  const int32_t* csr_src;     /* [B E]                                                        */
+  const float* x_in;          /* [B N, D]                                                     */
+  const float* w_in;          /* [B E, D]                                                     */
+  const float* lin_w;         /* [L,5,D,D]: v_lin1 .. v_lin4, e_lin                           */
+  const float* lin_b;         /* [L,5,D]                                                      */
+  const float* bn_w;          /* [L,2,D]: gamma of (v_bn, e_bn)                               */
+  const float* bn_b;          /* [L,2,D]: beta                                                */
+  float* workspace;           /* rl4co_nargnn_depot_train_workspace_bytes(B, N, K, L) bytes   */
+  int64_t workspace_bytes;
+  float* x_out;               /* [B N, D]       forward out                                   */
+  float* w_out;               /* [B E, D]       forward out                                   */
+  float* stats;               /* [L,6,D]        forward out, backward in                      */
+  const float* grad_x_out;    /* [B N, D]       backward in                                   */
+  const float* grad_w_out;    /* [B E, D]       backward in                                   */
+  float* grad_x_in;           /* [B N, D]       backward out                                  */
+  float* grad_w_in;           /* [B E, D]       backward out                                  */
+  float* grad_lin_w;          /* [L,5,D,D]      backward out                                  */
+  float* grad_lin_b;          /* [L,5,D]        backward out                                  */
+  float* grad_bn_w;           /* [L,2,D]        backward out                                  */
+  float* grad_bn_b;           /* [L,2,D]        backward out                                  */
+  int32_t* err;               /* sticky error bits                                            */
+} rl4co_nargnn_depot_train_args;
+
+int rl4co_nargnn_depot_train_forward(const rl4co_nargnn_depot_train_args* args, void* stream);
+int rl4co_nargnn_depot_train_backward(const rl4co_nargnn_depot_train_args* args, void* stream);
+/* Bytes of `workspace` at this shape (0 outside the served range). */
+int64_t rl4co_nargnn_depot_train_workspace_bytes(int B, int N, int K, int L);
 
 /* --------------------------------------------------------------------------
  * a11-a13  fused encoder + decoder-cache fold on the matrix cores (inference rollouts).

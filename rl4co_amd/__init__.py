@@ -8,7 +8,7 @@ See DESIGN.md for the path, the boundary and what is out of scope.
 __version__ = "0.1.0"
 
 __all__ = ["AntSystem", "DeepACOPolicy", "NARGNNDepotEncoder", "NARGNNEncoder", "NonAutoregressivePolicy",
-           "TrainableNARGNNEncoder"]
+           "TrainableNARGNNDepotEncoder", "TrainableNARGNNEncoder"]
 
 
 def __getattr__(name):
@@ -17,7 +17,8 @@ def __getattr__(name):
 
         return AntSystem
     # rl4co_amd.nargnn: DeepACO's heatmap encoders on rl4co_nargnn_heatmap / rl4co_nargnn_depot_heatmap
-    if name in ("NARGNNEncoder", "NARGNNDepotEncoder", "DeepACOPolicy", "NonAutoregressivePolicy", "TrainableNARGNNEncoder"):
+    if name in ("NARGNNEncoder", "NARGNNDepotEncoder", "DeepACOPolicy", "NonAutoregressivePolicy", "TrainableNARGNNEncoder",
+                "TrainableNARGNNDepotEncoder"):
         from . import nargnn
 
         return getattr(nargnn, name)

@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 26  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 27  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -165,6 +165,13 @@ class NargnnTrainArgs(C.Structure):
         ("grad_x_in", _vp), ("grad_w_in", _vp), ("grad_lin_w", _vp), ("grad_lin_b", _vp), ("grad_bn_w", _vp),
         ("grad_bn_b", _vp), ("err", _vp),
     ]
+
+
+class NargnnDepotTrainArgs(C.Structure):
+    """Mirror of ``struct rl4co_nargnn_depot_train_args``: the fields of ``rl4co_nargnn_train_args`` over the depot graph's
+    rows."""
+
+    _fields_ = list(NargnnTrainArgs._fields_)
 
 
 class AcoTspArgs(C.Structure):
@@ -356,6 +363,9 @@ SYMBOLS = {
     "rl4co_nargnn_train_forward": (C.c_int, [C.POINTER(NargnnTrainArgs), _vp]),
     "rl4co_nargnn_train_backward": (C.c_int, [C.POINTER(NargnnTrainArgs), _vp]),
     "rl4co_nargnn_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rl4co_nargnn_depot_train_forward": (C.c_int, [C.POINTER(NargnnDepotTrainArgs), _vp]),
+    "rl4co_nargnn_depot_train_backward": (C.c_int, [C.POINTER(NargnnDepotTrainArgs), _vp]),
+    "rl4co_nargnn_depot_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "rl4co_select_start_nodes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "rl4co_augment_dihedral8_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_augment_symmetric_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp]),

@@ -1,17 +1,22 @@
-// nargnn_train.hip — the GNN stack of DeepACO's TSP heatmap encoder in TRAIN mode and its backward (the reference's
-// models/nn/graph/gnn.py:45-61 with batch norms on batch statistics) for gfx950, fp32. The math and the C contract are in
-// include/rl4co_amd.h (rl4co_nargnn_train_args); the MFMA tile product and its operand convention are nargnn_shared.h's.
+// nargnn_train.hip — the GNN stack of DeepACO's heatmap encoder in TRAIN mode and its backward (the reference's
+// models/nn/graph/gnn.py:45-61 with batch norms on batch statistics) for gfx950, fp32, on two graphs: the regular k-nearest
+// graph of TSP (rl4co_nargnn_train_*) and the depot graph of CVRP, OP and PCTSP (rl4co_nargnn_depot_train_*). The math and
+// the C contract are in include/rl4co_amd.h (rl4co_nargnn_train_args, rl4co_nargnn_depot_train_args); the MFMA tile product
+// and its operand convention are nargnn_shared.h's. What a graph is to these kernels -- the edge rows per instance, a row's
+// two ends, a node's outgoing rows and its degree -- is stated once per graph (`Regular`, `Depot` below); k_check, the two
+// edge MFMA passes and the two node passes are templated on it, everything else does not know the graph.
 //
 // Nothing stays on chip across a layer: a batch norm needs every row of the batch before any row can go on. The work is
-// split by ROWS (16-row tiles of the flat [B N] node rows and [B N K] edge rows, rows of 64 floats), never by instance,
-// and every batch-wide reduction crosses a launch boundary: a pass writes one partial per workgroup, a one-workgroup
-// finalize launch combines the partials in ascending order, the next pass applies the result. No grid barrier, no spin,
-// no floating-point atomic; every sum has a fixed order, so every output is bit-identical run to run.
+// split by ROWS (16-row tiles of the flat [B N] node rows and [B N K] edge rows -- [B (N - 1)(K + 2)] on the depot graph --
+// rows of 64 floats), never by instance, and every batch-wide reduction crosses a launch boundary: a pass writes one
+// partial per workgroup, a one-workgroup finalize launch combines the partials in ascending order, the next pass applies
+// the result. No grid barrier, no spin, no floating-point atomic; every sum has a fixed order, so every output is
+// bit-identical run to run.
 //
 // A workgroup is four waves; rows R are cut into P(R) = min(ceil(R / 64), 1024) workgroups and each of the 4 P waves takes
 // a contiguous run of ceil(ceil(R / 16) / 4 P) tiles. Forward, per layer (6 launches):
 //   lin_fwd<node>   x1, x2, x3, x4 = v_lin1 .. v_lin4 (x0)                       MFMA, grid.y = matrix; x2 is saved
-//   vert_pre        pre_v[i] = x1[i] + (sum_k sigmoid(w0[i,k]) x2[j]) / K         wave = node, lane = channel
+//   vert_pre        pre_v[i] = x1[i] + (sum_k sigmoid(w0[i,k]) x2[j]) / deg(i)    wave = node, lane = channel
 //   lin_fwd<edge>   pre_e[e] = (e_lin(w0)[e] + x3[i]) + x4[j]                      MFMA
 //   row_stats       per workgroup (count, mean, M2) of pre_v and of pre_e, the mean and the M2 about it taken in two
 //                   sweeps of the wave's own rows (the second one hits the cache), summed in float64
@@ -21,13 +26,16 @@
 //   bwd_reduce      per workgroup sum gy, sum gy u^ on both sides, gy = g silu'(y)
 //   bwd_finalize    d beta, d gamma and the two means
 //   bwd_gu          gu = gamma r (gy - mean gy - u^ mean(gy u^)) -> gu_v (node plane 0) and gu_e
-//   lin_bwd<edge>   gw0 = gw + gu_e W_e + gu_v[i] x2[j] s (1 - s) / K; partials of dW_e = gu_e^T w0 and db_e       MFMA
-//   node_bwd        gx2[j], gx4[j] over j's incoming edges (the CSR, ascending), gx3[i] over i's own K rows    wave = node
+//   lin_bwd<edge>   gw0 = gw + gu_e W_e + gu_v[i] x2[j] s (1 - s) / deg(i); partials of dW_e = gu_e^T w0 and db_e  MFMA
+//   node_bwd        gx2[j], gx4[j] over j's incoming edges (the CSR, ascending), gx3[i] over i's own rows      wave = node
 //   lin_bwd<node>   four launches, m = 1 .. 4: gx0 (+)= gx_m W_m; partials of dW_m = gx_m^T x0 and db_m              MFMA
 //   dw_finalize     the five matrices' partials, ascending
 // The running gradients gx and gw live in one buffer each: lin_bwd reads and writes an element in the same lane.
 // The first launch of either call checks `neighbors` and the CSR and raises a flag in the workspace head; every other kernel
 // returns at once when it is set, so nothing is read through a bad index.
+// The depot's sums (its mean, its gx3 and its incoming sums are N - 1 terms long, every other node's K + 1 or so) are taken
+// as eight interleaved partial sums, term t into partial t mod 8, combined as ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)): eight
+// loads in flight instead of one, and an order that depends on nothing but the node.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,12 +68,12 @@ struct Layout {
   int Pv, Pe;
   int64_t xs, ws, pv, x2, pe, t, gx, gue, gw, part, dw, means, total;
 };
-inline Layout layout(int64_t B, int64_t N, int64_t K, int64_t L) {
+inline Layout layout(int64_t n_v, int64_t n_e, int64_t L) {
   Layout y;
-  y.nv = B * N * kD;
-  y.ne = y.nv * K;
-  y.Pv = groups_of(B * N);
-  y.Pe = groups_of(B * N * K);
+  y.nv = n_v * kD;
+  y.ne = n_e * kD;
+  y.Pv = groups_of(n_v);
+  y.Pe = groups_of(n_e);
   const int64_t Lm = L > 1 ? L - 1 : 0;
   int64_t at = kHead;
   const auto take = [&](int64_t n) { const int64_t o = at; at += n; return o; };
@@ -85,21 +93,148 @@ inline Layout layout(int64_t B, int64_t N, int64_t K, int64_t L) {
   return y;
 }
 
+// ---- the two graphs -------------------------------------------------------------------------------------------------------------
+// A graph says: the edge rows and the entries of `neighbors` per instance, the smallest neighbour index, the two ends of an
+// edge row and the out-degree of its source (`ends`), a node (`node`), that node's t-th outgoing row and its target (`out`),
+// and the source of one of its INCOMING rows with that source's out-degree (`source`). Nothing is stored: all are closed
+// forms of (row, neighbors).
+struct Regular {  // TSP: node i's K rows are i K .. i K + K - 1, row e is e / K -> neighbors[e]
+  static constexpr bool kDepot = false;
+  static constexpr int kMinN = 2, kFirst = 0;
+  int N, K;
+  __host__ __device__ Regular(int n, int k) : N(n), K(k) {}
+  __host__ __device__ int64_t rows() const { return (int64_t)N * K; }
+  __host__ __device__ int64_t lists() const { return (int64_t)N * K; }
+  struct Node {
+    int64_t v, base;
+    int deg;
+    bool depot;
+  };
+  __device__ void ends(int64_t e, const int32_t* nbr, int64_t& i, int64_t& j, float& deg) const {
+    i = e / K;
+    j = (i / N) * N + nbr[e];
+    deg = (float)K;
+  }
+  __device__ Node node(int64_t v) const { return Node{v, (v / N) * N, K, false}; }
+  __device__ void out(const Node& nd, int t, const int32_t* nbr, int64_t& e, int64_t& j) const {
+    e = nd.v * K + t;
+    j = nd.base + nbr[e];
+  }
+  __device__ void source(const Node&, int64_t e, int64_t& i, float& deg) const {
+    i = e / K;
+    deg = (float)K;
+  }
+};
+// CVRP, OP, PCTSP (CVRPEdgeEmbedding): C = N - 1 customers, E = C (K + 2) rows per instance in the reference's order:
+// [0, C K) the kNN rows by source, row (i - 1) K + k is i -> neighbors[i - 1, k]; [C K, C K + C) i -> 0; then 0 -> i.
+// A customer's out-degree is K + 1 (its K rows and its i -> 0 row), the depot's is C.
+struct Depot {
+  static constexpr bool kDepot = true;
+  static constexpr int kMinN = 3, kFirst = 1;  // the depot is nobody's kNN neighbour
+  int N, K, C, CK, E;
+  __host__ __device__ Depot(int n, int k) : N(n), K(k), C(n - 1), CK((n - 1) * k), E((n - 1) * (k + 2)) {}
+  __host__ __device__ int64_t rows() const { return E; }
+  __host__ __device__ int64_t lists() const { return CK; }
+  struct Node {
+    int64_t base, row0, list0;  // the instance's first node, first edge row and first entry of `neighbors`
+    int li, deg;
+    bool depot;
+  };
+  __device__ void ends(int64_t e, const int32_t* nbr, int64_t& i, int64_t& j, float& deg) const {
+    const int b = (int)e / E, r = (int)e - b * E;  // (e < 2^24)
+    const int64_t base = (int64_t)b * N;
+    if (r < CK) {
+      i = base + 1 + r / K;
+      j = base + nbr[(int64_t)b * CK + r];
+      deg = (float)(K + 1);
+    } else if (r < CK + C) {
+      i = base + 1 + (r - CK);
+      j = base;
+      deg = (float)(K + 1);
+    } else {
+      i = base;
+      j = base + 1 + (r - CK - C);
+      deg = (float)C;
+    }
+  }
+  __device__ Node node(int64_t v) const {
+    const int64_t b = v / N;
+    const int li = (int)(v - b * N);
+    return Node{b * N, b * E, b * CK, li, li == 0 ? C : K + 1, li == 0};
+  }
+  __device__ void out(const Node& nd, int t, const int32_t* nbr, int64_t& e, int64_t& j) const {
+    if (nd.depot) {
+      e = nd.row0 + CK + C + t;
+      j = nd.base + 1 + t;
+    } else if (t < K) {
+      const int r = (nd.li - 1) * K + t;
+      e = nd.row0 + r;
+      j = nd.base + nbr[nd.list0 + r];
+    } else {
+      e = nd.row0 + CK + (nd.li - 1);
+      j = nd.base;
+    }
+  }
+  __device__ void source(const Node& nd, int64_t e, int64_t& i, float& deg) const {  // e: a row of nd's instance
+    const int r = (int)(e - nd.row0);
+    i = r < CK ? nd.base + 1 + r / K : r < CK + C ? nd.base + 1 + (r - CK) : nd.base;
+    deg = r < CK + C ? (float)(K + 1) : (float)C;
+  }
+};
+
+// term(0) + .. + term(n - 1) as eight interleaved partial sums (the depot's long sums)
+template <class T, class F>
+__device__ inline T sum8(int n, F term) {
+  T p[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) p[q] = T{};
+  int t = 0;
+  for (; t + 8 <= n; t += 8) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) p[q] += term(t + q);
+  }
+#pragma unroll
+  for (int q = 0; q < 7; ++q)
+    if (t + q < n) p[q] += term(t + q);
+  return ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+}
+// the same sum for any node of graph G: in order, the depot's by sum8
+template <class T, class G, class F>
+__device__ inline T node_sum(bool depot, int n, F term) {
+  if (G::kDepot && depot) return sum8<T>(n, term);
+  T s{};
+  for (int t = 0; t < n; ++t) s += term(t);
+  return s;
+}
+// a node's two incoming sums, taken in one walk of its rows
+struct Incoming {
+  double g4;
+  float g2;
+  __device__ Incoming& operator+=(const Incoming& o) {
+    g4 += o.g4;
+    g2 += o.g2;
+    return *this;
+  }
+  friend __device__ Incoming operator+(Incoming a, const Incoming& o) { return a += o; }
+};
+
 // ---- the check ----------------------------------------------------------------------------------------------------------------
 struct CheckArgs {
   const int32_t *nbr, *ptr, *src;
-  int64_t n_v, n_e;
+  int64_t n_v, n_e, n_l;  // node rows, edge rows, entries of nbr
   int N, K;
   int* bad;
   int32_t* err;
 };
+template <class G>
 __global__ void __launch_bounds__(kT) k_check(const CheckArgs a) {
+  const G gr(a.N, a.K);
   const int64_t tid = (int64_t)blockIdx.x * kT + threadIdx.x, stride = (int64_t)gridDim.x * kT;
   const int lane = threadIdx.x & 63;
   bool bad = false;
-  for (int64_t e = tid; e < a.n_e; e += stride) {
+  for (int64_t e = tid; e < a.n_l; e += stride) {
     const int v = a.nbr[e];
-    bad |= v < 0 || v >= a.N;
+    bad |= v < G::kFirst || v >= a.N;
   }
   if (tid == 0) bad |= a.ptr[0] != 0 || (int64_t)a.ptr[a.n_v] != a.n_e;
   for (int64_t j = tid >> 6; j < a.n_v; j += stride >> 6) {
@@ -114,8 +249,10 @@ __global__ void __launch_bounds__(kT) k_check(const CheckArgs a) {
         bad = true;
         continue;
       }
-      const int v = a.nbr[e];
-      if (v < 0 || v >= a.N || (e / a.K / a.N) * a.N + v != j) bad = true;
+      int64_t i, jj;  // (a bad neighbour gives a wrong jj and nothing else: the loop above has raised the flag for it)
+      float deg;
+      gr.ends(e, a.nbr, i, jj, deg);
+      if (jj != j) bad = true;
       if (p > p0 && (int64_t)a.src[p - 1] >= e) bad = true;
     }
   }
@@ -150,9 +287,10 @@ struct LinFwdArgs {
   const int32_t* nbr;
   int N, K;
 };
-template <bool EDGE>
+template <bool EDGE, class G>
 __global__ void __launch_bounds__(kT) k_lin_fwd(const LinFwdArgs a) {
   if (*a.bad) return;
+  const G gr(a.N, a.K);
   const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const int m = EDGE ? 0 : blockIdx.y;
   const int64_t wg = (int64_t)blockIdx.x * kW + (threadIdx.x >> 6);
@@ -173,7 +311,9 @@ __global__ void __launch_bounds__(kT) k_lin_fwd(const LinFwdArgs a) {
       const int64_t n = 16 * t + 4 * g + r;
       if (n < a.rows) {
         if constexpr (EDGE) {
-          const int64_t i = n / a.K, j = (i / a.N) * a.N + a.nbr[n];
+          int64_t i, j;
+          float deg;
+          gr.ends(n, a.nbr, i, j, deg);
 #pragma unroll
           for (int ct = 0; ct < 4; ++ct) {
             const int col = 16 * ct + c;
@@ -202,15 +342,15 @@ struct LinBwdArgs {
   const int32_t* nbr;
   int N, K;
 };
-template <bool EDGE>
+template <bool EDGE, class G>
 __global__ void __launch_bounds__(kT) k_lin_bwd(const LinBwdArgs a) {
   __shared__ float sdw[kD * kD];
   __shared__ double sdb[kW][4][kD];
   if (*a.bad) return;
+  const G gr(a.N, a.K);
   const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const int w = threadIdx.x >> 6;
   const int64_t wg = (int64_t)blockIdx.x * kW + w;
-  const float count = (float)a.K;
   f32x4 dw[4][4];
   double db[4];  // (a bias ahead of a batch norm has a zero gradient: what is left is this sum's rounding)
 #pragma unroll
@@ -233,10 +373,8 @@ __global__ void __launch_bounds__(kT) k_lin_bwd(const LinBwdArgs a) {
         const int64_t n = 16 * t + 4 * g + r;
         if (n < a.rows) {
           int64_t i = 0, j = 0;
-          if constexpr (EDGE) {
-            i = n / a.K;
-            j = (i / a.N) * a.N + a.nbr[n];
-          }
+          float count = 1.0f;  // the out-degree of the row's source
+          if constexpr (EDGE) gr.ends(n, a.nbr, i, j, count);
 #pragma unroll
           for (int ct = 0; ct < 4; ++ct) {
             const int col = 16 * ct + c;
@@ -328,39 +466,52 @@ struct NodeArgs {
   int64_t n_v;
   int rpw, N, K;
 };
+template <class G>
 __global__ void __launch_bounds__(kT) k_vert_pre(const NodeArgs a) {
   if (*a.bad) return;
+  const G gr(a.N, a.K);
   const int lane = threadIdx.x & 63;
   const int64_t wg = (int64_t)blockIdx.x * kW + (threadIdx.x >> 6);
-  const float count = (float)a.K;
   const int64_t i1 = min(a.n_v, (wg + 1) * a.rpw);
   for (int64_t i = wg * a.rpw; i < i1; ++i) {
-    const int64_t base = (i / a.N) * a.N;
-    float s = 0.0f;
-    for (int k = 0; k < a.K; ++k) {
-      const int64_t e = i * a.K + k;
-      s += sigm(a.W0[e * kD + lane]) * a.X2[(base + a.nbr[e]) * kD + lane];
-    }
-    a.PV[i * kD + lane] = a.X1[i * kD + lane] + s / count;
+    const typename G::Node nd = gr.node(i);
+    const float s = node_sum<float, G>(nd.depot, nd.deg, [&](int t) {
+      int64_t e, j;
+      gr.out(nd, t, a.nbr, e, j);
+      return sigm(a.W0[e * kD + lane]) * a.X2[j * kD + lane];
+    });
+    a.PV[i * kD + lane] = a.X1[i * kD + lane] + s / (float)nd.deg;
   }
 }
+template <class G>
 __global__ void __launch_bounds__(kT) k_node_bwd(const NodeArgs a) {
   if (*a.bad) return;
+  const G gr(a.N, a.K);
   const int lane = threadIdx.x & 63;
   const int64_t wg = (int64_t)blockIdx.x * kW + (threadIdx.x >> 6);
   const float count = (float)a.K;
   const int64_t j1 = min(a.n_v, (wg + 1) * a.rpw);
   for (int64_t j = wg * a.rpw; j < j1; ++j) {
-    double s3 = 0.0, s4 = 0.0;  // (summed again over every node into a bias gradient that is zero in exact arithmetic)
-    float s2 = 0.0f;
-    for (int k = 0; k < a.K; ++k) s3 += (double)a.GUE[(j * a.K + k) * kD + lane];
-    const int p1 = a.ptr[j + 1];
-    for (int p = a.ptr[j]; p < p1; ++p) {  // an in-degree of 0: both sums stay 0
-      const int64_t e = a.src[p];
-      s4 += (double)a.GUE[e * kD + lane];
-      s2 += sigm(a.W0[e * kD + lane]) * a.GUV[(e / a.K) * kD + lane];
-    }
-    a.G2[j * kD + lane] = s2 / count;
+    const typename G::Node nd = gr.node(j);
+    // (s3 and s4 are summed again over every node into a bias gradient that is zero in exact arithmetic)
+    const double s3 = node_sum<double, G>(nd.depot, nd.deg, [&](int t) {
+      int64_t e, jj;
+      gr.out(nd, t, a.nbr, e, jj);
+      return (double)a.GUE[e * kD + lane];
+    });
+    const int p0 = a.ptr[j], n_in = a.ptr[j + 1] - p0;  // an in-degree of 0: both sums stay 0
+    // where the sources' out-degrees differ each term of gx2 is divided by its own, otherwise the sum by the one there is
+    const Incoming in = node_sum<Incoming, G>(nd.depot, n_in, [&](int t) {
+      const int64_t e = a.src[p0 + t];
+      int64_t i;
+      float deg;
+      gr.source(nd, e, i, deg);
+      const float v = sigm(a.W0[e * kD + lane]) * a.GUV[i * kD + lane];
+      return Incoming{(double)a.GUE[e * kD + lane], G::kDepot ? v / deg : v};
+    });
+    const float s2 = in.g2;
+    const double s4 = in.g4;
+    a.G2[j * kD + lane] = G::kDepot ? s2 : s2 / count;
     a.G3[j * kD + lane] = (float)s3;
     a.G4[j * kD + lane] = (float)s4;
   }
@@ -606,20 +757,29 @@ __global__ void __launch_bounds__(kT) k_bwd_gu(const RowArgs a) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-int require_common(const rl4co_nargnn_train_args& a) {
+template <class G>
+int64_t workspace_bytes(int B, int N, int K, int L) {
+  if (B < 1 || N < G::kMinN || N > 1024 || K < 1 || K > 64 || K > N - G::kMinN + 1 || L < 1 || L > (1 << 20)) return 0;
+  const int64_t n_e = B * G(N, K).rows();
+  if (n_e > (1 << 24)) return 0;
+  return layout((int64_t)B * N, n_e, L).total * 4;
+}
+
+template <class G, class A>
+int require_common(const A& a) {
   RL4CO_REQUIRE(a.D == kD);
   RL4CO_REQUIRE(a.B >= 1);
-  RL4CO_REQUIRE(a.N >= 2 && a.N <= 1024);
-  RL4CO_REQUIRE(a.K >= 1 && a.K <= 64 && a.K <= a.N - 1);
+  RL4CO_REQUIRE(a.N >= G::kMinN && a.N <= 1024);
+  RL4CO_REQUIRE(a.K >= 1 && a.K <= 64 && a.K <= a.N - G::kMinN + 1);  // (the depot has no kNN row)
   RL4CO_REQUIRE(a.L >= 1 && a.L <= (1 << 20));
-  RL4CO_REQUIRE((int64_t)a.B * a.N * a.K <= (1 << 24));  // row counts are exact in fp32, row indices fit an int32
+  RL4CO_REQUIRE(a.B * G(a.N, a.K).rows() <= (1 << 24));  // row counts are exact in fp32, row indices fit an int32
   RL4CO_REQUIRE(a.reserved0 == 0 && a.reserved1 == 0);
   RL4CO_REQUIRE(a.eps > 0.0f);
   RL4CO_REQUIRE(a.neighbors != nullptr && a.csr_ptr != nullptr && a.csr_src != nullptr);
   RL4CO_REQUIRE(a.x_in != nullptr && a.w_in != nullptr);
   RL4CO_REQUIRE(a.lin_w != nullptr && a.lin_b != nullptr && a.bn_w != nullptr && a.bn_b != nullptr);
   RL4CO_REQUIRE(a.workspace != nullptr && a.stats != nullptr && a.err != nullptr);
-  RL4CO_REQUIRE(a.workspace_bytes >= rl4co_nargnn_train_workspace_bytes(a.B, a.N, a.K, a.L));
+  RL4CO_REQUIRE(a.workspace_bytes >= workspace_bytes<G>(a.B, a.N, a.K, a.L));
   const uintptr_t all = reinterpret_cast<uintptr_t>(a.x_in) | reinterpret_cast<uintptr_t>(a.w_in) |
                         reinterpret_cast<uintptr_t>(a.lin_w) | reinterpret_cast<uintptr_t>(a.bn_w) |
                         reinterpret_cast<uintptr_t>(a.bn_b) | reinterpret_cast<uintptr_t>(a.workspace) |
@@ -629,12 +789,14 @@ int require_common(const rl4co_nargnn_train_args& a) {
 }
 
 // the flag is cleared and the lists are checked before any other launch of the call
-int launch_check(const rl4co_nargnn_train_args& a, hipStream_t s) {
+template <class G, class A>
+int launch_check(const A& a, hipStream_t s) {
   RL4CO_HIP_TRY(hipMemsetAsync(a.workspace, 0, kHead * 4, s));
-  CheckArgs c{a.neighbors, a.csr_ptr, a.csr_src, (int64_t)a.B * a.N, (int64_t)a.B * a.N * a.K, a.N, a.K,
+  const G gr(a.N, a.K);
+  CheckArgs c{a.neighbors, a.csr_ptr, a.csr_src, (int64_t)a.B * a.N, a.B * gr.rows(), a.B * gr.lists(), a.N, a.K,
               reinterpret_cast<int*>(a.workspace), a.err};
   const int grid = (int)std::min<int64_t>((c.n_e + kT - 1) / kT, kMaxGroups);
-  hipLaunchKernelGGL(k_check, dim3(grid), dim3(kT), 0, s, c);
+  hipLaunchKernelGGL(k_check<G>, dim3(grid), dim3(kT), 0, s, c);
   RL4CO_HIP_TRY(hipGetLastError());
   return RL4CO_OK;
 }
@@ -644,33 +806,27 @@ struct Shape {
   int64_t n_v, n_e;
   int rpw_v, rpw_e;  // rows per wave (16 tiles_per_wave)
 };
-Shape shape_of(const rl4co_nargnn_train_args& a) {
+template <class G, class A>
+Shape shape_of(const A& a) {
   Shape h;
-  h.y = layout(a.B, a.N, a.K, a.L);
   h.n_v = (int64_t)a.B * a.N;
-  h.n_e = h.n_v * a.K;
+  h.n_e = a.B * G(a.N, a.K).rows();
+  h.y = layout(h.n_v, h.n_e, a.L);
   h.rpw_v = 16 * tiles_per_wave(h.n_v, h.y.Pv);
   h.rpw_e = 16 * tiles_per_wave(h.n_e, h.y.Pe);
   return h;
 }
 
-}  // namespace
-
-extern "C" int64_t rl4co_nargnn_train_workspace_bytes(int B, int N, int K, int L) {
-  if (B < 1 || N < 2 || N > 1024 || K < 1 || K > 64 || K > N - 1 || L < 1 || L > (1 << 20)) return 0;
-  if ((int64_t)B * N * K > (1 << 24)) return 0;
-  return layout(B, N, K, L).total * 4;
-}
-
-extern "C" int rl4co_nargnn_train_forward(const rl4co_nargnn_train_args* args, void* stream) {
+template <class G, class A>
+int forward(const A* args, void* stream) {
   RL4CO_REQUIRE(args != nullptr);
-  const rl4co_nargnn_train_args& a = *args;
-  if (const int rc = require_common(a)) return rc;
+  const A& a = *args;
+  if (const int rc = require_common<G>(a)) return rc;
   RL4CO_REQUIRE(a.x_out != nullptr && a.w_out != nullptr);
   RL4CO_REQUIRE(((reinterpret_cast<uintptr_t>(a.x_out) | reinterpret_cast<uintptr_t>(a.w_out)) & 15) == 0);
   hipStream_t s = rl4co::as_stream(stream);
-  if (const int rc = launch_check(a, s)) return rc;
-  const Shape h = shape_of(a);
+  if (const int rc = launch_check<G>(a, s)) return rc;
+  const Shape h = shape_of<G>(a);
   const Layout& y = h.y;
   float* ws = a.workspace;
   const int* bad = reinterpret_cast<const int*>(ws);
@@ -688,14 +844,14 @@ extern "C" int rl4co_nargnn_train_forward(const rl4co_nargnn_train_args* args, v
     float* stat = a.stats + (int64_t)l * 6 * kD;
 
     LinFwdArgs nf{bad, x0, LW, LB, {T, x2, T + 2 * y.nv, T + 3 * y.nv}, h.n_v, h.rpw_v / 16, nullptr, nullptr, a.neighbors, a.N, a.K};
-    hipLaunchKernelGGL(k_lin_fwd<false>, dim3(y.Pv, 4), dim3(kT), 0, s, nf);
+    hipLaunchKernelGGL((k_lin_fwd<false, G>), dim3(y.Pv, 4), dim3(kT), 0, s, nf);
     NodeArgs na{};
     na.bad = bad, na.nbr = a.neighbors, na.W0 = w0, na.X1 = T, na.X2 = x2, na.PV = pv;
     na.n_v = h.n_v, na.rpw = h.rpw_v, na.N = a.N, na.K = a.K;
-    hipLaunchKernelGGL(k_vert_pre, dim3(y.Pv), dim3(kT), 0, s, na);
+    hipLaunchKernelGGL(k_vert_pre<G>, dim3(y.Pv), dim3(kT), 0, s, na);
     LinFwdArgs ef{bad, w0, LW + 4 * kD * kD, LB + 4 * kD, {pe, nullptr, nullptr, nullptr}, h.n_e, h.rpw_e / 16,
                   T + 2 * y.nv, T + 3 * y.nv, a.neighbors, a.N, a.K};
-    hipLaunchKernelGGL(k_lin_fwd<true>, dim3(y.Pe), dim3(kT), 0, s, ef);
+    hipLaunchKernelGGL((k_lin_fwd<true, G>), dim3(y.Pe), dim3(kT), 0, s, ef);
 
     float* part_v = ws + y.part;
     float* part_e = part_v + (int64_t)192 * y.Pv;
@@ -714,18 +870,19 @@ extern "C" int rl4co_nargnn_train_forward(const rl4co_nargnn_train_args* args, v
   return RL4CO_OK;
 }
 
-extern "C" int rl4co_nargnn_train_backward(const rl4co_nargnn_train_args* args, void* stream) {
+template <class G, class A>
+int backward(const A* args, void* stream) {
   RL4CO_REQUIRE(args != nullptr);
-  const rl4co_nargnn_train_args& a = *args;
-  if (const int rc = require_common(a)) return rc;
+  const A& a = *args;
+  if (const int rc = require_common<G>(a)) return rc;
   RL4CO_REQUIRE(a.grad_x_out != nullptr && a.grad_w_out != nullptr && a.grad_x_in != nullptr && a.grad_w_in != nullptr);
   RL4CO_REQUIRE(a.grad_lin_w != nullptr && a.grad_lin_b != nullptr && a.grad_bn_w != nullptr && a.grad_bn_b != nullptr);
   const uintptr_t all = reinterpret_cast<uintptr_t>(a.grad_x_out) | reinterpret_cast<uintptr_t>(a.grad_w_out) |
                         reinterpret_cast<uintptr_t>(a.grad_x_in) | reinterpret_cast<uintptr_t>(a.grad_w_in);
   RL4CO_REQUIRE((all & 15) == 0);
   hipStream_t s = rl4co::as_stream(stream);
-  if (const int rc = launch_check(a, s)) return rc;
-  const Shape h = shape_of(a);
+  if (const int rc = launch_check<G>(a, s)) return rc;
+  const Shape h = shape_of<G>(a);
   const Layout& y = h.y;
   float* ws = a.workspace;
   const int* bad = reinterpret_cast<const int*>(ws);
@@ -765,20 +922,40 @@ extern "C" int rl4co_nargnn_train_backward(const rl4co_nargnn_train_args* args, 
 
     LinBwdArgs eb{bad, GUE, w0, LW + 4 * kD * kD, gw, gw0, dwp + (int64_t)4 * y.Pv * kPartDw, h.n_e, h.rpw_e / 16,
                   T, x2, a.neighbors, a.N, a.K};
-    hipLaunchKernelGGL(k_lin_bwd<true>, dim3(y.Pe), dim3(kT), 0, s, eb);
+    hipLaunchKernelGGL((k_lin_bwd<true, G>), dim3(y.Pe), dim3(kT), 0, s, eb);
     NodeArgs na{};
     na.bad = bad, na.nbr = a.neighbors, na.ptr = a.csr_ptr, na.src = a.csr_src, na.W0 = w0, na.GUE = GUE, na.GUV = T;
     na.G2 = T + y.nv, na.G3 = T + 2 * y.nv, na.G4 = T + 3 * y.nv;
     na.n_v = h.n_v, na.rpw = h.rpw_v, na.N = a.N, na.K = a.K;
-    hipLaunchKernelGGL(k_node_bwd, dim3(y.Pv), dim3(kT), 0, s, na);
+    hipLaunchKernelGGL(k_node_bwd<G>, dim3(y.Pv), dim3(kT), 0, s, na);
     for (int m = 0; m < 4; ++m) {
       LinBwdArgs nb{bad, T + (int64_t)m * y.nv, x0, LW + m * kD * kD, m == 0 ? gx : gx0, gx0, dwp + (int64_t)m * y.Pv * kPartDw,
                     h.n_v, h.rpw_v / 16, nullptr, nullptr, a.neighbors, a.N, a.K};
-      hipLaunchKernelGGL(k_lin_bwd<false>, dim3(y.Pv), dim3(kT), 0, s, nb);
+      hipLaunchKernelGGL((k_lin_bwd<false, G>), dim3(y.Pv), dim3(kT), 0, s, nb);
     }
     DwFinalArgs df{bad, dwp, y.Pv, y.Pe, a.grad_lin_w + (int64_t)l * 5 * kD * kD, a.grad_lin_b + (int64_t)l * 5 * kD};
     hipLaunchKernelGGL(k_dw_finalize, dim3((kPartDw + kT - 1) / kT, 5), dim3(kT), 0, s, df);
     RL4CO_HIP_TRY(hipGetLastError());
   }
   return RL4CO_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t rl4co_nargnn_train_workspace_bytes(int B, int N, int K, int L) { return workspace_bytes<Regular>(B, N, K, L); }
+extern "C" int rl4co_nargnn_train_forward(const rl4co_nargnn_train_args* args, void* stream) {
+  return forward<Regular>(args, stream);
+}
+extern "C" int rl4co_nargnn_train_backward(const rl4co_nargnn_train_args* args, void* stream) {
+  return backward<Regular>(args, stream);
+}
+
+extern "C" int64_t rl4co_nargnn_depot_train_workspace_bytes(int B, int N, int K, int L) {
+  return workspace_bytes<Depot>(B, N, K, L);
+}
+extern "C" int rl4co_nargnn_depot_train_forward(const rl4co_nargnn_depot_train_args* args, void* stream) {
+  return forward<Depot>(args, stream);
+}
+extern "C" int rl4co_nargnn_depot_train_backward(const rl4co_nargnn_depot_train_args* args, void* stream) {
+  return backward<Depot>(args, stream);
 }

@@ -786,30 +786,61 @@ def incoming_csr(neighbors: Tensor) -> tuple[Tensor, Tensor]:
     return ptr.to(torch.int32), src.contiguous()
 
 
-def _nargnn_train_args(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps):
-    b, n, k = neighbors.shape
+def depot_incoming_csr(neighbors: Tensor) -> tuple[Tensor, Tensor]:
+    """:func:`incoming_csr` over the depot graph's rows: ``neighbors`` [B, C, K] (values in 1 .. N - 1, N = C + 1) gives
+    E = C (K + 2) edge rows per instance in the reference's order -- the kNN rows by source, every ``i -> 0``, every
+    ``0 -> i`` -- and ``(csr_ptr [B N + 1] int32, csr_src [B E] int32)`` lists, ascending, the rows whose target is each
+    global node. A stable sort of the closed-form targets keeps the rows ascending inside a node's run."""
+    b, c, k = neighbors.shape
+    n = c + 1
+    dev = neighbors.device
+    zero = torch.zeros(b, c, dtype=torch.int64, device=dev)
+    cust = torch.arange(1, n, dtype=torch.int64, device=dev).expand(b, c)
+    local = torch.cat((neighbors.to(torch.int64).reshape(b, c * k), zero, cust), 1)
+    target = (local + torch.arange(b, device=dev).view(b, 1) * n).reshape(-1)
+    src = torch.sort(target, stable=True).indices.to(torch.int32)
+    counts = torch.bincount(target.clamp(0, b * n - 1), minlength=b * n)  # (clamped for the count alone, as above)
+    ptr = torch.zeros(b * n + 1, dtype=torch.int64, device=dev)
+    ptr[1:] = counts.cumsum(0)
+    return ptr.to(torch.int32), src.contiguous()
+
+
+# graph -> (symbol stem, args struct, N from neighbors.shape[1], smallest N, edge rows per instance, the served range in words)
+_NARGNN_TRAIN_GRAPHS = {
+    "regular": ("rl4co_nargnn_train", _lib.NargnnTrainArgs, lambda m: m, 2, lambda n, k: n * k,
+                "B >= 1, 2 <= N <= 1024 and 1 <= K <= min(N - 1, 64)", "B N K <= 2^24"),
+    "depot": ("rl4co_nargnn_depot_train", _lib.NargnnDepotTrainArgs, lambda m: m + 1, 3, lambda n, k: (n - 1) * (k + 2),
+              "B >= 1, 3 <= N <= 1024 and 1 <= K <= min(N - 2, 64)", "B (N - 1)(K + 2) <= 2^24"),
+}
+
+
+def _nargnn_train_args(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps, graph="regular"):
+    stem, struct, nodes_of, min_n, rows_of, served, _ = _NARGNN_TRAIN_GRAPHS[graph]
+    b, m, k = neighbors.shape
+    n = nodes_of(m)
+    e = rows_of(n, k)  # edge rows per instance
     d = x_in.shape[-1]
     if d != 64:
-        raise NotImplementedError(f"nargnn_train serves embed_dim = 64 only, got {d}")
-    if b < 1 or not 2 <= n <= 1024 or not 1 <= k <= min(n - 1, 64):
-        raise NotImplementedError(f"nargnn_train serves B >= 1, 2 <= N <= 1024 and 1 <= K <= min(N - 1, 64), got "
-                                  f"B = {b}, N = {n}, K = {k}")
+        raise NotImplementedError(f"{stem[6:]} serves embed_dim = 64 only, got {d}")
+    if b < 1 or not min_n <= n <= 1024 or not 1 <= k <= min(n - min_n + 1, 64):
+        raise NotImplementedError(f"{stem[6:]} serves {served}, got B = {b}, N = {n}, K = {k}")
     layers = 0 if lin_w is None else lin_w.shape[0]
     if layers < 1:
-        raise ValueError("nargnn_train takes at least one layer (without layers the stack is the identity)")
-    want = dict(x_in=(x_in, (b, n, d)), w_in=(w_in, (b, n, k, d)), lin_w=(lin_w, (layers, 5, d, d)), lin_b=(lin_b, (layers, 5, d)),
+        raise ValueError(f"{stem[6:]} takes at least one layer (without layers the stack is the identity)")
+    w_shape = (b, n, k, d) if graph == "regular" else (b, e, d)
+    want = dict(x_in=(x_in, (b, n, d)), w_in=(w_in, w_shape), lin_w=(lin_w, (layers, 5, d, d)), lin_b=(lin_b, (layers, 5, d)),
                 bn_w=(bn_w, (layers, 2, d)), bn_b=(bn_b, (layers, 2, d)))
     for name, (t, shape) in want.items():
         if tuple(t.shape) != shape:
             raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
-    if tuple(csr_ptr.shape) != (b * n + 1,) or tuple(csr_src.shape) != (b * n * k,):
-        raise ValueError(f"csr_ptr must be [{b * n + 1}] and csr_src [{b * n * k}], got {tuple(csr_ptr.shape)} and "
+    if tuple(csr_ptr.shape) != (b * n + 1,) or tuple(csr_src.shape) != (b * e,):
+        raise ValueError(f"csr_ptr must be [{b * n + 1}] and csr_src [{b * e}], got {tuple(csr_ptr.shape)} and "
                          f"{tuple(csr_src.shape)}")
     for name, (t, _) in want.items():
         _dev(t, torch.float32, name)
     for name, t in (("neighbors", neighbors), ("csr_ptr", csr_ptr), ("csr_src", csr_src)):
         _dev(t, torch.int32, name)
-    a = _lib.NargnnTrainArgs()
+    a = struct()
     a.B, a.N, a.K, a.D, a.L, a.reserved0, a.eps, a.reserved1 = b, n, k, d, layers, 0, float(eps), 0
     values = dict(neighbors=neighbors, csr_ptr=csr_ptr, csr_src=csr_src, x_in=x_in, w_in=w_in, lin_w=lin_w, lin_b=lin_b, bn_w=bn_w,
                   bn_b=bn_b)
@@ -828,6 +859,45 @@ def _nargnn_train_launch(symbol: str, a, values: dict, err: Tensor | None, dev) 
         raise_if_error(word)
 
 
+def _nargnn_train_forward(graph, neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps, err):
+    stem, *_, rows = _NARGNN_TRAIN_GRAPHS[graph]
+    a, values, (b, n, k, d, layers) = _nargnn_train_args(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps, graph)
+    dev = x_in.device
+    nbytes = int(getattr(_lib.lib(), stem + "_workspace_bytes")(b, n, k, layers))
+    if nbytes <= 0:
+        raise NotImplementedError(f"{stem[6:]} does not serve B = {b}, N = {n}, K = {k}, L = {layers} ({rows})")
+    workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    x_out = torch.empty((b, n, d), dtype=torch.float32, device=dev)
+    w_out = torch.empty(tuple(w_in.shape), dtype=torch.float32, device=dev)
+    stats = torch.empty((layers, 6, d), dtype=torch.float32, device=dev)
+    a.workspace_bytes = nbytes
+    values.update(workspace=workspace, x_out=x_out, w_out=w_out, stats=stats)
+    _nargnn_train_launch(stem + "_forward", a, values, err, dev)
+    return x_out, w_out, stats, workspace
+
+
+def _nargnn_train_backward(graph, neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, stats, workspace, grad_x_out,
+                           grad_w_out, eps, err) -> dict:
+    stem = _NARGNN_TRAIN_GRAPHS[graph][0]
+    a, values, (b, n, k, d, layers) = _nargnn_train_args(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps, graph)
+    dev = x_in.device
+    for name, t, shape in (("grad_x_out", grad_x_out, (b, n, d)), ("grad_w_out", grad_w_out, tuple(w_in.shape)),
+                           ("stats", stats, (layers, 6, d))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+        _dev(t, torch.float32, name)
+    nbytes = int(getattr(_lib.lib(), stem + "_workspace_bytes")(b, n, k, layers))
+    if _dev(workspace, torch.float32, "workspace").numel() * 4 < nbytes or nbytes <= 0:
+        raise ValueError(f"workspace must hold {nbytes} bytes, got {workspace.numel() * 4}")
+    grads = dict(x_in=torch.empty_like(x_in), w_in=torch.empty_like(w_in), lin_w=torch.empty_like(lin_w),
+                 lin_b=torch.empty_like(lin_b), bn_w=torch.empty_like(bn_w), bn_b=torch.empty_like(bn_b))
+    a.workspace_bytes = workspace.numel() * 4
+    values.update(workspace=workspace, stats=stats, grad_x_out=grad_x_out, grad_w_out=grad_w_out,
+                  **{"grad_" + key: t for key, t in grads.items()})
+    _nargnn_train_launch(stem + "_backward", a, values, err, dev)
+    return grads
+
+
 def nargnn_train_forward(neighbors: Tensor, csr_ptr: Tensor, csr_src: Tensor, x_in: Tensor, w_in: Tensor, *, lin_w: Tensor,
                          lin_b: Tensor, bn_w: Tensor, bn_b: Tensor, eps: float = 1e-5, err: Tensor | None = None):
     """The L-layer GNN stack of the TSP heatmap encoder on BATCH statistics (rl4co_nargnn_train_forward), fp32.
@@ -837,19 +907,7 @@ def nargnn_train_forward(neighbors: Tensor, csr_ptr: Tensor, csr_src: Tensor, x_
     (gamma / beta of v_bn, e_bn). Returns ``(x_out, w_out, stats [L, 6, 64], workspace)``; ``stats[l]`` = (mu_v, r_v, var_v,
     mu_e, r_e, var_e), the variances biased. ``workspace`` holds what :func:`nargnn_train_backward` reads. Without ``err``
     the error word is read back and a bad neighbour list or CSR raises; the outputs are then not returned."""
-    a, values, (b, n, k, d, layers) = _nargnn_train_args(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps)
-    dev = x_in.device
-    nbytes = nargnn_train_workspace_bytes(b, n, k, layers)
-    if nbytes <= 0:
-        raise NotImplementedError(f"nargnn_train does not serve B = {b}, N = {n}, K = {k}, L = {layers} (B N K <= 2^24)")
-    workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-    x_out = torch.empty((b, n, d), dtype=torch.float32, device=dev)
-    w_out = torch.empty((b, n, k, d), dtype=torch.float32, device=dev)
-    stats = torch.empty((layers, 6, d), dtype=torch.float32, device=dev)
-    a.workspace_bytes = nbytes
-    values.update(workspace=workspace, x_out=x_out, w_out=w_out, stats=stats)
-    _nargnn_train_launch("rl4co_nargnn_train_forward", a, values, err, dev)
-    return x_out, w_out, stats, workspace
+    return _nargnn_train_forward("regular", neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps, err)
 
 
 def nargnn_train_backward(neighbors: Tensor, csr_ptr: Tensor, csr_src: Tensor, x_in: Tensor, w_in: Tensor, *, lin_w: Tensor,
@@ -858,23 +916,34 @@ def nargnn_train_backward(neighbors: Tensor, csr_ptr: Tensor, csr_src: Tensor, x
     """The backward of :func:`nargnn_train_forward` (rl4co_nargnn_train_backward) given its inputs, ``stats`` and
     ``workspace`` and the gradients of its two outputs. Returns the gradients by name: ``x_in``, ``w_in``, ``lin_w``,
     ``lin_b``, ``bn_w``, ``bn_b``."""
-    a, values, (b, n, k, d, layers) = _nargnn_train_args(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps)
-    dev = x_in.device
-    for name, t, shape in (("grad_x_out", grad_x_out, (b, n, d)), ("grad_w_out", grad_w_out, (b, n, k, d)),
-                           ("stats", stats, (layers, 6, d))):
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
-        _dev(t, torch.float32, name)
-    nbytes = nargnn_train_workspace_bytes(b, n, k, layers)
-    if _dev(workspace, torch.float32, "workspace").numel() * 4 < nbytes or nbytes <= 0:
-        raise ValueError(f"workspace must hold {nbytes} bytes, got {workspace.numel() * 4}")
-    grads = dict(x_in=torch.empty_like(x_in), w_in=torch.empty_like(w_in), lin_w=torch.empty_like(lin_w),
-                 lin_b=torch.empty_like(lin_b), bn_w=torch.empty_like(bn_w), bn_b=torch.empty_like(bn_b))
-    a.workspace_bytes = workspace.numel() * 4
-    values.update(workspace=workspace, stats=stats, grad_x_out=grad_x_out, grad_w_out=grad_w_out,
-                  **{"grad_" + key: t for key, t in grads.items()})
-    _nargnn_train_launch("rl4co_nargnn_train_backward", a, values, err, dev)
-    return grads
+    return _nargnn_train_backward("regular", neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, stats, workspace,
+                                  grad_x_out, grad_w_out, eps, err)
+
+
+def nargnn_depot_train_workspace_bytes(b: int, n: int, k: int, layers: int) -> int:
+    """Bytes of workspace the train-mode GNN stack needs on the depot graph (N with the depot; the formula is in
+    include/rl4co_amd.h); 0 outside the served range."""
+    return int(_lib.lib().rl4co_nargnn_depot_train_workspace_bytes(int(b), int(n), int(k), int(layers)))
+
+
+def nargnn_depot_train_forward(neighbors: Tensor, csr_ptr: Tensor, csr_src: Tensor, x_in: Tensor, w_in: Tensor, *, lin_w: Tensor,
+                               lin_b: Tensor, bn_w: Tensor, bn_b: Tensor, eps: float = 1e-5, err: Tensor | None = None):
+    """:func:`nargnn_train_forward` on the depot graph of CVRP, OP and PCTSP (rl4co_nargnn_depot_train_forward).
+
+    ``neighbors`` [B, N - 1, K] int32 with values in 1 .. N - 1, ``(csr_ptr, csr_src)`` from :func:`depot_incoming_csr`,
+    ``x_in`` [B, N, 64] (node 0 the depot) and ``w_in`` [B, E, 64] over the E = (N - 1)(K + 2) edge rows in the reference's
+    order (the kNN rows by source, every ``i -> 0``, every ``0 -> i``); the parameters and the return value as there, ``w_out``
+    [B, E, 64]. A neighbour of 0 (the depot) is refused like one outside the instance."""
+    return _nargnn_train_forward("depot", neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, eps, err)
+
+
+def nargnn_depot_train_backward(neighbors: Tensor, csr_ptr: Tensor, csr_src: Tensor, x_in: Tensor, w_in: Tensor, *,
+                                lin_w: Tensor, lin_b: Tensor, bn_w: Tensor, bn_b: Tensor, stats: Tensor, workspace: Tensor,
+                                grad_x_out: Tensor, grad_w_out: Tensor, eps: float = 1e-5, err: Tensor | None = None) -> dict:
+    """The backward of :func:`nargnn_depot_train_forward` (rl4co_nargnn_depot_train_backward); see
+    :func:`nargnn_train_backward`."""
+    return _nargnn_train_backward("depot", neighbors, csr_ptr, csr_src, x_in, w_in, lin_w, lin_b, bn_w, bn_b, stats, workspace,
+                                  grad_x_out, grad_w_out, eps, err)
 
 
 # ---- the Ant System: one table of families, one launch path for the search, one for the backward ---------------------------

@@ -12,7 +12,8 @@ lists are the reference's own selection (distance matrix, ``+inf`` on the diagon
 sorted=False)``) taken for the whole batch on the device; the eval-mode batch norms are folded into a per-channel scale and
 shift (in float64, rounded once). Training, CPU tensors, other environments, activations, aggregations and widths are
 refused with ``NotImplementedError``: there is no torch fall-back. ``TrainableNARGNNEncoder`` is ``NARGNNEncoder`` that also
-trains (TSP): in ``.train()`` the GNN stack runs on batch statistics, forward and backward, on csrc/nargnn_train.hip."""
+trains (TSP): in ``.train()`` the GNN stack runs on batch statistics, forward and backward, on csrc/nargnn_train.hip;
+``TrainableNARGNNDepotEncoder`` is the same for ``NARGNNDepotEncoder`` (CVRP, OP, PCTSP) on that file's depot-graph kernels."""
 from __future__ import annotations
 
 from functools import partial
@@ -195,59 +196,130 @@ class NARGNNEncoder(nn.Module):
 
 
 class _GNNStackTrain(torch.autograd.Function):
-    """The whole L-layer GNN stack on batch statistics as ONE autograd node: ``rl4co_nargnn_train_forward`` and
-    ``rl4co_nargnn_train_backward`` (csrc/nargnn_train.hip). ``stats`` [L, 6, 64] comes out beside the two states for the
-    running statistics and carries no gradient."""
+    """The whole L-layer GNN stack on batch statistics as ONE autograd node over the forward and backward entry points of
+    csrc/nargnn_train.hip for ``graph`` (``"regular"``: ``rl4co_nargnn_train_*``, ``"depot"``:
+    ``rl4co_nargnn_depot_train_*``). ``stats`` [L, 6, 64] comes out beside the two states for the running statistics and
+    carries no gradient."""
+
+    KERNELS = {"regular": ("nargnn_train_forward", "nargnn_train_backward"),
+               "depot": ("nargnn_depot_train_forward", "nargnn_depot_train_backward")}
 
     @staticmethod
-    def forward(ctx, x_in, w_in, lin_w, lin_b, bn_w, bn_b, neighbors, csr_ptr, csr_src, eps):
+    def forward(ctx, x_in, w_in, lin_w, lin_b, bn_w, bn_b, neighbors, csr_ptr, csr_src, eps, graph="regular"):
         tensors = [t.detach().contiguous() for t in (x_in, w_in, lin_w, lin_b, bn_w, bn_b)]
         keys = dict(lin_w=tensors[2], lin_b=tensors[3], bn_w=tensors[4], bn_b=tensors[5], eps=eps)
-        x_out, w_out, stats, workspace = K.nargnn_train_forward(neighbors, csr_ptr, csr_src, tensors[0], tensors[1], **keys)
+        run = getattr(K, _GNNStackTrain.KERNELS[graph][0])
+        x_out, w_out, stats, workspace = run(neighbors, csr_ptr, csr_src, tensors[0], tensors[1], **keys)
         ctx.save_for_backward(*tensors, neighbors, csr_ptr, csr_src, stats, workspace)
-        ctx.eps = eps
+        ctx.eps, ctx.graph = eps, graph
         ctx.mark_non_differentiable(stats)
         return x_out, w_out, stats
 
     @staticmethod
     def backward(ctx, grad_x, grad_w, _grad_stats):
         x_in, w_in, lin_w, lin_b, bn_w, bn_b, neighbors, csr_ptr, csr_src, stats, workspace = ctx.saved_tensors
-        g = K.nargnn_train_backward(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w=lin_w, lin_b=lin_b, bn_w=bn_w, bn_b=bn_b,
-                                    stats=stats, workspace=workspace, grad_x_out=grad_x.contiguous(),
-                                    grad_w_out=grad_w.contiguous(), eps=ctx.eps)
-        return g["x_in"], g["w_in"], g["lin_w"], g["lin_b"], g["bn_w"], g["bn_b"], None, None, None, None
+        run = getattr(K, _GNNStackTrain.KERNELS[ctx.graph][1])
+        g = run(neighbors, csr_ptr, csr_src, x_in, w_in, lin_w=lin_w, lin_b=lin_b, bn_w=bn_w, bn_b=bn_b, stats=stats,
+                workspace=workspace, grad_x_out=grad_x.contiguous(), grad_w_out=grad_w.contiguous(), eps=ctx.eps)
+        return g["x_in"], g["w_in"], g["lin_w"], g["lin_b"], g["bn_w"], g["bn_b"], None, None, None, None, None
 
 
-class TrainableNARGNNEncoder(NARGNNEncoder):
+class _TrainsOnKernels:
+    """What the trainable encoders share, mixed in ahead of the inference class: the train-mode refusals, the stacking of
+    the per-layer parameters, the one-eps / one-momentum rule, the call of the stack, the running statistics' update and
+    the heatmap MLP. A subclass names its graph and its smallest instance and supplies ``forward`` and ``encode_train``."""
+
+    GRAPH = "regular"                          # _GNNStackTrain.KERNELS' key
+    TRAIN_KERNEL = "rl4co_nargnn_train_forward"
+    MIN_NODES = 2
+
+    def _train_refusals(self, locs: Tensor) -> tuple:
+        me = type(self).__name__
+        return (
+            (bool(self.custom), f"{me} serves its own sub-modules only, got a custom {', '.join(self.custom)}"),
+            (self.env_name not in self.ENVS, f"{me} serves the {' / '.join(self.ENVS)} environment only, got {self.env_name!r}"),
+            (self.act_fn != "silu", f"{me} serves act_fn='silu' only, got {self.act_fn!r}"),
+            (self.agg_fn != "mean", f"{me} serves agg_fn='mean' only, got {self.agg_fn!r}"),
+            (self.embed_dim != 64, f"{me} serves embed_dim=64 only, got {self.embed_dim}"),
+            (not locs.is_cuda, f"{me} runs inside the MI355X kernels ({self.TRAIN_KERNEL}) only: td['locs'] on "
+                               f"{locs.device}"),
+        )
+
+    def _check(self, locs: Tensor, *others: Tensor) -> None:
+        if not self.training:
+            return super()._check(locs)
+        me = type(self).__name__
+        for refused, why in self._train_refusals(locs):
+            if refused:
+                raise NotImplementedError(why)
+        dtypes = {p.dtype for p in self.parameters()} | {locs.dtype} | {t.dtype for t in others}
+        if dtypes != {torch.float32}:
+            raise NotImplementedError(f"{me} trains in fp32 only, got {sorted(str(d) for d in dtypes)}")
+        least = self.MIN_NODES
+        if locs.dim() != 3 or locs.shape[0] * locs.shape[1] < 2 or locs.shape[1] < least:
+            raise NotImplementedError(f"{me} needs B N >= 2 rows for a batch statistic and N >= {least} nodes for an edge, got "
+                                      f"td['locs'] {tuple(locs.shape)}")
+
+    def _stack_train(self, x: Tensor, w: Tensor, neighbors: Tensor, csr: tuple) -> tuple[Tensor, Tensor]:
+        """The GNN layers over the activated embeddings ``x`` [B, N, 64] and ``w`` (the graph's edge rows), on the kernels;
+        updates every batch norm's running statistics once. Without layers the stack is the identity."""
+        layers = list(self.graph_network.layers)
+        if not layers:
+            return x, w
+        bns = [bn.module for layer in layers for bn in (layer.v_bn, layer.e_bn)]
+        eps, momentum = bns[0].eps, bns[0].momentum
+        if momentum is None or any(bn.eps != eps or bn.momentum != momentum for bn in bns):
+            raise NotImplementedError(f"{type(self).__name__} serves one eps and one momentum for all batch norms")
+        lins = [[getattr(layer, n) for n in ("v_lin1", "v_lin2", "v_lin3", "v_lin4", "e_lin")] for layer in layers]
+        lin_w = torch.stack([torch.stack([m.weight for m in row], 0) for row in lins], 0)
+        lin_b = torch.stack([torch.stack([m.bias for m in row], 0) for row in lins], 0)
+        bn_w = torch.stack([bn.weight for bn in bns], 0).view(len(layers), 2, -1)
+        bn_b = torch.stack([bn.bias for bn in bns], 0).view(len(layers), 2, -1)
+        x, w, stats = _GNNStackTrain.apply(x, w, lin_w, lin_b, bn_w, bn_b, neighbors, *csr, eps, self.GRAPH)
+        self._update_running_statistics(bns, stats, x.shape[0] * x.shape[1], 0, momentum, edge_rows=w.numel() // w.shape[-1])
+        return x, w
+
+    def _edge_probabilities(self, w: Tensor) -> Tensor:
+        """The heatmap MLP over the edge rows: ``w`` [..., 64] -> probabilities [...] in float64."""
+        gen = self.heatmap_generator
+        h = w
+        for linear in gen.linears:
+            h = nn.functional.silu(linear(h))
+        # the tail behind the last product runs in float64 -- the bias, the sigmoid and, in the caller, the scatter and the
+        # log, a few numbers per edge row: the logits are rounded to fp32 once, and on the way back the output bias's
+        # gradient, ONE number that sums every edge row of the batch with terms that nearly cancel, is summed in float64
+        out = nn.functional.linear(h, gen.output.weight).double()
+        if gen.output.bias is not None:
+            out = out + gen.output.bias.double()
+        return torch.sigmoid(out)[..., 0]
+
+    @staticmethod
+    @torch.no_grad()
+    def _update_running_statistics(bns: list, stats: Tensor, node_rows: int, k: int, momentum: float,
+                                   edge_rows: int | None = None) -> None:
+        """``BatchNorm1d``'s own update from the batch's mean and BIASED variance: ``stats`` [L, 6, D] = (mu_v, r_v, var_v, mu_e,
+        r_e, var_e) per layer; the running variance takes the unbiased one, var n / (n - 1), n the rows of its side:
+        ``node_rows`` and ``edge_rows`` (``node_rows * k`` when not given)."""
+        flat = stats.view(-1, 3, stats.shape[-1])  # [2 L]: v_bn, e_bn per layer
+        rows = [node_rows, node_rows * k if edge_rows is None else edge_rows]
+        unbiased = flat[:, 2] * torch.tensor([rows[i % 2] / (rows[i % 2] - 1) for i in range(len(bns))],
+                                             dtype=stats.dtype, device=stats.device)[:, None]
+        tracked = [i for i, bn in enumerate(bns) if bn.track_running_stats and bn.running_mean is not None]
+        means, variances = [bns[i].running_mean for i in tracked], [bns[i].running_var for i in tracked]
+        torch._foreach_mul_(means, 1.0 - momentum)
+        torch._foreach_add_(means, [flat[i, 0] for i in tracked], alpha=momentum)
+        torch._foreach_mul_(variances, 1.0 - momentum)
+        torch._foreach_add_(variances, [unbiased[i] for i in tracked], alpha=momentum)
+        torch._foreach_add_([bns[i].num_batches_tracked for i in tracked], 1)
+
+
+class TrainableNARGNNEncoder(_TrainsOnKernels, NARGNNEncoder):
     """``NARGNNEncoder`` that also trains, for TSP: the same constructor and ``state_dict`` keys. In ``.eval()`` it IS the
     parent (one launch of ``rl4co_nargnn_heatmap``, no gradient). In ``.train()`` ``forward(td)`` returns ``(heatmap_logits
     [B, N, N], node_embed [B, N, 64])`` attached to autograd, the batch norms on BATCH statistics as the reference's train
     mode, and updates ``running_mean``, ``running_var`` and ``num_batches_tracked`` of all 2 L batch norms once. The L-layer
     GNN stack, forward and backward, runs on the kernels of csrc/nargnn_train.hip behind one autograd node; the neighbour
     selection, the incoming-edge CSR, the two embeddings and the heatmap MLP are torch."""
-
-    def _check(self, locs: Tensor) -> None:
-        if not self.training:
-            return super()._check(locs)
-        me = type(self).__name__
-        refusals = (
-            (bool(self.custom), f"{me} serves its own sub-modules only, got a custom {', '.join(self.custom)}"),
-            (self.env_name not in self.ENVS, f"{me} serves the tsp environment only, got {self.env_name!r}"),
-            (self.act_fn != "silu", f"{me} serves act_fn='silu' only, got {self.act_fn!r}"),
-            (self.agg_fn != "mean", f"{me} serves agg_fn='mean' only, got {self.agg_fn!r}"),
-            (self.embed_dim != 64, f"{me} serves embed_dim=64 only, got {self.embed_dim}"),
-            (not locs.is_cuda, f"{me} runs inside the MI355X kernels (rl4co_nargnn_train_forward) only: td['locs'] on "
-                               f"{locs.device}"),
-        )
-        for refused, why in refusals:
-            if refused:
-                raise NotImplementedError(why)
-        dtypes = {p.dtype for p in self.parameters()} | {locs.dtype}
-        if dtypes != {torch.float32}:
-            raise NotImplementedError(f"{me} trains in fp32 only, got {sorted(str(d) for d in dtypes)}")
-        if locs.dim() != 3 or locs.shape[0] * locs.shape[1] < 2 or locs.shape[1] < 2:
-            raise NotImplementedError(f"{me} needs B N >= 2 rows for a batch statistic and N >= 2 nodes for an edge, got "
-                                      f"td['locs'] {tuple(locs.shape)}")
 
     def forward(self, td):
         if not self.training:
@@ -264,45 +336,12 @@ class TrainableNARGNNEncoder(NARGNNEncoder):
         node_embed = self.init_embedding.init_embed(locs)
         x = nn.functional.silu(node_embed)
         w = nn.functional.silu(self.edge_embedding.edge_embed(cost[..., None]))
-        layers = list(self.graph_network.layers)
-        if layers:  # (without layers the stack is the identity)
-            bns = [bn.module for layer in layers for bn in (layer.v_bn, layer.e_bn)]
-            eps, momentum = bns[0].eps, bns[0].momentum
-            if momentum is None or any(bn.eps != eps or bn.momentum != momentum for bn in bns):
-                raise NotImplementedError(f"{type(self).__name__} serves one eps and one momentum for all batch norms")
-            lins = [[getattr(layer, n) for n in ("v_lin1", "v_lin2", "v_lin3", "v_lin4", "e_lin")] for layer in layers]
-            lin_w = torch.stack([torch.stack([m.weight for m in row], 0) for row in lins], 0)
-            lin_b = torch.stack([torch.stack([m.bias for m in row], 0) for row in lins], 0)
-            bn_w = torch.stack([bn.weight for bn in bns], 0).view(len(layers), 2, -1)
-            bn_b = torch.stack([bn.bias for bn in bns], 0).view(len(layers), 2, -1)
-            csr_ptr, csr_src = K.incoming_csr(neighbors)
-            x, w, stats = _GNNStackTrain.apply(x, w, lin_w, lin_b, bn_w, bn_b, neighbors, csr_ptr, csr_src, eps)
-            self._update_running_statistics(bns, stats, x.shape[0] * x.shape[1], neighbors.shape[2], momentum)
-        gen = self.heatmap_generator
-        h = w
-        for linear in gen.linears:
-            h = nn.functional.silu(linear(h))
-        prob = torch.sigmoid(gen.output(h))[..., 0]  # [B, N, K]
+        if len(self.graph_network.layers):
+            x, w = self._stack_train(x, w, neighbors, K.incoming_csr(neighbors))
+        prob = self._edge_probabilities(w)  # [B, N, K]
         heat = torch.zeros(locs.shape[0], locs.shape[1], locs.shape[1], dtype=prob.dtype, device=prob.device)
         heat = heat.scatter(2, neighbors.to(torch.int64), prob)
-        return torch.log(heat + SMALL_VALUE), node_embed
-
-    @staticmethod
-    @torch.no_grad()
-    def _update_running_statistics(bns: list, stats: Tensor, node_rows: int, k: int, momentum: float) -> None:
-        """``BatchNorm1d``'s own update from the batch's mean and BIASED variance: ``stats`` [L, 6, D] = (mu_v, r_v, var_v, mu_e,
-        r_e, var_e) per layer; the running variance takes the unbiased one, var n / (n - 1)."""
-        flat = stats.view(-1, 3, stats.shape[-1])  # [2 L]: v_bn, e_bn per layer
-        rows = [node_rows, node_rows * k]
-        unbiased = flat[:, 2] * torch.tensor([rows[i % 2] / (rows[i % 2] - 1) for i in range(len(bns))],
-                                             dtype=stats.dtype, device=stats.device)[:, None]
-        tracked = [i for i, bn in enumerate(bns) if bn.track_running_stats and bn.running_mean is not None]
-        means, variances = [bns[i].running_mean for i in tracked], [bns[i].running_var for i in tracked]
-        torch._foreach_mul_(means, 1.0 - momentum)
-        torch._foreach_add_(means, [flat[i, 0] for i in tracked], alpha=momentum)
-        torch._foreach_mul_(variances, 1.0 - momentum)
-        torch._foreach_add_(variances, [unbiased[i] for i in tracked], alpha=momentum)
-        torch._foreach_add_([bns[i].num_batches_tracked for i in tracked], 1)
+        return torch.log(heat + SMALL_VALUE).float(), node_embed
 
 
 class _DepotInitEmbedding(nn.Module):
@@ -365,6 +404,53 @@ class NARGNNDepotEncoder(NARGNNEncoder):
         neighbors, cost, depot_cost = self.neighbors(locs)
         return K.nargnn_depot_heatmap(locs, feats, neighbors, cost, depot_cost, small_value=SMALL_VALUE,
                                       **self.packed_parameters(locs.device))
+
+
+class TrainableNARGNNDepotEncoder(_TrainsOnKernels, NARGNNDepotEncoder):
+    """``NARGNNDepotEncoder`` that also trains, for CVRP, OP and PCTSP: the same constructor and ``state_dict`` keys. In
+    ``.eval()`` it IS the parent (one launch of ``rl4co_nargnn_depot_heatmap``, no gradient). In ``.train()``
+    ``forward(td)`` returns ``(heatmap_logits [B, N, N], node_embed [B, N, 64])`` attached to autograd, the batch norms on
+    BATCH statistics, and updates the running statistics of all 2 L batch norms once (the unbiased factor from B N node
+    rows and B (N - 1)(K + 2) edge rows). The GNN stack runs on csrc/nargnn_train.hip's depot-graph kernels behind one
+    autograd node; the neighbour selection, the CSR, the embeddings, the heatmap MLP and the scatter are torch."""
+
+    GRAPH = "depot"
+    TRAIN_KERNEL = "rl4co_nargnn_depot_train_forward"
+    MIN_NODES = 3  # the depot and two customers: a customer needs a customer neighbour
+
+    def forward(self, td):
+        if not self.training:
+            return super().forward(td)
+        locs = td["locs"]
+        self._check(locs)  # (before the features are read: spctsp has other keys)
+        feats = _depot_features(self.env_name, td).detach().contiguous()
+        self._check(locs, feats)
+        locs = locs.detach().contiguous()
+        with torch.no_grad():
+            neighbors, cost, depot_cost = self.neighbors(locs)
+        return self.encode_train(locs, feats, neighbors, cost, depot_cost)
+
+    def encode_train(self, locs: Tensor, feats: Tensor, neighbors: Tensor, cost: Tensor, depot_cost: Tensor):
+        """Train mode on a given graph: ``neighbors`` [B, N - 1, K] int32 (values in 1 .. N - 1), the kNN edges' ``cost``
+        [B, N - 1, K] and ``depot_cost`` [B, N - 1]. The edge rows are in the reference's order: the kNN rows by source,
+        every ``i -> 0``, every ``0 -> i``."""
+        b, n, _ = locs.shape
+        c, k = n - 1, neighbors.shape[2]
+        init = self.init_embedding
+        node_embed = torch.cat((init.init_embed_depot(locs[:, :1]), init.init_embed(torch.cat((locs[:, 1:], feats), -1))), 1)
+        x = nn.functional.silu(node_embed)
+        row_cost = torch.cat((cost.reshape(b, c * k), depot_cost, depot_cost), 1)  # [B, E]
+        w = nn.functional.silu(self.edge_embedding.edge_embed(row_cost[..., None]))
+        if len(self.graph_network.layers):
+            x, w = self._stack_train(x, w, neighbors, K.depot_incoming_csr(neighbors))
+        prob = self._edge_probabilities(w)  # [B, E]
+        cust = torch.arange(1, n, device=locs.device).expand(b, c)
+        zero = torch.zeros_like(cust)
+        src = torch.cat((cust[:, :, None].expand(b, c, k).reshape(b, c * k), cust, zero), 1)
+        dst = torch.cat((neighbors.to(torch.int64).reshape(b, c * k), zero, cust), 1)
+        heat = torch.zeros(b, n, n, dtype=prob.dtype, device=prob.device)
+        heat = heat.index_put((torch.arange(b, device=locs.device)[:, None], src, dst), prob)
+        return torch.log(heat + SMALL_VALUE).float(), node_embed
 
 
 def _merge_with_defaults(value, **defaults) -> dict:
