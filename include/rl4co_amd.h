@@ -61,8 +61,10 @@ extern "C" {
  *  26: rl4co_nargnn_train_forward / rl4co_nargnn_train_backward / rl4co_nargnn_train_workspace_bytes (the heatmap
  *      encoder's GNN stack in train mode and its backward, rl4co_nargnn_train_args).
  *  27: rl4co_nargnn_depot_train_forward / rl4co_nargnn_depot_train_backward / rl4co_nargnn_depot_train_workspace_bytes
- *      (the same stack on the depot graphs of CVRP, OP and PCTSP, rl4co_nargnn_depot_train_args). */
-#define RL4CO_ABI_VERSION 27
+ *      (the same stack on the depot graphs of CVRP, OP and PCTSP, rl4co_nargnn_depot_train_args).
+ *  28: rl4co_nargnn_logz_forward / rl4co_nargnn_logz_backward / rl4co_nargnn_logz_workspace_bytes (GFACS's log-partition
+ *      head on the stack's edge state, rl4co_nargnn_logz_args, RL4CO_LOGZ_POOL_*). */
+#define RL4CO_ABI_VERSION 28
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -1182,6 +1184,55 @@ int rl4co_nargnn_depot_train_forward(const rl4co_nargnn_depot_train_args* args, 
 int rl4co_nargnn_depot_train_backward(const rl4co_nargnn_depot_train_args* args, void* stream);
 /* Bytes of `workspace` at this shape (0 outside the served range). */
 int64_t rl4co_nargnn_depot_train_workspace_bytes(int B, int N, int K, int L);
+
+/* --------------------------------------------------------------------------
+ * GFACS's log-partition head (the reference's models/zoo/gfacs/encoder.py:45-47, 62: Z_net = Linear(64, 64), SiLU,
+ * Linear(64, Z) over the GNN stack's edge state, then a mean), forward and backward, fp32, nargnn_logz.hip. `w` is the
+ * stack's output, flat and batch-major: rows = B E rows of 64 floats, instance 0's E rows first (E = N K for TSP,
+ * (N - 1)(K + 2) for the depot graphs).
+ *   score[r] = W2 silu(W1 w[r] + b1) + b2;   logZ[b] = (1 / E) sum of score[r] over b's group:
+ *     RL4CO_LOGZ_POOL_REFERENCE  the rows r with r % B == b: gfacs/encoder.py:62 as written, reshape(-1, B, Z).mean(0),
+ *                                which strides over the instances
+ *     RL4CO_LOGZ_POOL_INSTANCE   instance b's own rows b E .. b E + E - 1
+ * The hidden [rows, 64] is never written: the forward keeps it in the MFMA accumulators, the backward recomputes it.
+ * rl4co_nargnn_logz_backward, given the same inputs and grad_logZ, writes the gradients of w and of the four parameters.
+ * Every sum has a fixed order that depends on (B, E, pooling) alone (the pooled mean: 256 interleaved float64 sums per
+ * group, halved 128, 64, ...; the parameter gradients: one partial per workgroup, combined in ascending order in float64);
+ * no floating-point atomic, no grid barrier: every output is bit-identical run to run, and with B = 1 the two pooling
+ * rules give the same bits.
+ * Served: Z in {1, 2}, B >= 1, E >= 1, rows = B E <= 2^24. workspace floats: 2 rows + 4290 min(ceil(rows / 64), 1024).
+ * -------------------------------------------------------------------------- */
+#define RL4CO_LOGZ_POOL_REFERENCE 0
+#define RL4CO_LOGZ_POOL_INSTANCE 1
+
+typedef struct rl4co_nargnn_logz_args {
+  int32_t B;                  /* instances, >= 1                                              */
+  int32_t E;                  /* edge rows per instance, >= 1                                 */
+  int32_t Z;                  /* outputs of the head (gfacs/encoder.py: z_out_dim), 1 or 2    */
+  int32_t pooling;            /* RL4CO_LOGZ_POOL_*                                            */
+  int64_t rows;               /* B E                                                          */
+  const float* w;             /* [rows, 64]                                                   */
+  const float* W1;            /* [64, 64]: Z_net.0.weight                                     */
+  const float* b1;            /* [64]:     Z_net.0.bias                                       */
+  const float* W2;            /* [Z, 64]:  Z_net.2.weight                                     */
+  const float* b2;            /* [Z]:      Z_net.2.bias                                       */
+  float* workspace;           /* rl4co_nargnn_logz_workspace_bytes(rows) bytes                */
+  int64_t workspace_bytes;
+  float* logZ;                /* [B, Z]         forward out                                   */
+  const float* grad_logZ;     /* [B, Z]         backward in                                   */
+  float* grad_w;              /* [rows, 64]     backward out                                  */
+  float* grad_W1;             /* [64, 64]       backward out                                  */
+  float* grad_b1;             /* [64]           backward out                                  */
+  float* grad_W2;             /* [Z, 64]        backward out                                  */
+  float* grad_b2;             /* [Z]            backward out                                  */
+} rl4co_nargnn_logz_args;
+
+/* gfacs/encoder.py:62: logZ = Z_net(edge_attr).reshape(-1, len(td), z_out_dim).mean(0) */
+int rl4co_nargnn_logz_forward(const rl4co_nargnn_logz_args* args, void* stream);
+/* the backward of gfacs/encoder.py:62 through Z_net to edge_attr and Z_net's parameters */
+int rl4co_nargnn_logz_backward(const rl4co_nargnn_logz_args* args, void* stream);
+/* Bytes of `workspace` for `rows` rows of gfacs/encoder.py's edge_attr (0 outside the served range). */
+int64_t rl4co_nargnn_logz_workspace_bytes(int64_t rows);
 
 /* --------------------------------------------------------------------------
  * a11-a13  fused encoder + decoder-cache fold on the matrix cores (inference rollouts).

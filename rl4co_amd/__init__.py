@@ -7,8 +7,9 @@ See DESIGN.md for the path, the boundary and what is out of scope.
 """
 __version__ = "0.1.0"
 
-__all__ = ["AntSystem", "DeepACOPolicy", "NARGNNDepotEncoder", "NARGNNEncoder", "NonAutoregressivePolicy",
-           "TrainableNARGNNDepotEncoder", "TrainableNARGNNEncoder"]
+__all__ = ["AntSystem", "DeepACOPolicy", "GFACSDepotEncoder", "GFACSEncoder", "GFACSPolicy", "NARGNNDepotEncoder",
+           "NARGNNEncoder", "NonAutoregressivePolicy", "TrainableNARGNNDepotEncoder", "TrainableNARGNNEncoder", "gfacs_alpha",
+           "gfacs_beta", "gfacs_loss", "log_pb_uniform"]
 
 
 def __getattr__(name):
@@ -16,9 +17,13 @@ def __getattr__(name):
         from .aco import AntSystem
 
         return AntSystem
+    if name in ("gfacs_loss", "log_pb_uniform", "gfacs_alpha", "gfacs_beta"):  # rl4co_amd.aco: GFACS's trajectory-balance loss
+        from . import aco
+
+        return getattr(aco, name)
     # rl4co_amd.nargnn: DeepACO's heatmap encoders on rl4co_nargnn_heatmap / rl4co_nargnn_depot_heatmap
     if name in ("NARGNNEncoder", "NARGNNDepotEncoder", "DeepACOPolicy", "NonAutoregressivePolicy", "TrainableNARGNNEncoder",
-                "TrainableNARGNNDepotEncoder"):
+                "TrainableNARGNNDepotEncoder", "GFACSEncoder", "GFACSDepotEncoder", "GFACSPolicy"):
         from . import nargnn
 
         return getattr(nargnn, name)

@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 27  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 28  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -34,6 +34,7 @@ EBIT_TW_NEGATIVE, EBIT_TW_RETURN, EBIT_TW_DURATION, EBIT_TW_EMPTY, EBIT_TW_DEADL
 EBIT_BEAM_INFEASIBLE = 131072
 EBIT_TOUR_INDEX = 262144
 ACO_SAMPLE, ACO_UPDATE = 1, 2
+LOGZ_POOL_REFERENCE, LOGZ_POOL_INSTANCE = 0, 1
 
 # Reference assertion messages (file:line in the reference checkout) per sticky bit.
 ERROR_MESSAGES = {
@@ -172,6 +173,17 @@ class NargnnDepotTrainArgs(C.Structure):
     rows."""
 
     _fields_ = list(NargnnTrainArgs._fields_)
+
+
+class NargnnLogzArgs(C.Structure):
+    """Mirror of ``struct rl4co_nargnn_logz_args`` (field order and types must match the header)."""
+
+    _fields_ = [
+        ("B", _i32), ("E", _i32), ("Z", _i32), ("pooling", _i32), ("rows", _i64),
+        ("w", _vp), ("W1", _vp), ("b1", _vp), ("W2", _vp), ("b2", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+        ("logZ", _vp), ("grad_logZ", _vp), ("grad_w", _vp), ("grad_W1", _vp), ("grad_b1", _vp), ("grad_W2", _vp),
+        ("grad_b2", _vp),
+    ]
 
 
 class AcoTspArgs(C.Structure):
@@ -366,6 +378,9 @@ SYMBOLS = {
     "rl4co_nargnn_depot_train_forward": (C.c_int, [C.POINTER(NargnnDepotTrainArgs), _vp]),
     "rl4co_nargnn_depot_train_backward": (C.c_int, [C.POINTER(NargnnDepotTrainArgs), _vp]),
     "rl4co_nargnn_depot_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rl4co_nargnn_logz_forward": (C.c_int, [C.POINTER(NargnnLogzArgs), _vp]),
+    "rl4co_nargnn_logz_backward": (C.c_int, [C.POINTER(NargnnLogzArgs), _vp]),
+    "rl4co_nargnn_logz_workspace_bytes": (C.c_int64, [C.c_int64]),
     "rl4co_select_start_nodes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "rl4co_augment_dihedral8_f32": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "rl4co_augment_symmetric_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp]),

@@ -32,9 +32,12 @@ Training: :func:`heatmap_rollout` is DeepACO's constructive training decode — 
 "pctsp" or "spctsp" the SAMPLE launch of ``rl4co_aco_cvrp`` / ``rl4co_aco_prize`` forward and
 ``rl4co_aco_depot_logp_grad`` (csrc/aco_depot_grad.hip) backward; every pair joined by the one ``torch.autograd.Function`` below — and
 :func:`deepaco_loss` the model's REINFORCE loss with the shared baseline (deepaco/model.py:79-91).
-``rl4co_amd.NonAutoregressivePolicy`` (rl4co_amd/nargnn.py) is the reference's training surface over it."""
+``rl4co_amd.NonAutoregressivePolicy`` (rl4co_amd/nargnn.py) is the reference's training surface over it.
+:func:`gfacs_loss`, :func:`log_pb_uniform`, :func:`gfacs_alpha` and :func:`gfacs_beta` are GFACS's trajectory-balance loss and
+its two schedules (gfacs/model.py); ``rl4co_amd.GFACSPolicy`` returns what the loss reads."""
 from __future__ import annotations
 
+import math
 from functools import cached_property
 from typing import NamedTuple
 
@@ -191,6 +194,61 @@ def deepaco_loss(out: dict, train_with_local_search: bool = False, ls_reward_aug
         ls_advantage = ls_reward - ls_reward.mean(dim=1, keepdim=True)
         advantage = advantage * (1 - ls_reward_aug_W) + ls_advantage * ls_reward_aug_W
     return -(advantage * out["log_likelihood"]).mean()
+
+
+def log_pb_uniform(actions: Tensor, env_name: str, n_ants: int):
+    """gfacs/model.py:140-157, ``GFACS.calculate_log_pb_uniform``: the log of the uniform backward policy of a trajectory.
+    tsp: ``log(1 / 2 * N)`` as the reference writes it; op and pctsp: ``log(1 / 2)``; cvrp: per row
+    ``-lgamma(routes + 1) - multinode_routes log 2`` from counts of non-zeros of ``actions`` [n_ants * B, W] and of its
+    shifted differences, float64 [B, n_ants] -- the reference's formula with ``torch.lgamma`` on the actions' device in
+    place of numpy and scipy on the host: no read-back."""
+    if env_name == "tsp":
+        return math.log(1 / 2 * actions.size(1))
+    if env_name == "cvrp":
+        a = actions.detach()
+        n_nodes = torch.count_nonzero(a, dim=1)
+        n_routes = torch.count_nonzero(a[:, 1:] - a[:, :-1], dim=1) - n_nodes
+        n_multinode_routes = torch.count_nonzero(a[:, 2:] - a[:, :-2], dim=1) - n_nodes
+        log_b_p = -torch.lgamma((n_routes + 1).to(torch.float64)) - n_multinode_routes.to(torch.float64) * math.log(2)
+        return log_b_p.view(n_ants, -1).t()  # unbatchify: ant-major rows -> [B, n_ants]
+    if env_name in ("op", "pctsp"):
+        return math.log(1 / 2)
+    raise ValueError(f"Unknown environment: {env_name}")
+
+
+def gfacs_loss(out: dict, env_name: str, alpha: float = 1.0, beta: float = 1.0, train_with_local_search: bool = False) -> Tensor:
+    """gfacs/model.py:107-138, ``GFACS.calculate_loss``: the trajectory-balance loss ``mean((log_likelihood + logZ -
+    log_pb_uniform - beta * advantage)^2)`` with the mean over an instance's ants as the baseline; with local search the
+    advantage is ``(1 - alpha)`` of the sampled tours' and ``alpha`` of the improved tours', and the same loss on the
+    improved tours (``ls_log_likelihood``, ``ls_logZ``, ``ls_actions``, their own advantage) is added. ``out`` is
+    ``GFACSPolicy``'s train-phase dict: ``reward``, ``log_likelihood`` [B, n_ants], ``logZ`` [B, 1], ``actions`` ant-major."""
+    reward = out["reward"]
+    n_ants = reward.size(1)
+    advantage = reward - reward.mean(dim=1, keepdim=True)
+    if train_with_local_search:
+        ls_reward = out["ls_reward"]
+        ls_advantage = ls_reward - ls_reward.mean(dim=1, keepdim=True)
+        weighted_advantage = advantage * (1 - alpha) + ls_advantage * alpha
+    else:
+        weighted_advantage = advantage
+    forward_flow = out["log_likelihood"] + out["logZ"].repeat(1, n_ants)
+    backward_flow = log_pb_uniform(out["actions"], env_name, n_ants) + weighted_advantage.detach() * beta
+    tb_loss = torch.pow(forward_flow - backward_flow, 2).mean()
+    if train_with_local_search:
+        ls_forward_flow = out["ls_log_likelihood"] + out["ls_logZ"].repeat(1, n_ants)
+        ls_backward_flow = log_pb_uniform(out["ls_actions"], env_name, n_ants) + ls_advantage.detach() * beta
+        tb_loss = tb_loss + torch.pow(ls_forward_flow - ls_backward_flow, 2).mean()
+    return tb_loss
+
+
+def gfacs_alpha(epoch: int, max_epochs: int, alpha_min: float = 0.5, alpha_max: float = 1.0, alpha_flat_epochs: int = 5) -> float:
+    """gfacs/model.py:75-80: the weight of the improved tours' advantage, linear in the epoch up to ``alpha_max``."""
+    return alpha_min + (alpha_max - alpha_min) * min(epoch / (max_epochs - alpha_flat_epochs), 1.0)
+
+
+def gfacs_beta(epoch: int, max_epochs: int, beta_min: float = 1.0, beta_max: float = 1.0, beta_flat_epochs: int = 5) -> float:
+    """gfacs/model.py:82-88: the inverse temperature of the reward, logarithmic in the epoch up to ``beta_max``."""
+    return beta_min + (beta_max - beta_min) * min(math.log(epoch + 1) / math.log(max_epochs - beta_flat_epochs), 1.0)
 
 
 class AntSystem:

@@ -946,6 +946,71 @@ def nargnn_depot_train_backward(neighbors: Tensor, csr_ptr: Tensor, csr_src: Ten
                                   grad_x_out, grad_w_out, eps, err)
 
 
+# ---- GFACS's log-partition head on the stack's edge state (csrc/nargnn_logz.hip) -------------------------------------------------
+LOGZ_POOLING = {"reference": _lib.LOGZ_POOL_REFERENCE, "instance": _lib.LOGZ_POOL_INSTANCE}
+
+
+def _nargnn_logz_args(w, W1, b1, W2, b2, batch, pooling):
+    if pooling not in LOGZ_POOLING:
+        raise ValueError(f"pooling must be one of {sorted(LOGZ_POOLING)}, got {pooling!r}")
+    d = w.shape[-1]
+    if d != 64:
+        raise NotImplementedError(f"nargnn_logz serves embed_dim = 64 only, got {d}")
+    z = W2.shape[0]
+    if z not in (1, 2):
+        raise NotImplementedError(f"nargnn_logz serves z_out_dim 1 or 2, got {z}")
+    rows, batch = w.numel() // d, int(batch)
+    if batch < 1 or rows < 1 or rows % batch:
+        raise ValueError(f"w must hold B E >= 1 rows for B = {batch} >= 1, got {rows}")
+    for name, t, shape in (("W1", W1, (d, d)), ("b1", b1, (d,)), ("W2", W2, (z, d)), ("b2", b2, (z,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    for name, t in (("w", w), ("W1", W1), ("b1", b1), ("W2", W2), ("b2", b2)):
+        _dev(t, torch.float32, name)
+    nbytes = int(_lib.lib().rl4co_nargnn_logz_workspace_bytes(rows))
+    if nbytes <= 0:
+        raise NotImplementedError(f"nargnn_logz does not serve {rows} rows (B E <= 2^24)")
+    a = _lib.NargnnLogzArgs()
+    a.B, a.E, a.Z, a.pooling, a.rows = batch, rows // batch, z, LOGZ_POOLING[pooling], rows
+    a.workspace_bytes = nbytes
+    values = dict(w=w, W1=W1, b1=b1, W2=W2, b2=b2, workspace=torch.empty(nbytes // 4, dtype=torch.float32, device=w.device))
+    return a, values, z
+
+
+def _nargnn_logz_launch(symbol: str, a, values: dict) -> None:
+    for name, ctype in a._fields_:
+        if ctype is C.c_void_p:
+            setattr(a, name, _ptr(values.get(name)))
+    _lib.check(getattr(_lib.lib(), symbol)(C.byref(a), _stream()), symbol)
+
+
+def nargnn_logz_forward(w: Tensor, W1: Tensor, b1: Tensor, W2: Tensor, b2: Tensor, *, batch: int,
+                        pooling: str = "reference") -> Tensor:
+    """GFACS's log-partition head (gfacs/encoder.py:45-47, 62; rl4co_nargnn_logz_forward), fp32: ``w`` [..., 64] the GNN
+    stack's edge state, flat and batch-major (``batch`` instances of E rows each), ``W1`` [64, 64], ``b1`` [64], ``W2``
+    [Z, 64], ``b2`` [Z] the two linears of ``Z_net``, Z in {1, 2}. Returns ``logZ`` [B, Z]: the mean of the rows' scores over
+    the rows r with ``r % B == b`` (``pooling="reference"``: the reference's reshape read literally) or over instance b's own
+    rows (``"instance"``)."""
+    a, values, z = _nargnn_logz_args(w, W1, b1, W2, b2, batch, pooling)
+    values["logZ"] = torch.empty((a.B, z), dtype=torch.float32, device=w.device)
+    _nargnn_logz_launch("rl4co_nargnn_logz_forward", a, values)
+    return values["logZ"]
+
+
+def nargnn_logz_backward(w: Tensor, W1: Tensor, b1: Tensor, W2: Tensor, b2: Tensor, grad_logz: Tensor, *, batch: int,
+                         pooling: str = "reference") -> dict:
+    """The backward of :func:`nargnn_logz_forward` (rl4co_nargnn_logz_backward) given its inputs and ``grad_logz`` [B, Z]; the
+    hidden is recomputed. Returns the gradients by name: ``w``, ``W1``, ``b1``, ``W2``, ``b2``."""
+    a, values, z = _nargnn_logz_args(w, W1, b1, W2, b2, batch, pooling)
+    if tuple(grad_logz.shape) != (a.B, z):
+        raise ValueError(f"grad_logz must be {(a.B, z)}, got {tuple(grad_logz.shape)}")
+    grads = dict(w=torch.empty_like(w), W1=torch.empty_like(W1), b1=torch.empty_like(b1), W2=torch.empty_like(W2),
+                 b2=torch.empty_like(b2))
+    values.update(grad_logZ=_dev(grad_logz, torch.float32, "grad_logz"), **{"grad_" + key: t for key, t in grads.items()})
+    _nargnn_logz_launch("rl4co_nargnn_logz_backward", a, values)
+    return grads
+
+
 # ---- the Ant System: one table of families, one launch path for the search, one for the backward ---------------------------
 _ACO_PRIZE_ENVS = {"op": _lib.ENV_OP, "pctsp": _lib.ENV_PCTSP, "spctsp": _lib.ENV_PCTSP}  # spctsp: the caller's prize is the stochastic one
 _ACO_DEPOT_GRAD_ENVS = {"cvrp": _lib.ENV_CVRP, **_ACO_PRIZE_ENVS}

@@ -13,7 +13,9 @@ sorted=False)``) taken for the whole batch on the device; the eval-mode batch no
 shift (in float64, rounded once). Training, CPU tensors, other environments, activations, aggregations and widths are
 refused with ``NotImplementedError``: there is no torch fall-back. ``TrainableNARGNNEncoder`` is ``NARGNNEncoder`` that also
 trains (TSP): in ``.train()`` the GNN stack runs on batch statistics, forward and backward, on csrc/nargnn_train.hip;
-``TrainableNARGNNDepotEncoder`` is the same for ``NARGNNDepotEncoder`` (CVRP, OP, PCTSP) on that file's depot-graph kernels."""
+``TrainableNARGNNDepotEncoder`` is the same for ``NARGNNDepotEncoder`` (CVRP, OP, PCTSP) on that file's depot-graph kernels.
+``GFACSEncoder`` / ``GFACSDepotEncoder`` add GFACS's log-partition head (models/zoo/gfacs/encoder.py) on csrc/nargnn_logz.hip,
+``GFACSPolicy`` is the reference's policy over them (models/zoo/gfacs/policy.py)."""
 from __future__ import annotations
 
 from functools import partial
@@ -333,6 +335,10 @@ class TrainableNARGNNEncoder(_TrainsOnKernels, NARGNNEncoder):
 
     def encode_train(self, locs: Tensor, neighbors: Tensor, cost: Tensor):
         """Train mode on a given graph: ``neighbors`` [B, N, K] int32 and the edges' ``cost`` [B, N, K]."""
+        return self._encode_train(locs, neighbors, cost)[:2]
+
+    def _encode_train(self, locs: Tensor, neighbors: Tensor, cost: Tensor):
+        """``encode_train`` and, third, the stack's edge state ``w`` [B, N, K, 64] (what a further head reads)."""
         node_embed = self.init_embedding.init_embed(locs)
         x = nn.functional.silu(node_embed)
         w = nn.functional.silu(self.edge_embedding.edge_embed(cost[..., None]))
@@ -341,7 +347,7 @@ class TrainableNARGNNEncoder(_TrainsOnKernels, NARGNNEncoder):
         prob = self._edge_probabilities(w)  # [B, N, K]
         heat = torch.zeros(locs.shape[0], locs.shape[1], locs.shape[1], dtype=prob.dtype, device=prob.device)
         heat = heat.scatter(2, neighbors.to(torch.int64), prob)
-        return torch.log(heat + SMALL_VALUE).float(), node_embed
+        return torch.log(heat + SMALL_VALUE).float(), node_embed, w
 
 
 class _DepotInitEmbedding(nn.Module):
@@ -434,6 +440,10 @@ class TrainableNARGNNDepotEncoder(_TrainsOnKernels, NARGNNDepotEncoder):
         """Train mode on a given graph: ``neighbors`` [B, N - 1, K] int32 (values in 1 .. N - 1), the kNN edges' ``cost``
         [B, N - 1, K] and ``depot_cost`` [B, N - 1]. The edge rows are in the reference's order: the kNN rows by source,
         every ``i -> 0``, every ``0 -> i``."""
+        return self._encode_train(locs, feats, neighbors, cost, depot_cost)[:2]
+
+    def _encode_train(self, locs: Tensor, feats: Tensor, neighbors: Tensor, cost: Tensor, depot_cost: Tensor):
+        """``encode_train`` and, third, the stack's edge state ``w`` [B, E, 64] (what a further head reads)."""
         b, n, _ = locs.shape
         c, k = n - 1, neighbors.shape[2]
         init = self.init_embedding
@@ -450,7 +460,81 @@ class TrainableNARGNNDepotEncoder(_TrainsOnKernels, NARGNNDepotEncoder):
         dst = torch.cat((neighbors.to(torch.int64).reshape(b, c * k), zero, cust), 1)
         heat = torch.zeros(b, n, n, dtype=prob.dtype, device=prob.device)
         heat = heat.index_put((torch.arange(b, device=locs.device)[:, None], src, dst), prob)
-        return torch.log(heat + SMALL_VALUE).float(), node_embed
+        return torch.log(heat + SMALL_VALUE).float(), node_embed, w
+
+
+class _LogZHead(torch.autograd.Function):
+    """GFACS's log-partition head (gfacs/encoder.py:45-47, 62) as ONE autograd node over csrc/nargnn_logz.hip: ``w`` [..., 64]
+    the stack's edge state (``batch`` instances, batch-major), the two linears of ``Z_net`` -> ``logZ`` [B, Z]. The hidden is
+    never stored: the backward recomputes it. There is no double backward."""
+
+    @staticmethod
+    def forward(ctx, w, W1, b1, W2, b2, batch, pooling):
+        tensors = [t.detach().contiguous() for t in (w, W1, b1, W2, b2)]
+        ctx.save_for_backward(*tensors)
+        ctx.batch, ctx.pooling = batch, pooling
+        return K.nargnn_logz_forward(*tensors, batch=batch, pooling=pooling)
+
+    @staticmethod
+    def backward(ctx, grad_logz):
+        if torch.is_grad_enabled():
+            raise RuntimeError("the logZ head has no double backward: rl4co_nargnn_logz_backward is not differentiable "
+                               "(create_graph=True is not served)")
+        g = K.nargnn_logz_backward(*ctx.saved_tensors, grad_logz.to(torch.float32).contiguous(), batch=ctx.batch,
+                                   pooling=ctx.pooling)
+        return g["w"], g["W1"], g["b1"], g["W2"], g["b2"], None, None
+
+
+class _EstimatesLogZ:
+    """What the two GFACS encoders add to their trainable parents, mixed in ahead of them: ``Z_net`` under the reference's
+    keys (``Z_net.0.*``, ``Z_net.2.*``), ``z_out_dim``, the pooling rule, and the third output."""
+
+    def _add_z_net(self, embed_dim: int, z_out_dim: int, pooling: str) -> None:
+        if z_out_dim not in (1, 2):
+            raise NotImplementedError(f"{type(self).__name__} serves z_out_dim 1 or 2 (logZ, and ls_logZ when training with "
+                                      f"local search), got {z_out_dim}")
+        if pooling not in K.LOGZ_POOLING:
+            raise ValueError(f"pooling must be one of {sorted(K.LOGZ_POOLING)}, got {pooling!r}")
+        self.Z_net = nn.Sequential(nn.Linear(embed_dim, embed_dim), nn.SiLU(), nn.Linear(embed_dim, z_out_dim))
+        self.z_out_dim, self.pooling = z_out_dim, pooling
+
+    def forward(self, td):
+        """``.train()``: ``(heatmap_logits [B, N, N], node_embed [B, N, 64], logZ [B, z_out_dim])``, all attached to autograd.
+        ``.eval()``: ``(heatmap_logits, node_embed, None)`` -- the fused inference kernel keeps the edge state on chip and
+        the reference's val / test path never reads ``logZ``."""
+        if not self.training:
+            return (*super().forward(td), None)
+        return super().forward(td)  # (the parent's graph selection, then encode_train below)
+
+    def encode_train(self, *graph):
+        """The parent's ``encode_train`` and ``logZ`` [B, z_out_dim] from the kernel head on the stack's output ``w`` (without
+        GNN layers: on the activated edge embedding). The heatmap MLP and the head both read ``w``; autograd adds the two
+        gradients."""
+        heat, node_embed, w = self._encode_train(*graph)
+        first, last = self.Z_net[0], self.Z_net[2]
+        logz = _LogZHead.apply(w, first.weight, first.bias, last.weight, last.bias, heat.shape[0], self.pooling)
+        return heat, node_embed, logz
+
+
+class GFACSEncoder(_EstimatesLogZ, TrainableNARGNNEncoder):
+    """gfacs/encoder.py:8-68 for TSP: ``TrainableNARGNNEncoder`` plus the log-partition head ``Z_net`` (``Linear(64, 64)``,
+    ``SiLU``, ``Linear(64, z_out_dim)``) for the trajectory-balance loss; a reference GFACS ``state_dict`` loads with
+    ``strict=True``. ``pooling="reference"`` (the default, what the reference's checkpoints were trained with) is
+    encoder.py:62 as written: ``logZ[b]`` is the mean over the flat edge rows r with ``r % B == b``; ``pooling="instance"``
+    is the mean over instance b's own rows. See ``forward``."""
+
+    def __init__(self, embed_dim: int = 64, env_name: str = "tsp", z_out_dim: int = 1, pooling: str = "reference", **kwargs):
+        super().__init__(embed_dim=embed_dim, env_name=env_name, **kwargs)
+        self._add_z_net(embed_dim, z_out_dim, pooling)
+
+
+class GFACSDepotEncoder(_EstimatesLogZ, TrainableNARGNNDepotEncoder):
+    """:class:`GFACSEncoder` for CVRP, OP and PCTSP: ``TrainableNARGNNDepotEncoder`` plus ``Z_net`` over the depot graph's
+    B (N - 1)(K + 2) edge rows."""
+
+    def __init__(self, embed_dim: int = 64, env_name: str = "cvrp", z_out_dim: int = 1, pooling: str = "reference", **kwargs):
+        super().__init__(embed_dim=embed_dim, env_name=env_name, **kwargs)
+        self._add_z_net(embed_dim, z_out_dim, pooling)
 
 
 def _merge_with_defaults(value, **defaults) -> dict:
@@ -528,7 +612,7 @@ class DeepACOPolicy(nn.Module):
             from .envs import get_env
 
             env = get_env(self.env_name if env is None else env)
-        heatmap, _ = self.encoder(td_initial)
+        heatmap = self.encoder(td_initial)[0]  # (heatmap, node_embed) or, from a GFACS encoder, (heatmap, node_embed, logZ)
         heatmap /= self.temperature
         aco = self.aco_class(heatmap, n_ants=n_ants, **self.aco_kwargs)
         self.last_aco = aco
@@ -585,6 +669,91 @@ class DeepACOPolicy(nn.Module):
             self.last_aco = aco
             _, ls_reward = aco.local_search(td_initial, env, rolled["actions"], decoding_kwargs)
             out["ls_reward"] = unbatchify(ls_reward)
+        return out
+
+
+class GFACSPolicy(DeepACOPolicy):
+    """gfacs/policy.py:22-180 with the reference's constructor. With ``encoder=None`` the policy builds the trainable GFACS
+    encoder of ``env_name`` (``z_out_dim = 2 if train_with_local_search else 1``), and unlike ``DeepACOPolicy`` its own
+    encoder trains. ``train_with_local_search`` (default True, as in the reference) needs
+    ``aco_kwargs["use_local_search"]`` and is refused for cvrp, op and pctsp, where no local search is served.
+
+    ``phase="train"`` (policy.py:107-160): one :func:`rl4co_amd.aco.heatmap_rollout` and ``reward``, ``log_likelihood``
+    [B, n_ants] and ``logZ`` [B, 1]; with local search ``aco.local_search`` on the sampled tours (2-opt, or NLS with
+    ``use_nls``), a second ``heatmap_rollout(actions=ls_actions)`` and ``ls_logZ`` [B, 1], ``ls_reward``,
+    ``ls_log_likelihood`` [B, n_ants] and ``ls_actions``. ``actions`` and ``ls_actions`` stay ant-major rows
+    [n_ants * B, W]. tsp runs multistart, cvrp / op / pctsp multisample (cvrp multistart too, with ``multistart=True``).
+    The decoding keywords ``DeepACOPolicy``'s train path refuses are refused here too, before the encoder runs.
+    ``phase="val"`` / ``"test"``: ``DeepACOPolicy.forward`` itself, which reads the first output of the encoder."""
+
+    def __init__(self, encoder: nn.Module | None = None, env_name: str = "tsp", temperature: float = 1.0, top_p: float = 0.0,
+                 top_k: int = 0, aco_class: type | None = None, aco_kwargs: dict = {}, train_with_local_search: bool = True,
+                 n_ants: int | dict | None = None, n_iterations: int | dict | None = None, multistart: bool = False,
+                 k_sparse: int | None = None, **encoder_kwargs):
+        from .aco import _SERVES
+
+        why = _SERVES[env_name].no_local_search if env_name in _SERVES else None
+        if train_with_local_search and why:
+            raise NotImplementedError(f"GFACSPolicy(train_with_local_search=True) is not served for {env_name}: {why} "
+                                      f"(pass train_with_local_search=False)")
+        if encoder is None:
+            cls = GFACSDepotEncoder if env_name in DEPOT_ENVS else GFACSEncoder
+            encoder = cls(env_name=env_name, z_out_dim=2 if train_with_local_search else 1, **encoder_kwargs)
+        elif train_with_local_search and getattr(encoder, "z_out_dim", 2) < 2:
+            raise ValueError("GFACSPolicy(train_with_local_search=True) reads logZ[:, 1]: the encoder needs z_out_dim=2")
+        super().__init__(encoder=encoder, env_name=env_name, temperature=temperature, top_p=top_p, top_k=top_k,
+                         aco_class=aco_class, aco_kwargs=aco_kwargs, train_with_local_search=train_with_local_search,
+                         n_ants=n_ants, n_iterations=n_iterations, multistart=multistart, k_sparse=k_sparse)
+
+    def forward(self, td_initial, env=None, phase: str = "train", return_actions: bool = True, return_hidden: bool = False,
+                actions=None, **decoding_kwargs):
+        if phase != "train":  # the parent's Ant System search on the encoder's heatmap; it refuses any other phase
+            return super().forward(td_initial, env, phase, return_actions, **decoding_kwargs)
+        if env is None or isinstance(env, str):
+            from .envs import get_env
+
+            env = get_env(self.env_name if env is None else env)
+        return self._train(td_initial, env, self.n_ants["train"], return_actions, return_hidden, actions, decoding_kwargs)
+
+    def _train(self, td_initial, env, n_ants: int, return_actions: bool, return_hidden: bool, actions, decoding_kwargs: dict):
+        if actions is not None or decoding_kwargs.pop("actions", None) is not None:
+            raise NotImplementedError("GFACSPolicy phase='train' does not serve actions= (the reference's 'evaluate' strategy); "
+                                      "rl4co_amd.aco.heatmap_rollout(actions=...) evaluates given rows")
+        if decoding_kwargs.pop("return_entropy", False):
+            raise NotImplementedError("GFACSPolicy phase='train' does not serve return_entropy=True")
+        if not decoding_kwargs.pop("return_sum_log_likelihood", True):
+            raise NotImplementedError("GFACSPolicy phase='train' does not serve return_sum_log_likelihood=False")
+        multistart = "multistart" in self.decode_type
+        decoding_kwargs.setdefault("temperature", self.temperature)
+        decoding_kwargs.update(self.default_decoding_kwargs)
+        decoding_kwargs.update({"num_starts": n_ants} if multistart else {"num_samples": n_ants})
+        # the refusals come before the encoder runs: the search's own check on an empty heatmap on the instances' device
+        locs = td_initial["locs"]
+        self.aco_class(locs.new_empty((locs.shape[0], 0, 0)), n_ants=n_ants, **self.aco_kwargs)._check(td_initial, env, decoding_kwargs)
+        heatmap, _, logz = self.encoder(td_initial)
+        aco = self.aco_class(heatmap.detach(), n_ants=n_ants, **self.aco_kwargs)
+        temperature = aco._check(td_initial, env, decoding_kwargs)  # (the encoder's output device)
+        starts = aco._start_nodes(td_initial, env, decoding_kwargs) if multistart else None  # called once
+        graph = {} if self.env_name == "tsp" else {"env_name": self.env_name, "td": td_initial}
+        rolled = heatmap_rollout(heatmap, locs, n_ants=n_ants, start_nodes=starts, temperature=temperature, **graph)
+
+        def unbatchify(x):  # [rows] ant-major -> [B, n_ants]
+            return x.view(n_ants, -1).t()
+
+        out = {"logZ": logz[:, [0]], "reward": unbatchify(rolled["reward"]),
+               "log_likelihood": unbatchify(rolled["log_likelihood"])}
+        if return_actions:
+            out["actions"] = rolled["actions"]
+        if self.train_with_local_search:
+            self.last_aco = aco
+            ls_actions, ls_reward = aco.local_search(td_initial, env, rolled["actions"], decoding_kwargs)
+            searched = heatmap_rollout(heatmap, locs, n_ants=n_ants, actions=ls_actions, temperature=temperature, **graph)
+            out.update({"ls_logZ": logz[:, [1]], "ls_reward": unbatchify(ls_reward),
+                        "ls_log_likelihood": unbatchify(searched["log_likelihood"])})
+            if return_actions:
+                out["ls_actions"] = searched["actions"]
+        if return_hidden:
+            out["hidden"] = heatmap
         return out
 
 
