@@ -63,8 +63,10 @@ extern "C" {
  *  27: rl4co_nargnn_depot_train_forward / rl4co_nargnn_depot_train_backward / rl4co_nargnn_depot_train_workspace_bytes
  *      (the same stack on the depot graphs of CVRP, OP and PCTSP, rl4co_nargnn_depot_train_args).
  *  28: rl4co_nargnn_logz_forward / rl4co_nargnn_logz_backward / rl4co_nargnn_logz_workspace_bytes (GFACS's log-partition
- *      head on the stack's edge state, rl4co_nargnn_logz_args, RL4CO_LOGZ_POOL_*). */
-#define RL4CO_ABI_VERSION 28
+ *      head on the stack's edge state, rl4co_nargnn_logz_args, RL4CO_LOGZ_POOL_*).
+ *  29: rl4co_aco_tsp_opts / rl4co_aco_cvrp_opts / rl4co_aco_prize_opts / rl4co_aco_tsp_logp_grad_opts /
+ *      rl4co_aco_depot_logp_grad_opts (greedy and top-k / top-p decoding of a heatmap, rl4co_heatmap_decode_opts). */
+#define RL4CO_ABI_VERSION 29
 
 /* ---- status codes ------------------------------------------------------ */
 #define RL4CO_OK 0
@@ -899,6 +901,41 @@ int rl4co_aco_prize(const rl4co_aco_prize_args* args, void* stream);
 /* Largest N at which rl4co_aco_prize keeps the logits and the pheromone in LDS for `env` (aco_prize.hip header); -1 for an
  * environment it does not serve. */
 int rl4co_aco_prize_lds_nodes(int env);
+
+/* --------------------------------------------------------------------------
+ * Greedy and top-k / top-p (nucleus) decoding of a heatmap (utils/decoding.py:109-188 under NonAutoregressiveDecoder; the
+ * reference's NARGNNPolicy validates and tests with multistart_greedy and decodes its large graphs with top_k): the three
+ * searches and the two gradients above with one options struct behind their own, unchanged argument struct. With every
+ * option off (a zero-initialised struct) an *_opts entry point IS the entry point without the suffix: the same kernel
+ * instantiation, the same bits; rl4co_aco_tsp(args, stream) is rl4co_aco_tsp_opts(args, &zeros, stream), and so on.
+ *   top_k   0 < top_k < the step's number of feasible nodes: the feasible logits below the top_k-th largest are removed
+ *           (ties at that value stay; a feasible -inf counts, so the threshold can be -inf and nothing is below it).
+ *   top_p   0 < top_p < 1, after top_k and over its survivors: in (logit, node) ascending order, nodes are removed while
+ *           their cumulative mass is <= (1 - top_p) Z; masses are exp(z - zmax) in the step's own order of sums. The
+ *           largest logit is never removed.
+ *           Everything after the filter (the log-softmax statistics, the log-probs, the argmax, all_logps) runs on the
+ *           kept set: a removed node has log-prob -inf, and a forced action outside the kept set gets -inf and raises
+ *           RL4CO_EBIT_NEG_INF_LOGP ("Logprobs should not be -inf").
+ *   greedy  1: the chosen node is the argmax of the log-probs over the kept set, the lowest node on equal values; no noise
+ *           is read and no Philox word is drawn (ln_noise must be NULL). The log-prob is reported as in sampling. The
+ *           gradients ignore it.
+ * The gradients recompute each step's kept set from the row's logits and the step's feasible set in the forward's own
+ * text and run g * ((n == a_t) - p_n) / temperature over the kept nodes only: a removed node gets 0. Ascending-ant sums,
+ * no float atomics, identical bits for any row_split and the per-instance refusals hold as without the filter.
+ * -------------------------------------------------------------------------- */
+typedef struct rl4co_heatmap_decode_opts {
+  int32_t greedy;           /* 0 sample, 1 argmax of the log-probs (searches; ignored by the gradients) */
+  int32_t top_k;            /* >= 0; 0 or >= the feasible nodes: off                          */
+  float top_p;              /* 0 .. 1; 0 and 1: off                                           */
+  int32_t reserved0;        /* 0                                                              */
+} rl4co_heatmap_decode_opts;
+
+int rl4co_aco_tsp_opts(const rl4co_aco_tsp_args* args, const rl4co_heatmap_decode_opts* opts, void* stream);
+int rl4co_aco_cvrp_opts(const rl4co_aco_cvrp_args* args, const rl4co_heatmap_decode_opts* opts, void* stream);
+int rl4co_aco_prize_opts(const rl4co_aco_prize_args* args, const rl4co_heatmap_decode_opts* opts, void* stream);
+int rl4co_aco_tsp_logp_grad_opts(const rl4co_aco_tsp_grad_args* args, const rl4co_heatmap_decode_opts* opts, void* stream);
+int rl4co_aco_depot_logp_grad_opts(const rl4co_aco_depot_grad_args* args, const rl4co_heatmap_decode_opts* opts,
+                                   void* stream);
 
 /* --------------------------------------------------------------------------
  * Neural-guided local search for TSP (DeepACO's NLS: AntSystem.local_search with use_nls, antsystem.py:173-230) as ONE

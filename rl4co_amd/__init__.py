@@ -8,7 +8,7 @@ See DESIGN.md for the path, the boundary and what is out of scope.
 __version__ = "0.1.0"
 
 __all__ = ["AntSystem", "DeepACOPolicy", "GFACSDepotEncoder", "GFACSEncoder", "GFACSPolicy", "NARGNNDepotEncoder",
-           "NARGNNEncoder", "NonAutoregressivePolicy", "TrainableNARGNNDepotEncoder", "TrainableNARGNNEncoder", "gfacs_alpha",
+           "NARGNNEncoder", "NARGNNPolicy", "NonAutoregressivePolicy", "TrainableNARGNNDepotEncoder", "TrainableNARGNNEncoder", "gfacs_alpha",
            "gfacs_beta", "gfacs_loss", "log_pb_uniform"]
 
 
@@ -23,7 +23,7 @@ def __getattr__(name):
         return getattr(aco, name)
     # rl4co_amd.nargnn: DeepACO's heatmap encoders on rl4co_nargnn_heatmap / rl4co_nargnn_depot_heatmap
     if name in ("NARGNNEncoder", "NARGNNDepotEncoder", "DeepACOPolicy", "NonAutoregressivePolicy", "TrainableNARGNNEncoder",
-                "TrainableNARGNNDepotEncoder", "GFACSEncoder", "GFACSDepotEncoder", "GFACSPolicy"):
+                "TrainableNARGNNDepotEncoder", "GFACSEncoder", "GFACSDepotEncoder", "GFACSPolicy", "NARGNNPolicy"):
         from . import nargnn
 
         return getattr(nargnn, name)

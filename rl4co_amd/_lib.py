@@ -12,7 +12,7 @@ from functools import lru_cache
 from . import build as _build
 
 RL4CO_OK = 0
-ABI_VERSION = 28  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
+ABI_VERSION = 29  # RL4CO_ABI_VERSION of include/rl4co_amd.h this binding's argument lists were written for
 ENV_TSP, ENV_CVRP, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_CVRPTW, ENV_SDVRP, ENV_MTSP = 0, 1, 2, 3, 4, 5, 6, 7
 DECODE_GREEDY, DECODE_SAMPLE, DECODE_EVALUATE = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
@@ -253,6 +253,12 @@ class AcoPrizeArgs(C.Structure):
     ]
 
 
+class HeatmapDecodeOpts(C.Structure):
+    """Mirror of ``struct rl4co_heatmap_decode_opts`` (field order and types must match the header)."""
+
+    _fields_ = [("greedy", _i32), ("top_k", _i32), ("top_p", _f32), ("reserved0", _i32)]
+
+
 class EnvReplayArgs(C.Structure):
     """Mirror of ``struct rl4co_env_replay_args``."""
 
@@ -364,6 +370,11 @@ SYMBOLS = {
     "rl4co_aco_cvrp_lds_nodes": (C.c_int, []),
     "rl4co_aco_prize": (C.c_int, [C.POINTER(AcoPrizeArgs), _vp]),
     "rl4co_aco_prize_lds_nodes": (C.c_int, [C.c_int]),
+    "rl4co_aco_tsp_opts": (C.c_int, [C.POINTER(AcoTspArgs), C.POINTER(HeatmapDecodeOpts), _vp]),
+    "rl4co_aco_cvrp_opts": (C.c_int, [C.POINTER(AcoCvrpArgs), C.POINTER(HeatmapDecodeOpts), _vp]),
+    "rl4co_aco_prize_opts": (C.c_int, [C.POINTER(AcoPrizeArgs), C.POINTER(HeatmapDecodeOpts), _vp]),
+    "rl4co_aco_tsp_logp_grad_opts": (C.c_int, [C.POINTER(AcoTspGradArgs), C.POINTER(HeatmapDecodeOpts), _vp]),
+    "rl4co_aco_depot_logp_grad_opts": (C.c_int, [C.POINTER(AcoDepotGradArgs), C.POINTER(HeatmapDecodeOpts), _vp]),
     "rl4co_tsp_nls": (C.c_int, [C.POINTER(TspNlsArgs), _vp]),
     "rl4co_tsp_nls_lds_nodes": (C.c_int, []),
     "rl4co_nargnn_heatmap": (C.c_int, [C.POINTER(NargnnArgs), _vp]),

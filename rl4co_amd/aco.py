@@ -75,12 +75,13 @@ class _AntLogLikelihood(torch.autograd.Function):
     """The ants' per-step log-probs and their sum as functions of the heatmap: the forward is the SAMPLE launch of the
     environment's search kernel (``kernels.aco_search``; pheromone of ones, alpha = beta = 1: ``rl4co_logf(1) == 0`` exactly,
     so its logits ARE the heatmap), the backward is its log-likelihood gradient kernel (``kernels.aco_logp_grad``). ``data``:
-    ``locs`` and the instance tensors the bindings take by name; ``lengths`` is None for tsp. Nothing is saved unless the
+    ``locs`` and the instance tensors the bindings take by name; ``lengths`` is None for tsp. ``decode``: the options
+    ``greedy`` / ``top_k`` / ``top_p`` of both launches (empty: the symbols without them). Nothing is saved unless the
     heatmap requires a gradient; there is no double backward."""
 
     @staticmethod
-    def forward(ctx, heatmap, env_name, data, start_nodes, forced, n_ants, temperature, seed, err):
-        kw = dict(data)
+    def forward(ctx, heatmap, env_name, data, start_nodes, forced, n_ants, temperature, seed, err, decode):
+        kw = dict(data, **decode)
         if K.aco_family(env_name).start_nodes:
             kw["start_nodes"] = None if start_nodes is None else start_nodes[None].contiguous()
         out = K.aco_search(env_name, torch.ones_like(heatmap), n_ants=n_ants, phases=_lib.ACO_SAMPLE, log_heuristic=heatmap,
@@ -90,6 +91,7 @@ class _AntLogLikelihood(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(heatmap, actions)
             ctx.temperature, ctx.err, ctx.env_name, ctx.multistart = temperature, err, env_name, start_nodes is not None
+            ctx.decode = decode
             ctx.data = {key: data[key] for key, _ in K.aco_grad_family(env_name).needs[env_name]}
         ctx.mark_non_differentiable(*(t for t in (actions, lengths, reward) if t is not None))
         return logps, logps.sum(1), actions, lengths, reward
@@ -109,16 +111,18 @@ class _AntLogLikelihood(torch.autograd.Function):
         own = ctx.err is None
         err = K.new_error_word(heatmap.device) if own else ctx.err
         grad = K.aco_logp_grad(ctx.env_name, heatmap, actions, grad_ll, grad_steps=grad_logps, temperature=ctx.temperature,
-                               err=err, **ctx.data, **({"multistart": ctx.multistart} if fam.depot else {}))
+                               err=err, **ctx.data, **ctx.decode, **({"multistart": ctx.multistart} if fam.depot else {}))
         if own:
             _lib.raise_for_error_bits(int(err.item()))
-        return grad, None, None, None, None, None, None, None, None
+        return grad, None, None, None, None, None, None, None, None, None
 
 
 def heatmap_rollout(heatmap: Tensor, locs: Tensor, *, n_ants: int, start_nodes: Tensor | None = None,
                     actions: Tensor | None = None, temperature: float = 1.0, seed: int | None = None,
                     err: Tensor | None = None, env_name: str = "tsp", td=None) -> dict:
-    """DeepACO's constructive training rollout for TSP (``ConstructivePolicy.forward`` under ``NonAutoregressiveDecoder``:
+    """:func:`heatmap_decode` with ``decode_type="sampling"`` and no filter.
+
+    DeepACO's constructive training rollout for TSP (``ConstructivePolicy.forward`` under ``NonAutoregressiveDecoder``:
     ``n_ants`` tours per instance sampled step by step from ``softmax(heatmap[b, current, unvisited] / temperature)``) as
     ONE launch, with the gradient back to ``heatmap`` [B, N, N] as one more.
 
@@ -136,6 +140,29 @@ def heatmap_rollout(heatmap: Tensor, locs: Tensor, *, n_ants: int, start_nodes: 
     ``W`` wide (``kernels.aco_depot_width``) and zero-filled after ``lengths`` [rows], which is returned too; ``logps``
     [rows, W] are 0 there, ``reward`` is the environment's ``get_reward`` on the W-wide row. ``actions`` [rows, W] are
     followed and evaluated (with ``start_nodes`` given too, column 0 is the multistart start)."""
+    return heatmap_decode(heatmap, locs, n_ants=n_ants, start_nodes=start_nodes, actions=actions, temperature=temperature,
+                          seed=seed, err=err, env_name=env_name, td=td)
+
+
+def heatmap_decode(heatmap: Tensor, locs: Tensor, *, n_ants: int, decode_type: str = "sampling", top_k: int = 0,
+                   top_p: float = 0.0, start_nodes: Tensor | None = None, actions: Tensor | None = None,
+                   temperature: float = 1.0, seed: int | None = None, err: Tensor | None = None, env_name: str = "tsp",
+                   td=None) -> dict:
+    """One constructive decode of a heatmap, ``n_ants`` rows per instance, as ONE launch (the gradient back to ``heatmap``
+    as one more): NonAutoregressiveDecoder's rows under the reference's ``Sampling`` or ``Greedy`` strategy with
+    ``process_logits`` (utils/decoding.py:138-188) at every step. Every keyword, shape and returned key is
+    :func:`heatmap_rollout`'s; on top of it:
+
+    ``decode_type`` "sampling" (the Philox noise of ``seed``) or "greedy" (the argmax of the step's log-probs, the lowest
+    node on equal values; no noise, ``seed`` is not drawn). ``top_k`` / ``top_p``: the step's feasible logits are cut to
+    the ``top_k`` largest (ties at the k-th value stay) and then to the nucleus of mass ``top_p`` before the log-softmax,
+    so log-probs, ``log_likelihood`` and the gradient are those of the filtered distribution (a removed node gets gradient
+    0). Given ``actions`` are evaluated under the same filter: an action outside a step's kept set has log-prob -inf and
+    raises the reference's "Logprobs should not be -inf". With "sampling" and no filter this is :func:`heatmap_rollout`,
+    launch for launch."""
+    if decode_type not in ("sampling", "greedy"):
+        raise NotImplementedError(f"heatmap_decode serves decode_type 'sampling' and 'greedy', got {decode_type!r}")
+    greedy = decode_type == "greedy"
     for name, t in (("heatmap", heatmap), ("locs", locs)):
         if not t.is_cuda:
             raise NotImplementedError(f"heatmap_rollout runs inside the MI355X kernel (rl4co_aco_tsp) only: {name} on {t.device}")
@@ -173,10 +200,12 @@ def heatmap_rollout(heatmap: Tensor, locs: Tensor, *, n_ants: int, start_nodes: 
         if start_nodes.shape[0] != rows:
             raise ValueError(f"start_nodes must be [n_ants * B] = [{rows}], got {tuple(start_nodes.shape)}")
     if seed is None:
-        seed = int(torch.randint(0, 2**62, (1,)).item())
+        seed = 0 if greedy else int(torch.randint(0, 2**62, (1,)).item())
+    top_k, top_p = K.decoding_filter(top_k, top_p, n)
+    decode = {key: value for key, value in (("greedy", greedy), ("top_k", top_k), ("top_p", top_p)) if value}
     # err goes through as it is: with None the forward launch and the backward launch each read their own word
     logps, ll, acts, lengths, reward = _AntLogLikelihood.apply(heatmap, env_name, data, start_nodes, actions, n_ants,
-                                                               float(temperature), int(seed), err)
+                                                               float(temperature), int(seed), err, decode)
     out = {"actions": acts, "lengths": lengths, "logps": logps, "log_likelihood": ll, "reward": reward}
     if not depot:
         del out["lengths"]

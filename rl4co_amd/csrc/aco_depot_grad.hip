@@ -72,8 +72,11 @@ __host__ __device__ inline int node_bytes(int env, int N) { return 4 * node_vect
 // state [A, N] fp32, len [A] int32, pos [A, N] uint16, rounded up to 16 bytes
 __host__ __device__ inline int64_t table_bytes(int A, int N) { return ((int64_t)6 * A * N + (int64_t)4 * A + 15) & ~(int64_t)15; }
 
-template <int ENV, int KMAX, bool LDS>
-__global__ void __launch_bounds__(kThreads) aco_depot_grad_kernel(const rl4co_aco_depot_grad_args a) {
+// FILTER: each contribution runs over the kept set of its step under `o` (ant_system.h: filter_kept, the forward's text); false
+// reads no `o` and is the kernel without it
+template <int ENV, int KMAX, bool LDS, bool FILTER>
+__global__ void __launch_bounds__(kThreads) aco_depot_grad_kernel(const rl4co_aco_depot_grad_args a,
+                                                                  const rl4co_heatmap_decode_opts o) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool kCvrp = ENV == RL4CO_ENV_CVRP, kOp = ENV == RL4CO_ENV_OP;
 
@@ -224,6 +227,7 @@ __global__ void __launch_bounds__(kThreads) aco_depot_grad_kernel(const rl4co_ac
     }
     // one masked softmax: `feas` bit k of a lane: node lane + 64 k is feasible; `at` the action taken; `g` its upstream
     const auto contribute = [&](uint32_t feas, int at, float g) {
+      if constexpr (FILTER) feas = filter_kept<KMAX>(z, feas, N, lane, o.top_k, o.top_p);  // removed nodes get 0
       const auto z_of = [&](int k, int) { return z[k]; };
       const auto feas_of = [&](int k) { return ((feas >> k) & 1u) != 0; };
       bool nan_seen;
@@ -335,18 +339,23 @@ __global__ void __launch_bounds__(kThreads) aco_depot_grad_kernel(const rl4co_ac
   }
 }
 
-template <int ENV, bool LDS>
-int launch_grad(const rl4co_aco_depot_grad_args& a, int bytes, hipStream_t s) {
+template <int ENV, bool LDS, bool FILTER>
+int launch_grad(const rl4co_aco_depot_grad_args& a, const rl4co_heatmap_decode_opts& o, int bytes, hipStream_t s) {
   return grad_ladder(a.N, [&](auto kmax) {
-    return launch<aco_depot_grad_kernel<ENV, decltype(kmax)::value, LDS>>(a, bytes, s, a.B * a.row_split);
+    return launch<aco_depot_grad_kernel<ENV, decltype(kmax)::value, LDS, FILTER>>(a, bytes, s, a.B * a.row_split, o);
   });
 }
 
-template <int ENV>
-int launch_env(const rl4co_aco_depot_grad_args& a, hipStream_t s) {
+template <int ENV, bool FILTER>
+int launch_tier(const rl4co_aco_depot_grad_args& a, const rl4co_heatmap_decode_opts& o, hipStream_t s) {
   const int fixed = kScratchBytes + node_bytes(ENV, a.N);
-  if (a.scratch == nullptr) return launch_grad<ENV, true>(a, fixed + (int)table_bytes(a.n_ants, a.N), s);
-  return launch_grad<ENV, false>(a, fixed, s);
+  if (a.scratch == nullptr) return launch_grad<ENV, true, FILTER>(a, o, fixed + (int)table_bytes(a.n_ants, a.N), s);
+  return launch_grad<ENV, false, FILTER>(a, o, fixed, s);
+}
+
+template <int ENV>
+int launch_env(const rl4co_aco_depot_grad_args& a, const rl4co_heatmap_decode_opts& o, hipStream_t s) {
+  return decode_filter_on(o) ? launch_tier<ENV, true>(a, o, s) : launch_tier<ENV, false>(a, o, s);
 }
 
 }  // namespace
@@ -359,8 +368,16 @@ extern "C" int64_t rl4co_aco_depot_grad_scratch_bytes(int n_ants, int N) {
 }
 
 extern "C" int rl4co_aco_depot_logp_grad(const rl4co_aco_depot_grad_args* args, void* stream) {
+  const rl4co_heatmap_decode_opts off = {};
+  return rl4co_aco_depot_logp_grad_opts(args, &off, stream);
+}
+
+extern "C" int rl4co_aco_depot_logp_grad_opts(const rl4co_aco_depot_grad_args* args, const rl4co_heatmap_decode_opts* opts,
+                                              void* stream) {
   RL4CO_REQUIRE(args != nullptr);
   const rl4co_aco_depot_grad_args& a = *args;
+  if (const int rc = require_decode_opts(opts, nullptr)) return rc;
+  const rl4co_heatmap_decode_opts& o = *opts;  // (greedy is the forward's selector: nothing to differentiate)
   RL4CO_REQUIRE(a.env == RL4CO_ENV_CVRP || a.env == RL4CO_ENV_OP || a.env == RL4CO_ENV_PCTSP);
   RL4CO_REQUIRE(a.B >= 1);
   RL4CO_REQUIRE(a.N >= 2 && a.N <= kMaxNodes);
@@ -378,7 +395,7 @@ extern "C" int rl4co_aco_depot_logp_grad(const rl4co_aco_depot_grad_args* args, 
   RL4CO_REQUIRE(a.err != nullptr);
   RL4CO_REQUIRE(a.scratch != nullptr || (int64_t)a.n_ants * a.N <= kTableLdsEntries);  // above, the table lives in the caller's scratch
   hipStream_t s = rl4co::as_stream(stream);
-  if (a.env == RL4CO_ENV_CVRP) return launch_env<RL4CO_ENV_CVRP>(a, s);
-  if (a.env == RL4CO_ENV_OP) return launch_env<RL4CO_ENV_OP>(a, s);
-  return launch_env<RL4CO_ENV_PCTSP>(a, s);
+  if (a.env == RL4CO_ENV_CVRP) return launch_env<RL4CO_ENV_CVRP>(a, o, s);
+  if (a.env == RL4CO_ENV_OP) return launch_env<RL4CO_ENV_OP>(a, o, s);
+  return launch_env<RL4CO_ENV_PCTSP>(a, o, s);
 }

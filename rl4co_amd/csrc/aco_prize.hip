@@ -98,8 +98,9 @@ struct VecTerms {
   __device__ inline float seg(int t) const { return vec[t]; }
 };
 
-template <int ENV, bool LDS>
-__global__ void __launch_bounds__(kThreads) aco_prize_kernel(const rl4co_aco_prize_args a) {
+// OPTS: the step with the decode options `o` (ant_system.h: ant_step<true>); false reads no `o` and is the kernel without them
+template <int ENV, bool LDS, bool OPTS>
+__global__ void __launch_bounds__(kThreads) aco_prize_kernel(const rl4co_aco_prize_args a, const rl4co_heatmap_decode_opts o) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool kOp = ENV == RL4CO_ENV_OP;
 
@@ -208,8 +209,8 @@ __global__ void __launch_bounds__(kThreads) aco_prize_kernel(const rl4co_aco_pri
             float* alp = a.all_logps ? a.all_logps + (row * W + t) * N : nullptr;
             const float* lnz = a.ln_noise ? a.ln_noise + (((int64_t)it * W + t) * rows + row) * N : nullptr;
             float logp;
-            const int chosen = ant_step(Lm + cur * N, N, K, lane, feas, a.temperature, forced, alp, lnz, seed,
-                                        a.philox_offset + (uint64_t)it * W + t, (uint32_t)row, logp, errbits);
+            const int chosen = ant_step<OPTS>(Lm + cur * N, N, K, lane, feas, a.temperature, forced, alp, lnz, seed,
+                                              a.philox_offset + (uint64_t)it * W + t, (uint32_t)row, logp, errbits, &o);
             const uint32_t could = __shfl(feas, chosen & 63, 64);
             const uint32_t was = __shfl(vis, chosen & 63, 64);
             if (!((could >> (chosen >> 6)) & 1u)) errbits |= RL4CO_EBIT_INFEASIBLE;  // a forced node that is infeasible
@@ -287,12 +288,16 @@ __global__ void __launch_bounds__(kThreads) aco_prize_kernel(const rl4co_aco_pri
 }
 
 template <int ENV>
-int launch_env(const rl4co_aco_prize_args& a, hipStream_t s) {
+int launch_env(const rl4co_aco_prize_args& a, const rl4co_heatmap_decode_opts& o, hipStream_t s) {
   const bool lds = a.N <= rl4co_aco_prize_lds_nodes(ENV);
   RL4CO_REQUIRE(lds || a.logits_scratch != nullptr);  // above the LDS tier L / delta live in the caller's [B,N,N] scratch
   const int bytes = (int)aco_lds_bytes(ENV, lds, a.N);
   const int grid = a.n_workgroups > 0 ? a.n_workgroups : a.B;
-  return lds ? launch<aco_prize_kernel<ENV, true>>(a, bytes, s, grid) : launch<aco_prize_kernel<ENV, false>>(a, bytes, s, grid);
+  if (decode_opts_on(o))
+    return lds ? launch<aco_prize_kernel<ENV, true, true>>(a, bytes, s, grid, o)
+               : launch<aco_prize_kernel<ENV, false, true>>(a, bytes, s, grid, o);
+  return lds ? launch<aco_prize_kernel<ENV, true, false>>(a, bytes, s, grid, o)
+             : launch<aco_prize_kernel<ENV, false, false>>(a, bytes, s, grid, o);
 }
 
 }  // namespace
@@ -303,10 +308,16 @@ extern "C" int rl4co_aco_prize_lds_nodes(int env) {
 }
 
 extern "C" int rl4co_aco_prize(const rl4co_aco_prize_args* args, void* stream) {
+  const rl4co_heatmap_decode_opts off = {};
+  return rl4co_aco_prize_opts(args, &off, stream);
+}
+
+extern "C" int rl4co_aco_prize_opts(const rl4co_aco_prize_args* args, const rl4co_heatmap_decode_opts* opts, void* stream) {
   RL4CO_REQUIRE(args != nullptr);
   const rl4co_aco_prize_args& a = *args;
   RL4CO_REQUIRE(a.env == RL4CO_ENV_OP || a.env == RL4CO_ENV_PCTSP);
   if (const int rc = require_common(a)) return rc;
+  if (const int rc = require_decode_opts(opts, a.ln_noise)) return rc;
   RL4CO_REQUIRE(a.n_workgroups >= 0 && a.n_workgroups <= a.B);
   const bool sample = (a.phases & RL4CO_ACO_SAMPLE) != 0;
   RL4CO_REQUIRE(sample ? a.T == a.N : a.T >= 2);  // sampled rows are W = N wide; UPDATE alone takes any width
@@ -315,5 +326,5 @@ extern "C" int rl4co_aco_prize(const rl4co_aco_prize_args* args, void* stream) {
   RL4CO_REQUIRE(!sample || a.env != RL4CO_ENV_PCTSP || a.penalty != nullptr);
   RL4CO_REQUIRE(!sample || a.lengths != nullptr);
   hipStream_t s = rl4co::as_stream(stream);
-  return a.env == RL4CO_ENV_OP ? launch_env<RL4CO_ENV_OP>(a, s) : launch_env<RL4CO_ENV_PCTSP>(a, s);
+  return a.env == RL4CO_ENV_OP ? launch_env<RL4CO_ENV_OP>(a, *opts, s) : launch_env<RL4CO_ENV_PCTSP>(a, *opts, s);
 }

@@ -57,8 +57,9 @@ __host__ __device__ inline int64_t aco_lds_bytes(bool lds, int N) {
   return kScratchBytes + kTourBytes + (lds ? (int64_t)8 * N * N : 0);
 }
 
-template <bool LDS>
-__global__ void __launch_bounds__(kThreads) aco_tsp_kernel(const rl4co_aco_tsp_args a) {
+// OPTS: the step with the decode options `o` (ant_system.h: ant_step<true>); false reads no `o` and is the kernel without them
+template <bool LDS, bool OPTS>
+__global__ void __launch_bounds__(kThreads) aco_tsp_kernel(const rl4co_aco_tsp_args a, const rl4co_heatmap_decode_opts o) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -117,8 +118,8 @@ __global__ void __launch_bounds__(kThreads) aco_tsp_kernel(const rl4co_aco_tsp_a
           float* alp = a.all_logps ? a.all_logps + row * NN + (int64_t)t * N : nullptr;
           const float* lnz = a.ln_noise ? a.ln_noise + (((int64_t)it * (N - 1) + (t - 1)) * rows + row) * N : nullptr;
           float logp;
-          const int chosen = ant_step(Lm + cur * N, N, K, lane, ~vis, a.temperature, forced, alp, lnz, seed,
-                                      a.philox_offset + (uint64_t)it * N + t, (uint32_t)row, logp, errbits);
+          const int chosen = ant_step<OPTS>(Lm + cur * N, N, K, lane, ~vis, a.temperature, forced, alp, lnz, seed,
+                                            a.philox_offset + (uint64_t)it * N + t, (uint32_t)row, logp, errbits, &o);
           const uint32_t was = __shfl(vis, chosen & 63, 64);
           if ((was >> (chosen >> 6)) & 1u) errbits |= RL4CO_EBIT_INFEASIBLE;  // a forced node that was visited already
           if ((chosen & 63) == lane) vis |= 1u << (chosen >> 6);
@@ -167,14 +168,23 @@ __global__ void __launch_bounds__(kThreads) aco_tsp_kernel(const rl4co_aco_tsp_a
 extern "C" int rl4co_aco_tsp_lds_nodes(void) { return lds_nodes(aco_lds_bytes); }
 
 extern "C" int rl4co_aco_tsp(const rl4co_aco_tsp_args* args, void* stream) {
+  const rl4co_heatmap_decode_opts off = {};
+  return rl4co_aco_tsp_opts(args, &off, stream);
+}
+
+extern "C" int rl4co_aco_tsp_opts(const rl4co_aco_tsp_args* args, const rl4co_heatmap_decode_opts* opts, void* stream) {
   RL4CO_REQUIRE(args != nullptr);
   const rl4co_aco_tsp_args& a = *args;
   if (const int rc = require_common(a)) return rc;
+  if (const int rc = require_decode_opts(opts, a.ln_noise)) return rc;
+  const rl4co_heatmap_decode_opts& o = *opts;
   const bool sample = (a.phases & RL4CO_ACO_SAMPLE) != 0;
   RL4CO_REQUIRE(!sample || (a.log_heuristic != nullptr && a.start_nodes != nullptr));
   const bool lds = a.N <= rl4co_aco_tsp_lds_nodes();
   RL4CO_REQUIRE(lds || a.logits_scratch != nullptr);  // above the LDS tier L / delta live in the caller's [B,N,N] scratch
   hipStream_t s = rl4co::as_stream(stream);
   const int bytes = (int)aco_lds_bytes(lds, a.N);
-  return lds ? launch<aco_tsp_kernel<true>>(a, bytes, s) : launch<aco_tsp_kernel<false>>(a, bytes, s);
+  if (decode_opts_on(o))
+    return lds ? launch<aco_tsp_kernel<true, true>>(a, bytes, s, 0, o) : launch<aco_tsp_kernel<false, true>>(a, bytes, s, 0, o);
+  return lds ? launch<aco_tsp_kernel<true, false>>(a, bytes, s, 0, o) : launch<aco_tsp_kernel<false, false>>(a, bytes, s, 0, o);
 }

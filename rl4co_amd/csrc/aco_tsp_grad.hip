@@ -45,8 +45,11 @@ using namespace rl4co::aco;  // ant_system.h: the constants, check_indices, log_
 constexpr int kPosLdsEntries = 16384;
 constexpr uint16_t kNoPos = 0xffff;
 
-template <int KMAX, bool LDS>
-__global__ void __launch_bounds__(kThreads) aco_tsp_grad_kernel(const rl4co_aco_tsp_grad_args a) {
+// FILTER: each contribution runs over the kept set of its step under `o` (ant_system.h: filter_kept, the forward's text); false
+// reads no `o` and is the kernel without it
+template <int KMAX, bool LDS, bool FILTER>
+__global__ void __launch_bounds__(kThreads) aco_tsp_grad_kernel(const rl4co_aco_tsp_grad_args a,
+                                                                const rl4co_heatmap_decode_opts o) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -110,6 +113,7 @@ __global__ void __launch_bounds__(kThreads) aco_tsp_grad_kernel(const rl4co_aco_
           hit |= (pn == pi + 1 ? 1u : 0u) << k;
         }
       }
+      if constexpr (FILTER) feas = filter_kept<KMAX>(z, feas, N, lane, o.top_k, o.top_p);  // removed nodes get 0
       const auto z_of = [&](int k, int) { return z[k]; };
       const auto feas_of = [&](int k) { return ((feas >> k) & 1u) != 0; };
       bool nan_seen;
@@ -137,10 +141,10 @@ __global__ void __launch_bounds__(kThreads) aco_tsp_grad_kernel(const rl4co_aco_
   }
 }
 
-template <bool LDS>
-int launch_grad(const rl4co_aco_tsp_grad_args& a, int bytes, hipStream_t s) {
+template <bool LDS, bool FILTER>
+int launch_grad(const rl4co_aco_tsp_grad_args& a, const rl4co_heatmap_decode_opts& o, int bytes, hipStream_t s) {
   return grad_ladder(a.N, [&](auto kmax) {
-    return launch<aco_tsp_grad_kernel<decltype(kmax)::value, LDS>>(a, bytes, s, a.B * a.row_split);
+    return launch<aco_tsp_grad_kernel<decltype(kmax)::value, LDS, FILTER>>(a, bytes, s, a.B * a.row_split, o);
   });
 }
 
@@ -149,8 +153,16 @@ int launch_grad(const rl4co_aco_tsp_grad_args& a, int bytes, hipStream_t s) {
 extern "C" int rl4co_aco_tsp_grad_lds_entries(void) { return kPosLdsEntries; }
 
 extern "C" int rl4co_aco_tsp_logp_grad(const rl4co_aco_tsp_grad_args* args, void* stream) {
+  const rl4co_heatmap_decode_opts off = {};
+  return rl4co_aco_tsp_logp_grad_opts(args, &off, stream);
+}
+
+extern "C" int rl4co_aco_tsp_logp_grad_opts(const rl4co_aco_tsp_grad_args* args, const rl4co_heatmap_decode_opts* opts,
+                                            void* stream) {
   RL4CO_REQUIRE(args != nullptr);
   const rl4co_aco_tsp_grad_args& a = *args;
+  if (const int rc = require_decode_opts(opts, nullptr)) return rc;
+  const rl4co_heatmap_decode_opts& o = *opts;  // (greedy is the forward's selector: nothing to differentiate)
   RL4CO_REQUIRE(a.B >= 1);
   RL4CO_REQUIRE(a.N >= 2 && a.N <= kMaxNodes);
   RL4CO_REQUIRE(a.n_ants >= 1);
@@ -164,5 +176,7 @@ extern "C" int rl4co_aco_tsp_logp_grad(const rl4co_aco_tsp_grad_args* args, void
   const bool lds = a.pos_scratch == nullptr;
   RL4CO_REQUIRE(!lds || (int64_t)a.n_ants * a.N <= kPosLdsEntries);  // above, pos lives in the caller's scratch
   hipStream_t s = rl4co::as_stream(stream);
-  return lds ? launch_grad<true>(a, kScratchBytes + 2 * a.n_ants * a.N, s) : launch_grad<false>(a, kScratchBytes, s);
+  const int bytes = lds ? kScratchBytes + 2 * a.n_ants * a.N : kScratchBytes;
+  if (decode_filter_on(o)) return lds ? launch_grad<true, true>(a, o, bytes, s) : launch_grad<false, true>(a, o, bytes, s);
+  return lds ? launch_grad<true, false>(a, o, bytes, s) : launch_grad<false, false>(a, o, bytes, s);
 }

@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "rl4co_math.h"
+#include "topkp.h"
 
 namespace rl4co::aco {
 
@@ -100,6 +101,112 @@ __device__ inline float log_softmax_lse(int N, int K, int lane, ZFn z, FeasFn fe
   return rl4co_logf(zsum);
 }
 
+// The kept set of one step under top-k / top-p (utils/decoding.py:109-188), for one wave, as bits: z[k] is the logit of node
+// lane + 64 k, already divided by the temperature, read only where bit k of `feas` is set and the node is below N. Returns
+// `feas` (cut to the nodes below N) without the bits the filter removes. This is topkp.h's topkp_filter in register form:
+// a lane holds its nodes' keys and masses in registers instead of walking a list in LDS, the list position c is the node,
+// and what is removed leaves the bit mask instead of becoming -inf. Restated from topkp.h: lines 37-54 (top-k: the k-th
+// largest topkp_key by 32 counting passes with bfly_i_sum, keys < tau removed, ties at tau stay; fewer than k feasible nodes
+// remove nothing; a feasible -inf counts, so tau can be -inf's key and nothing is below it), lines 55-63 (`mass`) and lines
+// 64-89 (top-p over the survivors in (z, node) ascending order: removed while the cumulative mass is <= (1 - p) Z, the
+// threshold kept under Z so that the largest logit always stays). The masses are rl4co_expf(z - zmax) and every sum of them
+// runs lane-strided over ascending k and then through the butterfly, the order of log_softmax_lse. Stated once for ant_step
+// and for the two backward kernels, which therefore see exactly the set the forward sampled from.
+template <int KMAX>
+__device__ inline uint32_t filter_kept(const float (&z)[KMAX], uint32_t feas, int N, int lane, int top_k, float top_p) {
+  uint32_t kept = 0u;
+  uint32_t key[KMAX];
+  int mine = 0;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    const bool live = lane + 64 * k < N && ((feas >> k) & 1u) != 0;
+    key[k] = live ? rl4co::topkp_key(z[k]) : 0u;
+    if (live) {
+      kept |= 1u << k;
+      ++mine;
+    }
+  }
+  if (top_k > 0 && top_k < rl4co::bfly_i_sum(mine)) {
+    // tau = largest T with #{n : key_n >= T} >= k = the key of the k-th largest z, counted with multiplicity
+    uint32_t tau = 0;
+#pragma unroll 1
+    for (int b = 31; b >= 0; --b) {
+      const uint32_t cand = tau | (1u << b);
+      int n = 0;
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) n += (((kept >> k) & 1u) && key[k] >= cand) ? 1 : 0;
+      if (rl4co::bfly_i_sum(n) >= top_k) tau = cand;
+    }
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (key[k] < tau) kept &= ~(1u << k);  // the reference removes logits < tau: ties at tau stay
+  }
+  if (top_p > 0.0f && top_p < 1.0f) {
+    float zmax = kNegInf;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if ((kept >> k) & 1u) zmax = fmaxf(zmax, z[k]);
+    zmax = rl4co::bfly_max<1, 64>(zmax);
+    if (zmax > kNegInf) {  // (wave-uniform) else every kept logit is -inf (or NaN): nothing to order
+      float e[KMAX];
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) e[k] = ((kept >> k) & 1u) ? rl4co_expf(z[k] - zmax) : 0.0f;
+      const auto mass = [&](uint32_t below, uint32_t at, int upto) {  // sum of e over key < below, or key == at and n <= upto
+        float s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+          if ((kept >> k) & 1u) s = s + ((key[k] < below || (key[k] == at && lane + 64 * k <= upto)) ? e[k] : 0.0f);
+        return rl4co::bfly_sum<1, 64>(s);
+      };
+      // nodes ordered by (z, n) ascending; n is removed iff A_n = mass of the nodes up to n <= (1 - p) Z
+      const float zall = mass(0xFFFFFFFFu, 0xFFFFFFFFu, 0x7fffffff);
+      const float thr = fminf((1.0f - top_p) * zall, __uint_as_float(__float_as_uint(zall) - 1u));
+      uint32_t cut = 0;  // largest T with mass(key < T) <= thr: below it all removed, above it all kept
+#pragma unroll 1
+      for (int b = 31; b >= 0; --b) {
+        const uint32_t cand = cut | (1u << b);
+        if (mass(cand, 0u, -1) <= thr) cut = cand;
+      }
+      int lo = -1, hi = N;  // the tie group at the cut, by node: the largest lo with A(lo) <= thr
+#pragma unroll 1
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (mass(cut, cut, mid) <= thr) lo = mid; else hi = mid;
+      }
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (key[k] < cut || (key[k] == cut && lane + 64 * k <= lo)) kept &= ~(1u << k);
+    }
+  }
+  return kept;
+}
+
+// whether the options ask for anything (all off: the entry points launch the instantiation without them)
+__host__ __device__ inline bool decode_opts_on(const rl4co_heatmap_decode_opts& o) {
+  return o.greedy != 0 || o.top_k > 0 || (o.top_p > 0.0f && o.top_p < 1.0f);
+}
+__host__ __device__ inline bool decode_filter_on(const rl4co_heatmap_decode_opts& o) {
+  return o.top_k > 0 || (o.top_p > 0.0f && o.top_p < 1.0f);
+}
+
+// filter_kept on row `lrow` of L: the lane's logits into KMAX registers (the quotient ant_step forms), KMAX >= K
+template <int KMAX>
+__device__ inline uint32_t filter_kept_row(const float* lrow, int N, int lane, uint32_t feas, float temp, int top_k,
+                                           float top_p) {
+  float z[KMAX];
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    const int n = lane + 64 * k;
+    float v = 0.0f;
+    if (n < N && ((feas >> k) & 1u)) {
+      v = lrow[n];
+      if (temp != 1.0f) v = v / temp;
+    }
+    z[k] = v;
+  }
+  return filter_kept<KMAX>(z, feas, N, lane, top_k, top_p);
+}
+
 // One sampling step of one wave: row `lrow` of L over the nodes of `feas` (bit k of a lane: node lane + 64 k is feasible;
 // bits of nodes >= N are not read), divided by `temp` when it is not 1, log-softmax in the project's order (max butterfly,
 // lane-strided sum of rl4co_expf, butterfly, rl4co_logf), then the argmax over feasible n of lp[n] - ln_noise[n], lowest
@@ -109,9 +216,23 @@ __device__ inline float log_softmax_lse(int N, int K, int lane, ZFn z, FeasFn fe
 // log-prob in `logp`; ORs into `errbits` RL4CO_EBIT_NAN_LOGIT (a feasible logit is NaN), RL4CO_EBIT_INFEASIBLE (every
 // feasible logit is -inf or NaN: the lowest feasible node is taken) and RL4CO_EBIT_NEG_INF_LOGP. The caller checks a forced
 // node against its own mask, updates its state and stores.
+// OPTS (a compile-time choice; false is the step above and reads no `o`): with top_k / top_p the feasible set is first cut
+// to filter_kept's and everything after runs on the kept set, so a removed node has lp = -inf in `alp` and a forced node
+// outside the kept set gets logp = -inf and raises RL4CO_EBIT_NEG_INF_LOGP (decoding.py:56). With `greedy` the key is lp
+// itself: the argmax over the kept set, lowest node on equal values; no noise is read and no Philox word is drawn.
+template <bool OPTS = false>
 __device__ inline int ant_step(const float* lrow, int N, int K, int lane, uint32_t feas, float temp, int forced, float* alp,
                                const float* lnz, unsigned long long seed, uint64_t counter, uint32_t row, float& logp,
-                               uint32_t& errbits) {
+                               uint32_t& errbits, const rl4co_heatmap_decode_opts* o = nullptr) {
+  if constexpr (OPTS) {
+    if (decode_filter_on(*o)) {  // (uniform over the launch)
+      if (K <= 1) feas = filter_kept_row<1>(lrow, N, lane, feas, temp, o->top_k, o->top_p);
+      else if (K <= 2) feas = filter_kept_row<2>(lrow, N, lane, feas, temp, o->top_k, o->top_p);
+      else if (K <= 4) feas = filter_kept_row<4>(lrow, N, lane, feas, temp, o->top_k, o->top_p);
+      else if (K <= 8) feas = filter_kept_row<8>(lrow, N, lane, feas, temp, o->top_k, o->top_p);
+      else feas = filter_kept_row<16>(lrow, N, lane, feas, temp, o->top_k, o->top_p);
+    }
+  }
   const auto z_of = [&](int, int n) {
     float z = lrow[n];
     if (temp != 1.0f) z = z / temp;
@@ -142,8 +263,15 @@ __device__ inline int ant_step(const float* lrow, int N, int K, int lane, uint32
     if (forced >= 0) {
       if (n == forced) blp = lp;
     } else {
-      const float ln = lnz ? lnz[n] : rl4co_logf(rl4co_exp1_noise(seed, counter, row, (uint32_t)n));
-      float key = lp - ln;  // multinomial(p, 1) == argmax(log p - log Exp(1))
+      float key;
+      bool greedy = false;
+      if constexpr (OPTS) greedy = o->greedy != 0;
+      if (greedy) {
+        key = lp;
+      } else {
+        const float ln = lnz ? lnz[n] : rl4co_logf(rl4co_exp1_noise(seed, counter, row, (uint32_t)n));
+        key = lp - ln;  // multinomial(p, 1) == argmax(log p - log Exp(1))
+      }
       if (key != key) key = kNegInf;
       if (bi == kEmpty || key > best) {  // ascending nodes, strict '>': equal keys keep the lower node
         best = key;
@@ -262,9 +390,9 @@ inline int lds_nodes(BytesFn lds_bytes) {
 }
 
 // one workgroup per instance with `lds_bytes` of dynamic LDS; `grid` > 0: that many workgroups (a kernel that strides
-// over the instances itself)
-template <auto Kernel, typename Args>
-int launch(const Args& a, int lds_bytes, hipStream_t stream, int grid = 0) {
+// over the instances itself); `more`: the kernel's arguments behind `a` (the decode options)
+template <auto Kernel, typename Args, typename... More>
+int launch(const Args& a, int lds_bytes, hipStream_t stream, int grid = 0, const More&... more) {
   hipFuncAttributes fa;
   RL4CO_HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(Kernel)));
   RL4CO_REQUIRE((int64_t)fa.sharedSizeBytes <= kStaticLds);  // the budget behind *_lds_nodes() holds
@@ -272,7 +400,7 @@ int launch(const Args& a, int lds_bytes, hipStream_t stream, int grid = 0) {
     RL4CO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       lds_bytes));
   }
-  hipLaunchKernelGGL(Kernel, dim3(grid > 0 ? grid : a.B), dim3(kThreads), lds_bytes, stream, a);
+  hipLaunchKernelGGL(Kernel, dim3(grid > 0 ? grid : a.B), dim3(kThreads), lds_bytes, stream, a, more...);
   RL4CO_HIP_TRY(hipGetLastError());
   return RL4CO_OK;
 }
@@ -296,6 +424,18 @@ int require_common(const Args& a) {
   RL4CO_REQUIRE(a.reward != nullptr);
   RL4CO_REQUIRE(!update || (a.final_reward != nullptr && a.final_actions != nullptr));
   RL4CO_REQUIRE(a.err != nullptr);
+  return RL4CO_OK;
+}
+
+// rl4co_heatmap_decode_opts as every *_opts entry point takes it; `ln_noise`: the caller's noise (nullptr: none, the
+// gradients)
+inline int require_decode_opts(const rl4co_heatmap_decode_opts* o, const void* ln_noise) {
+  RL4CO_REQUIRE(o != nullptr);
+  RL4CO_REQUIRE(o->greedy == 0 || o->greedy == 1);
+  RL4CO_REQUIRE(o->top_k >= 0);
+  RL4CO_REQUIRE(o->top_p >= 0.0f && o->top_p <= 1.0f);
+  RL4CO_REQUIRE(o->reserved0 == 0);
+  RL4CO_REQUIRE(!(o->greedy != 0 && ln_noise != nullptr));  // greedy reads no noise: a caller's noise is a mistake
   return RL4CO_OK;
 }
 

@@ -7,6 +7,7 @@ There is no CPU path: a non-CUDA tensor is an error.
 from __future__ import annotations
 
 import ctypes as C
+import inspect
 from typing import Callable, NamedTuple
 
 import torch
@@ -1080,20 +1081,46 @@ def aco_family(env: str) -> AcoFamily:
     return next(fam for fam in ACO_FAMILIES if env in fam.envs)
 
 
+def heatmap_decode_opts(greedy, top_k, top_p, n: int):
+    """``rl4co_heatmap_decode_opts`` of a decode over ``n`` nodes, ``top_k`` / ``top_p`` normalised by
+    :func:`decoding_filter`; None when every option is off (the launch then goes to the symbol without ``_opts``)."""
+    k, p = decoding_filter(top_k, top_p, n)
+    if not (greedy or k or p):
+        return None
+    return _lib.HeatmapDecodeOpts(greedy=int(bool(greedy)), top_k=k, top_p=p, reserved0=0)
+
+
 def aco_search(env: str, pheromone: Tensor, **kw) -> dict:
-    """:func:`aco_tsp`, :func:`aco_cvrp` or :func:`aco_prize`, whichever serves ``env``."""
+    """:func:`aco_tsp`, :func:`aco_cvrp` or :func:`aco_prize`, whichever serves ``env``. ``greedy=``, ``top_k=`` and
+    ``top_p=`` (utils/decoding.py:109-188 at every step; ``greedy``: the argmax of the log-probs, no noise) go to the
+    family's ``*_opts`` symbol when any of them is on, with the binding's own keywords and defaults."""
     fam = aco_family(env)
-    return globals()[fam.name](pheromone, **kw, **({"env": env} if "env" in fam.scalars else {}))
+    binding = globals()[fam.name]
+    opts = heatmap_decode_opts(kw.pop("greedy", False), kw.pop("top_k", 0), kw.pop("top_p", 0.0), pheromone.shape[-1])
+    if "env" in fam.scalars:
+        kw["env"] = env
+    if opts is None:
+        return binding(pheromone, **kw)
+    bound = inspect.signature(binding).bind(pheromone, **kw)
+    bound.apply_defaults()
+    if opts.greedy and bound.arguments.get("ln_noise") is not None:
+        raise ValueError("greedy reads no noise: ln_noise must be None")
+    return _aco_search(fam, **{"env": env, **bound.arguments}, decode_opts=opts)
 
 
-def _aco_launch(symbol: str, a, values: dict, err: Tensor | None, dev) -> None:
+def _aco_launch(symbol: str, a, values: dict, err: Tensor | None, dev, opts=None) -> None:
     """Fill the struct ``a`` field by field from ``values`` (tensors as pointers, a pointer without a value NULL), launch and
-    check. With ``err`` the sticky bits are OR-ed into the caller's word; without, the launch's own word is read back."""
+    check. With ``err`` the sticky bits are OR-ed into the caller's word; without, the launch's own word is read back.
+    ``opts``: a ``HeatmapDecodeOpts`` for ``symbol + "_opts"``."""
     own = err is None
     values["err"] = new_error_word(dev) if own else _dev(err, torch.int32, "err")
     for name, ctype in a._fields_:
         setattr(a, name, _ptr(values.get(name)) if ctype is C.c_void_p else values[name])
-    st = getattr(_lib.lib(), symbol)(C.byref(a), _stream())
+    if opts is None:
+        st = getattr(_lib.lib(), symbol)(C.byref(a), _stream())
+    else:
+        symbol += "_opts"
+        st = getattr(_lib.lib(), symbol)(C.byref(a), C.byref(opts), _stream())
     _lib.check(st, symbol)
     if own:
         raise_if_error(values["err"])
@@ -1102,8 +1129,9 @@ def _aco_launch(symbol: str, a, values: dict, err: Tensor | None, dev) -> None:
 def _aco_search(fam: AcoFamily, pheromone, *, n_ants, phases, iterations, log_heuristic, alpha, beta, decay, Q, temperature,
                 ln_noise, philox_seed, philox_offset, philox_seed_dev, forced_actions, actions, reward, final_reward,
                 final_actions, has_best, all_logps, record_iterations, err, env, start_nodes=None, final_iteration=None,
-                iteration_base=0, n_workgroups=0, **given) -> dict:
-    """The one body of the three search bindings; ``given``: the family's instance tensors by keyword."""
+                iteration_base=0, n_workgroups=0, decode_opts=None, **given) -> dict:
+    """The one body of the three search bindings; ``given``: the family's instance tensors by keyword; ``decode_opts``:
+    :func:`heatmap_decode_opts` (None: the symbol without them)."""
     who, d = fam.name, "n" if fam.ragged else "N"
     if env not in fam.envs:
         raise NotImplementedError(f"{who} ({fam.symbol}) serves {sorted(fam.envs)}, got env = {env!r}")
@@ -1192,7 +1220,7 @@ def _aco_search(fam: AcoFamily, pheromone, *, n_ants, phases, iterations, log_he
                   philox_seed_dev=philox_seed_dev, log_heuristic=log_heuristic, pheromone=pheromone, start_nodes=start_nodes,
                   ln_noise=ln_noise, forced_actions=forced_actions, logits_scratch=scratch, **given,
                   **{key: extra[key] for key in fam.scalars})
-    _aco_launch(fam.symbol, fam.args(), values, err, dev)
+    _aco_launch(fam.symbol, fam.args(), values, err, dev, decode_opts)
     return out
 
 
@@ -1335,14 +1363,28 @@ def aco_grad_family(env: str) -> AcoGradFamily:
 
 
 def aco_logp_grad(env: str, heatmap: Tensor, actions: Tensor, grad_ll: Tensor, **kw) -> Tensor:
-    """:func:`aco_tsp_logp_grad` or :func:`aco_depot_logp_grad`, whichever serves ``env``."""
+    """:func:`aco_tsp_logp_grad` or :func:`aco_depot_logp_grad`, whichever serves ``env``. ``top_k=`` / ``top_p=``: the
+    forward's filter — each contribution runs over its step's kept set, removed nodes get 0 (the family's ``*_opts``
+    symbol); ``greedy=`` is accepted and changes nothing (it is the forward's selector)."""
     fam = aco_grad_family(env)
-    return globals()[fam.name](heatmap, actions, grad_ll, **kw, **({"env": env} if fam.depot else {}))
+    binding = globals()[fam.name]
+    kw.pop("greedy", None)
+    opts = heatmap_decode_opts(False, kw.pop("top_k", 0), kw.pop("top_p", 0.0), heatmap.shape[-1])
+    if fam.depot:
+        kw["env"] = env
+    if opts is None:
+        return binding(heatmap, actions, grad_ll, **kw)
+    bound = inspect.signature(binding).bind(heatmap, actions, grad_ll, **kw)
+    bound.apply_defaults()
+    args = {"env": env, **bound.arguments}
+    args["in_scratch"] = args.pop("table_in_scratch" if fam.depot else "pos_in_scratch")
+    return _aco_logp_grad(fam, **args, decode_opts=opts)
 
 
 def _aco_logp_grad(fam: AcoGradFamily, heatmap, actions, grad_ll, *, env, grad_steps, temperature, row_split, in_scratch, err,
-                   multistart=False, **given) -> Tensor:
-    """The one body of the two gradient bindings; ``given``: the instance tensors by keyword."""
+                   multistart=False, decode_opts=None, **given) -> Tensor:
+    """The one body of the two gradient bindings; ``given``: the instance tensors by keyword; ``decode_opts``:
+    :func:`heatmap_decode_opts` (None: the symbol without them)."""
     who, depot = fam.name, fam.depot
     d, wd = ("n", "W") if depot else ("N", "N")
     if env not in fam.envs:
@@ -1396,7 +1438,7 @@ def _aco_logp_grad(fam: AcoGradFamily, heatmap, actions, grad_ll, *, env, grad_s
                   temperature=float(temperature), reserved0=0, heatmap=heatmap, actions=actions, grad_ll=grad_ll,
                   grad_steps=grad_steps, grad_heatmap=grad)
     values[field] = alloc(b * int(row_split), n_ants, n, dev) if in_scratch else None
-    _aco_launch(fam.symbol, fam.args(), values, err, dev)
+    _aco_launch(fam.symbol, fam.args(), values, err, dev, decode_opts)
     return grad
 
 

@@ -15,7 +15,9 @@ refused with ``NotImplementedError``: there is no torch fall-back. ``TrainableNA
 trains (TSP): in ``.train()`` the GNN stack runs on batch statistics, forward and backward, on csrc/nargnn_train.hip;
 ``TrainableNARGNNDepotEncoder`` is the same for ``NARGNNDepotEncoder`` (CVRP, OP, PCTSP) on that file's depot-graph kernels.
 ``GFACSEncoder`` / ``GFACSDepotEncoder`` add GFACS's log-partition head (models/zoo/gfacs/encoder.py) on csrc/nargnn_logz.hip,
-``GFACSPolicy`` is the reference's policy over them (models/zoo/gfacs/policy.py)."""
+``GFACSPolicy`` is the reference's policy over them (models/zoo/gfacs/policy.py). ``NARGNNPolicy`` (models/zoo/nargnn/policy.py)
+is the family's base model: the trainable encoder and :func:`rl4co_amd.aco.heatmap_decode`, with greedy and top-k / top-p
+decoding for ``phase="val"`` / ``"test"``."""
 from __future__ import annotations
 
 from functools import partial
@@ -24,7 +26,7 @@ import torch
 from torch import Tensor, nn
 
 from . import kernels as K
-from .aco import AntSystem, heatmap_rollout
+from .aco import AntSystem, heatmap_decode, heatmap_rollout
 
 SMALL_VALUE = 1e-12  # encoder.py:81-82: the fp32 heatmap's guard against log(0)
 
@@ -862,6 +864,145 @@ class NonAutoregressivePolicy(nn.Module):
         out = {"reward": rolled["reward"], "log_likelihood": rolled["log_likelihood"]}
         if return_actions:
             out["actions"] = rolled["actions"]
+        if return_hidden:
+            out["hidden"] = hidden
+        if return_init_embeds:
+            out["init_embeds"] = init_embeds
+        return out
+
+
+_DECODE_TYPES = ("greedy", "sampling", "multistart_greedy", "multistart_sampling")
+
+
+class NARGNNPolicy(nn.Module):
+    """models/zoo/nargnn/policy.py:15-105 with the reference's constructor: the plain heatmap model. With ``encoder=None``
+    it builds :class:`TrainableNARGNNEncoder` (``tsp``) or :class:`TrainableNARGNNDepotEncoder` (``cvrp``, ``op``,
+    ``pctsp``), so a reference ``NARGNNPolicy.state_dict()`` loads with ``strict=True``. ``temperature``,
+    ``tanh_clipping`` and ``mask_logits`` are ``ConstructivePolicy``'s keywords.
+
+    ``forward`` is ``ConstructivePolicy.forward`` (constructive/base.py:154-263) with the decode loop as ONE launch of
+    :func:`rl4co_amd.aco.heatmap_decode` (and one more for the gradient). Served: ``phase`` "train", "val" and "test" with
+    the reference's defaults (``multistart_sampling``, then ``multistart_greedy`` twice); ``decode_type`` "greedy",
+    "sampling", "multistart_greedy" and "multistart_sampling"; ``multistart`` / ``num_starts`` (tsp and cvrp; None: the
+    environment's ``get_num_starts``) with ``select_start_nodes_fn``; ``multisample`` / ``num_samples`` (cvrp, op, pctsp);
+    neither on a depot graph: one row per instance from the depot; ``select_best`` (the best row of every instance, picked on
+    the device); ``temperature``, ``top_k``, ``top_p``; ``actions=`` (evaluate: ant-major rows [n * B, W], with multistart
+    column 0 is the start); ``calc_reward``, ``return_actions``, ``return_hidden``, ``return_init_embeds`` and
+    ``return_sum_log_likelihood``. Rows are ant-major (the reference's batchify) and W wide, zero-filled after each row's
+    length. Refused by name before the encoder runs (``NotImplementedError``): a multistart decode type on ``op`` / ``pctsp``
+    (every ant starts at the depot), ``tsp`` without multistart (the ants' kernel starts a tour from a given node),
+    ``tanh_clipping``, ``mask_logits=False``, ``return_entropy``, beam search and other decode types, unknown decoding
+    keywords, a ``decoder=`` and CPU tensors."""
+
+    def __init__(self, encoder: nn.Module | None = None, decoder=None, embed_dim: int = 64, env_name: str = "tsp",
+                 init_embedding: nn.Module | None = None, edge_embedding: nn.Module | None = None,
+                 graph_network: nn.Module | None = None, heatmap_generator: nn.Module | None = None,
+                 num_layers_heatmap_generator: int = 5, num_layers_graph_encoder: int = 15, act_fn="silu", agg_fn="mean",
+                 linear_bias: bool = True, train_decode_type: str = "multistart_sampling",
+                 val_decode_type: str = "multistart_greedy", test_decode_type: str = "multistart_greedy",
+                 **constructive_policy_kw):
+        super().__init__()
+        if decoder is not None:
+            raise NotImplementedError("NARGNNPolicy(decoder=...) is not served: the decode is the Ant System kernels' "
+                                      "(NonAutoregressiveDecoder's heatmap rows)")
+        if env_name not in _TRAIN_ENVS:
+            raise NotImplementedError(f"NARGNNPolicy serves env_name in {_TRAIN_ENVS}, got {env_name!r}")
+        self.temperature = constructive_policy_kw.pop("temperature", 1.0)
+        self.tanh_clipping = constructive_policy_kw.pop("tanh_clipping", 0)
+        self.mask_logits = constructive_policy_kw.pop("mask_logits", True)
+        if constructive_policy_kw:  # (the reference logs "Unused kwargs" and hands them on)
+            raise NotImplementedError(f"NARGNNPolicy does not serve the keywords {sorted(constructive_policy_kw)}")
+        if encoder is None:
+            if env_name == "spctsp":
+                raise NotImplementedError("NARGNNPolicy builds no encoder for spctsp: pass encoder=")
+            cls = TrainableNARGNNDepotEncoder if env_name in DEPOT_ENVS else TrainableNARGNNEncoder
+            encoder = cls(embed_dim=embed_dim, env_name=env_name, init_embedding=init_embedding, edge_embedding=edge_embedding,
+                          graph_network=graph_network, heatmap_generator=heatmap_generator,
+                          num_layers_heatmap_generator=num_layers_heatmap_generator,
+                          num_layers_graph_encoder=num_layers_graph_encoder, act_fn=act_fn, agg_fn=agg_fn,
+                          linear_bias=linear_bias)
+        self.encoder = encoder
+        self.env_name = env_name
+        self.train_decode_type = train_decode_type
+        self.val_decode_type = val_decode_type
+        self.test_decode_type = test_decode_type
+
+    def forward(self, td, env=None, phase: str = "train", calc_reward: bool = True, return_actions: bool = True,
+                return_entropy: bool = False, return_hidden: bool = False, return_init_embeds: bool = False,
+                return_sum_log_likelihood: bool = True, actions=None, max_steps=1_000_000, **decoding_kwargs) -> dict:
+        name, env_name = "NARGNNPolicy", self.env_name
+        if phase not in ("train", "val", "test"):
+            raise NotImplementedError(f"{name} serves phase 'train', 'val' and 'test', got {phase!r}")
+        if return_entropy:
+            raise NotImplementedError(f"{name} does not serve return_entropy=True")
+        kw = dict(decoding_kwargs)
+        decode_type = kw.pop("decode_type", None) or getattr(self, f"{phase}_decode_type")
+        if decode_type not in _DECODE_TYPES:
+            raise NotImplementedError(f"{name} serves the decode types {_DECODE_TYPES}, got {decode_type!r}")
+        temperature = float(kw.pop("temperature", self.temperature))
+        if kw.pop("tanh_clipping", self.tanh_clipping):
+            raise NotImplementedError(f"{name} does not serve tanh_clipping")
+        if not kw.pop("mask_logits", self.mask_logits):
+            raise NotImplementedError(f"{name} does not serve mask_logits=False")
+        top_k, top_p = kw.pop("top_k", 0), kw.pop("top_p", 0.0)
+        K.decoding_filter(top_k, top_p, 2)  # decoding.py:184: "top-p should be in (0, 1]."
+        select_best = bool(kw.pop("select_best", False))
+        kw.pop("store_all_logp", None)
+        multistart = bool(kw.pop("multistart", False)) or "multistart" in decode_type
+        multisample = bool(kw.pop("multisample", False))
+        num_starts, num_samples = kw.pop("num_starts", None), kw.pop("num_samples", None)
+        start_fn = kw.pop("select_start_nodes_fn", None)
+        if kw:
+            raise NotImplementedError(f"{name} does not serve the decoding keywords {sorted(kw)}")
+        # DecodingStrategy.__init__ (decoding.py:237-253)
+        assert not (multistart and multisample), "Using both multistart and multisample is not supported"
+        if num_samples and num_starts:
+            assert not (num_samples > 1 and num_starts > 1), f"num_samples={num_samples} and num_starts={num_starts} are both > 1"
+        if num_samples is not None:
+            multisample = num_samples > 1
+        if num_starts is not None:
+            multistart = num_starts > 1
+        if multistart and env_name not in ("tsp", "cvrp"):
+            raise NotImplementedError(f"decoding_kwargs['multistart'] is not served for {env_name}: every ant starts at the "
+                                      f"depot (multisample); decode type {decode_type!r}")
+        if not multistart and env_name == "tsp":
+            raise NotImplementedError(f"{name} serves tsp with multistart (a multistart decode type or multistart=True, "
+                                      f"num_starts > 1): the ants' kernel starts every tour from a given node")
+        if not td["locs"].is_cuda:
+            raise NotImplementedError(f"{name} runs inside the MI355X kernels only: td['locs'] on {td['locs'].device}")
+        if env is None or isinstance(env, str):
+            from .envs import get_env
+
+            env = get_env(env_name if env is None else env)
+        batch = td["locs"].shape[0]
+        n_rows = num_starts if multistart else num_samples if multisample else 1
+        if actions is not None:  # the 'evaluate' strategy: the rows say how many there are per instance
+            if actions.dim() != 2 or actions.shape[0] == 0 or actions.shape[0] % batch:
+                raise ValueError(f"actions must be [n * B, W] ant-major with B = {batch}, got {tuple(actions.shape)}")
+            n_rows = actions.shape[0] // batch
+        elif n_rows is None:  # pre_decoder_hook (decoding.py:289-290)
+            n_rows = int(env.get_num_starts(td))
+        n_rows = int(n_rows)
+
+        hidden, init_embeds = self.encoder(td)
+        starts = None
+        if multistart and actions is None:  # pre_decoder_hook: called once
+            starts = start_fn(td, env, n_rows) if start_fn is not None else env.select_start_nodes(td, num_starts=n_rows)
+            starts = starts.to(device=hidden.device, dtype=torch.int64).reshape(-1)
+        elif multistart and env_name == "cvrp":
+            starts = actions[:, 0]  # (says that column 0 is a given customer)
+        rolled = heatmap_decode(hidden, td["locs"], n_ants=n_rows, decode_type="greedy" if "greedy" in decode_type else "sampling",
+                                top_k=top_k, top_p=top_p, start_nodes=starts, actions=actions, temperature=temperature,
+                                env_name=env_name, td=td)
+        reward, acts = rolled["reward"], rolled["actions"]
+        ll = rolled["log_likelihood"] if return_sum_log_likelihood else rolled["logps"]
+        if select_best and n_rows > 1 and actions is None:  # DecodingStrategy._select_best: rows are ant-major
+            best = reward.view(n_rows, batch).t().max(dim=-1)[1]
+            rows = best * batch + torch.arange(batch, device=best.device)
+            reward, acts, ll = reward[rows], acts[rows], ll[rows]
+        out = {"reward": reward, "log_likelihood": ll} if calc_reward else {"log_likelihood": ll}
+        if return_actions:
+            out["actions"] = acts
         if return_hidden:
             out["hidden"] = hidden
         if return_init_embeds:
